@@ -1,6 +1,12 @@
 """bench.py -- point-clouds/sec forward, ModelNet40 5k-pt 8x8 SOM (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W         (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full  (the headline plus every figure and check below)
+
+A plain run sets up, spins up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, ...);
+--dump-outputs DIR also writes what the last timed step computed.  Everything else -- further windows, the single-stream
+figure, per-kernel rooflines, the oracle parity check, the other BASELINE configs and arithmetics, the CPU baseline -- runs
+with --full only.
 
 A "step" is one forward pass of the SO-Net ModelNet40 classifier (level-2 Encoder + Classifier
 head, eval mode) over one batch of synthetic clouds already resident in HBM: B clouds per GPU,
@@ -12,7 +18,7 @@ timed region runs --spin-up seconds (default 1 s, reported as `spin_up`) of unti
 and reaches its clocks after 0.3-0.5 s of load (profiles/r04y_first_process.log: 3 % on a 20-step window, 40 % on the
 first 40 training steps of a fresh box).
 
-Extra objects on the line (task contract (4)):
+Extra objects on the line of a --full run (task contract (4)):
   roofline      -- for the dominant kernel of the step (largest share of kernel time): algorithmic
                    flops (or bytes) per launch / its mean launch duration, measured live with HIP
                    events recorded on the launch stream inside the timed region.
@@ -74,7 +80,20 @@ def parse():
     ap.add_argument("--spin-up", type=float, default=1.0,
                     help="seconds of untimed steps before the W warm-up steps of a timed region: an idle MI355X sits at 94 MHz and needs "
                          "0.3-0.5 s of load to reach its clocks (tools/first_process.py); 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: further windows, single-stream figure, per-kernel rooflines, oracle parity check, "
+                         "other BASELINE configs, other arithmetics, CPU baseline (the --no-* options and --windows / --other-steps refine it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; rank 0's shard)")
     return ap.parse_args()
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy in float32 (the caller passes what its timed path hands back, well under 64 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def spawn_ranks(args):
@@ -623,7 +642,22 @@ def train_bench(args, enc, cls, inp, world, rank, dev):
         opt_c.step()
         return loss, nbytes
 
+    # The spin-up runs for a wall time, not a number of steps, and every step moves the weights, the optimizer moments, the BatchNorm
+    # statistics and the dropout generator: the warm-up and timed steps start from the state before it, so that their inputs are the
+    # same in every run with the same arguments (--dump-outputs).  (Their outputs are not bit-reproducible: the BatchNorm-backward
+    # channel sums are float atomics, and Adam turns last-bit differences of small gradients into lr-sized ones.)
+    start = [{k: v.clone() for k, v in m.state_dict().items()} for m in (enc, cls)]
+    rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev))
     _spin_up(step, args.spin_up, chunk=8)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for m, sd in zip((enc, cls), start):
+            for k, v in m.state_dict().items():
+                v.copy_(sd[k])
+    del start
+    torch.set_rng_state(rng[0])
+    torch.cuda.set_rng_state(rng[1], dev)
+    opt_e, opt_c = make_adam(enc), make_adam(cls)
     for _ in range(max(1, args.warmup)):
         loss, nbytes = step()
     dp.barrier()
@@ -641,6 +675,10 @@ def train_bench(args, enc, cls, inp, world, rank, dev):
     ranks = rank_evidence(world, rank, dev, args.batch * args.steps / my_elapsed)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # what a caller of the training step ends up with: its loss and the weights / BatchNorm statistics it leaves behind
+        flat = lambda m: torch.cat([v.detach().float().reshape(-1) for v in m.state_dict().values() if v.is_floating_point()])   # noqa: E731
+        dump_outputs(args.dump_outputs, {"loss": loss, "encoder_state": flat(enc), "classifier_state": flat(cls)})
     B, N = args.batch, args.points
     from sonet_hip import ops
     return ({
@@ -662,6 +700,48 @@ def train_bench(args, enc, cls, inp, world, rank, dev):
                       "buckets": len(reducer.buckets), "exposed_us_per_step": round(exposed_us, 1),
                       "what": "GPU time between the last backward kernel and the arrival of the last bucket (HIP events around the waits)"},
         "range_guard": {"enabled": bool(ops.RANGE_GUARD), "arithmetic_at_end": ops.POINTMLP_PRECISION}})
+
+
+def headline(args, world, rank, dev, elapsed, window_s, P, use_graph, spin_calls, host_pin):
+    """The forward metric's result line: every rank calls it (the times are the max over ranks), `value` is the first timed window."""
+    from sonet_hip import dp, ops
+    B, N = args.batch, args.points
+    my_elapsed = elapsed
+    elapsed = dp.all_reduce_max(elapsed, dev)
+    window_s = [dp.all_reduce_max(w_, dev) for w_ in window_s]
+    ranks = rank_evidence(world, rank, dev, B * args.steps / my_elapsed)
+    dtype = ("bf16 (bf16 storage, one bf16 MFMA per product, f32 accumulate; features within 5e-2 of the f32 oracle, indices exact)" if ops.POINTMLP_PRECISION == "bf16"
+             else "f32 (operands split into fp16 pieces, 3 fp16 MFMAs per product, f32 accumulate; parity 1e-5)" if ops.POINTMLP_PRECISION == "h3"
+             else "f32 (3xbf16-split operands on bf16 MFMA, f32 accumulate; parity 1e-5)" if ops.POINTMLP_PRECISION == "x3"
+             else "f32 (exact f32 MFMA)")
+    line = {
+        "metric": "point-clouds/sec forward, ModelNet40 5k-pt 8x8 SOM",
+        "value": round(world * B * args.steps / elapsed, 2), "unit": "clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": dtype, "data": "synthetic",
+        "config": {"workload": "ModelNet40 classifier forward (level-2 Encoder + Classifier head, eval), %d pts, 8x8 SOM, "
+                               "k=3, som_k=9, surface normals" % N,
+                   "batch_per_gpu": B, "global_batch": B * world, "points": N,
+                   "parallelism": "dp%d: batch shards, no data-path collective" % world},
+        "launch_mode": ("hip-graph replay, %d independent batches in flight on %d streams" % (P, P) if use_graph and P > 1
+                        else "hip-graph replay" if use_graph else "eager"),
+        "spin_up": {"seconds": args.spin_up, "untimed_steps": spin_calls,
+                    "what": "untimed replays before the W warm-up steps: an idle MI355X sits at its lowest clock and needs 0.3-0.5 s of load to "
+                            "leave it (tools/first_process.py, profiles/r04y_first_process.log); --spin-up 0 = none.  Before every timed region "
+                            "sonet_hip.host.freeze_gc() (gc.collect + gc.freeze: no 70 ms generation-2 pause of the Python collector inside a window)"},
+        "ranks": ranks,
+        "host_threads": host_pin if host_pin is not None else {"pinned": False, "what": "one rank: the process keeps the host's cores (the CPU oracle legs run outside every timed window: asserted)"},
+        "in_flight": P, "arithmetic": ops.POINTMLP_PRECISION,
+    }
+    if args.full:
+        # (`value` is the FIRST timed window, as the contract says; the windows of one process spread by several per cent -- clocks --, so
+        #  the median of all of them is printed next to it)
+        line["value_median"] = round(world * B * args.steps / sorted(window_s)[len(window_s) // 2], 2)
+        line["windows"] = {"steps_each": args.steps, "clouds_per_s": [round(world * B * args.steps / w_, 1) for w_ in window_s],
+                           "min": round(world * B * args.steps / max(window_s), 1),
+                           "median": round(world * B * args.steps / sorted(window_s)[len(window_s) // 2], 1),
+                           "what": "whole-job clouds/s of every timed window (max over ranks each); `value` is the first"}
+    return line
 
 
 def main():
@@ -747,7 +827,7 @@ def main():
         # (nothing but the barrier between two windows: the first call of any other operator -- the isfinite check below -- loads its code
         #  object, the GPU idles for a millisecond, and the window behind it starts on sagging clocks: 10-12 % low, docs/findings.md R5.11)
         window_s = [elapsed]
-        for _ in range(max(0, args.windows - 1)):
+        for _ in range(max(0, args.windows - 1) if args.full else 0):
             dp.barrier()
             torch.cuda.synchronize()
             tw = time.perf_counter()
@@ -757,6 +837,12 @@ def main():
                 torch.cuda.synchronize()
             window_s.append(time.perf_counter() - tw)
         assert torch.isfinite(out).all()
+        # (every window ends with the same step on the same graph: `out` holds the last timed step's scores, rank 0's shard)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"score": out})
+        if not args.full:
+            line = headline(args, world, rank, dev, elapsed, window_s, P, use_graph, spin_calls, host_pin)
+            return line if rank == 0 else None
         single = None
         overlap_ok = None
         if use_graph and P > 1:
@@ -856,12 +942,7 @@ def main():
                     dt = time.perf_counter() - t2
                 other[mode] = {"clouds_per_s": round(B * args.steps / dt, 1), "ms_per_step": round(dt * 1e3 / args.steps, 4), "in_flight": 1}
                 del g2
-    my_elapsed = elapsed
-    elapsed = dp.all_reduce_max(elapsed, dev)
-    window_s = [dp.all_reduce_max(w_, dev) for w_ in window_s]
-    ms_per_step = elapsed * 1e3 / args.steps
-    value = world * B * args.steps / elapsed
-    ranks = rank_evidence(world, rank, dev, B * args.steps / my_elapsed)
+    line = headline(args, world, rank, dev, elapsed, window_s, P, use_graph, spin_calls, host_pin)
 
     train_entries = None
     if world > 1 and not args.no_other_configs:
@@ -872,10 +953,7 @@ def main():
         train_entries = other_configs(args, dev, world, rank)
     if rank != 0:
         return
-    dtype = ("bf16 (bf16 storage, one bf16 MFMA per product, f32 accumulate; features within 5e-2 of the f32 oracle, indices exact)" if ops.POINTMLP_PRECISION == "bf16"
-             else "f32 (operands split into fp16 pieces, 3 fp16 MFMAs per product, f32 accumulate; parity 1e-5)" if ops.POINTMLP_PRECISION == "h3"
-             else "f32 (3xbf16-split operands on bf16 MFMA, f32 accumulate; parity 1e-5)" if ops.POINTMLP_PRECISION == "x3"
-             else "f32 (exact f32 MFMA)")
+
     def kernel_entries(summary, steps, suffix=""):
         out = []
         for name, s_ in sorted(summary.items(), key=lambda kv: -kv[1]["total_ms"]):
@@ -947,39 +1025,15 @@ def main():
                                          "frac": round(dom["achieved"] / (tf / 3.0), 4)}
             except Exception as e:  # the probe is a diagnostic: never fail the bench on it
                 roofline["sustained"] = {"error": str(e)}
-    line = {
-        "metric": "point-clouds/sec forward, ModelNet40 5k-pt 8x8 SOM",
-        "value": round(value, 2), "unit": "clouds/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        # (`value` is the FIRST timed window, as the contract says; the windows of one process spread by several per cent -- clocks --, so
-        #  the median of all of them is printed next to it)
-        "value_median": round(world * B * args.steps / sorted(window_s)[len(window_s) // 2], 2),
-        "dtype": dtype, "data": "synthetic",
-        "config": {"workload": "ModelNet40 classifier forward (level-2 Encoder + Classifier head, eval), %d pts, 8x8 SOM, "
-                               "k=3, som_k=9, surface normals" % N,
-                   "batch_per_gpu": B, "global_batch": B * world, "points": N,
-                   "parallelism": "dp%d: batch shards, no data-path collective" % world},
-        "launch_mode": ("hip-graph replay, %d independent batches in flight on %d streams" % (P, P) if use_graph and P > 1
-                        else "hip-graph replay" if use_graph else "eager"),
-        "windows": {"steps_each": args.steps, "clouds_per_s": [round(world * B * args.steps / w_, 1) for w_ in window_s],
-                    "min": round(world * B * args.steps / max(window_s), 1),
-                    "median": round(world * B * args.steps / sorted(window_s)[len(window_s) // 2], 1),
-                    "what": "whole-job clouds/s of every timed window (max over ranks each); `value` is the first"},
-        "spin_up": {"seconds": args.spin_up, "untimed_steps": spin_calls,
-                    "what": "untimed replays before the W warm-up steps: an idle MI355X sits at its lowest clock and needs 0.3-0.5 s of load to "
-                            "leave it (tools/first_process.py, profiles/r04y_first_process.log); --spin-up 0 = none.  Before every timed region "
-                            "sonet_hip.host.freeze_gc() (gc.collect + gc.freeze: no 70 ms generation-2 pause of the Python collector inside a window)"},
-        "ranks": ranks,
-        "host_threads": host_pin if host_pin is not None else {"pinned": False, "what": "one rank: the process keeps the host's cores (the CPU oracle legs run outside every timed window: asserted)"},
-        "in_flight": P, "single_stream": single, "replay_among_others_equals_replay_alone": overlap_ok,
-        "arithmetic": ops.POINTMLP_PRECISION, "other_arithmetics": other,
+    line.update({
+        "single_stream": single, "replay_among_others_equals_replay_alone": overlap_ok, "other_arithmetics": other,
         "range_guard": {"enabled": bool(ops.RANGE_GUARD), "violations": len(range_bad)},
         "eager_instrumented_ms_per_step": round(eager_ms, 4),
         "roofline": roofline,
         "kernel_ms_per_step": round(sum(k["ms_per_step"] for k in kernels), 4),
         "kernels": kernels,
         "kernels_store_path": store_path,
-    }
+    })
     if not args.no_parity_check:
         line["parity_checked"] = parity_check(args, enc, cls, inp, out, enc_cpu, cls_cpu)
     if world == 1 and not args.no_other_configs:

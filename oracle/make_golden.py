@@ -90,6 +90,23 @@ def golden_index_max(ref):
         save("index_max_" + tag, data=data, index=index, K=K, out=fwd(data, index, K))
 
 
+def golden_index_max_differential(ref):
+    """The reference's index_max on the seeded random cases of tests/test_oracle_differential.py (the test regenerates the inputs)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))                           # (its conftest: the golden loader)
+    spec = importlib.util.spec_from_file_location("oracle_differential", os.path.join(ROOT, "tests", "test_oracle_differential.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    fwd, fwd_mt = ref.index_max.forward_cpu, ref.index_max.forward_multi_thread_cpu
+    outs = {}
+    for key, shape, flavour, data, index in m.index_max_cases():
+        K = shape[3]
+        d, i = torch.from_numpy(data), torch.from_numpy(index)
+        out = fwd(d, i, K)
+        assert torch.equal(out, fwd_mt(d, i, K, 2)), key
+        outs[key] = out
+    save("differential_index_max", **outs)  # (not index_max_*: those are the KAT files of tests/test_oracle_golden.py)
+
+
 # ------------------------------------------------------------------------------------------ query_topk
 def golden_query_topk(ref):
     for tag, (B, N, rows, seed, kind) in {"a": (2, 257, 8, 21, "uniform"), "b": (3, 1024, 8, 22, "som"),
@@ -388,6 +405,7 @@ def main():
     ref = ref_harness.import_reference()
     golden_state_dict_keys(ref)
     golden_index_max(ref)
+    golden_index_max_differential(ref)
     golden_query_topk(ref)
     golden_layers(ref)
     golden_classifier(ref, "b2_n256", B=2, N=256, seed=101, node_kind="uniform")

@@ -1,8 +1,9 @@
 """Randomised differential checks of the CPU oracle's C restatement (oracle/sonet_oracle.c), beyond the fixed
 golden fixtures:
 
-* ``index_max`` against the reference's OWN compiled ``index_max.cpp`` (oracle/_ref/index_max.so, which travels to
-  the GPU box) on seeded random shapes with the edge cases the domain has: ties, NaN, +-inf, values <= -1000 (the
+* ``index_max`` against the reference's OWN compiled ``index_max.cpp`` (its outputs stored in
+  tests/golden/differential_index_max.npz by oracle/make_golden.py, and live where oracle/_ref/index_max.so is built)
+  on seeded random shapes with the edge cases the domain has: ties, NaN, +-inf, values <= -1000 (the
   reference's initial running maximum, index_max.cpp:89-91), signed zeros, empty nodes, odd sizes;
 * ``som_query_topk`` / ``som_group`` / ``knn_gather`` against the aten expressions the reference itself evaluates
   (util/som.py:245-267, models/networks.py:128-171, models/operations.py:38-54), written out here with
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import golden
 from oracle import cpu_oracle as O
 
 SHAPES = [(1, 1, 1, 1), (1, 3, 7, 2), (2, 5, 33, 4), (3, 16, 257, 64), (2, 384, 300, 64), (1, 7, 1024, 100), (4, 2, 63, 1)]
@@ -40,16 +42,28 @@ def _index_max_case(seed, B, C, N, K, flavour):
     return data, index
 
 
+def index_max_case_key(shape, flavour):
+    return "x".join(map(str, shape)) + "_" + flavour
+
+
+def index_max_cases():
+    """(key, shape, flavour, data, index) of every seeded case; oracle/make_golden.py stores the reference's outputs on them."""
+    for shape in SHAPES:
+        for flavour in ("plain", "ties", "special", "empty", "low"):
+            B, C, N, K = shape
+            yield (index_max_case_key(shape, flavour), shape, flavour) + _index_max_case(1000 * SHAPES.index(shape) + len(flavour), B, C, N, K, flavour)
+
+
 @pytest.mark.parametrize("flavour", ["plain", "ties", "special", "empty", "low"])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_index_max_restatement_vs_compiled_reference(shape, flavour):
-    if O.ref_module() is None:
-        pytest.skip("oracle/_ref/index_max.so not built")
     B, C, N, K = shape
     data, index = _index_max_case(1000 * SHAPES.index(shape) + len(flavour), B, C, N, K, flavour)
-    ref = O.ref_index_max(data, index, K)
+    ref = golden("differential_index_max")[index_max_case_key(shape, flavour)]    # the compiled reference's output on this case
     np.testing.assert_array_equal(O.index_max(data, index, K), ref)
-    np.testing.assert_array_equal(O.ref_index_max(data, index, K, threads=2), ref)   # index_max.cpp:51-67 agrees with :73-112
+    if O.ref_module() is not None:                                                  # where the reference is built: the live binary too
+        np.testing.assert_array_equal(O.ref_index_max(data, index, K), ref)
+        np.testing.assert_array_equal(O.ref_index_max(data, index, K, threads=2), ref)   # index_max.cpp:51-67 agrees with :73-112
     if flavour == "low":
         assert not ref.any()
 

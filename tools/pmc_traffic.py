@@ -10,6 +10,7 @@ import csv
 import json
 import os
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDE_READERS = ("index_max",)
@@ -18,7 +19,7 @@ NAMES = [("pointresnet_bf16_pool2_kernel", "pointresnet_bf16_pool_L15000"), ("po
 
 
 def load(counter):
-    path = os.path.join(ROOT, "gpurun_out", "pmc_traffic_%s" % counter, "pmc_counter_collection.csv")
+    path = os.path.join(tempfile.gettempdir(), "pmc_traffic_%s" % counter, "pmc_counter_collection.csv")     # (tools/pmc_traffic.sh: $TMPDIR)
     agg = collections.defaultdict(list)
     for r in csv.DictReader(open(path)):
         if r["Counter_Name"] == counter:
