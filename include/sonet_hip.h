@@ -131,6 +131,31 @@ int sonet_som_group_f32(const float *x, const float *sn, const int32_t *min_idx_
                         float *som_node, int32_t *row_max, float *centers, float *x_decentered,
                         float *x_augmented, sonet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * som_train  -- replaces BatchSOM.batch_update / BatchSOM.optimize (the SOM trainer)
+ *   reference: util/som.py:295-366 (one iteration :295-352, the schedule :355-366)
+ * T iterations of the batch SOM for B clouds in ONE launch, one workgroup per cloud (nodes, counts, sums in LDS).
+ * Inputs: x [B][3][N] f32; node0 [B][3][M] f32, or [3][M] shared by every cloud when node0_shared != 0;
+ *         w [T][M][M] f32, w[t][i][j] = neighbourhood weight of node j around centre node i at iteration t (the M x rows x cols
+ *         table of get_weighting_matrix viewed as M x M); lr [T] f32.  The kernel knows no schedule: any (lr, w) sequence runs.
+ * Output: node_out [B][3][M] f32, the nodes after T iterations (T = 0: a copy of node0).
+ * Iteration t, arithmetic contract:
+ *   assign   d = (dx*dx + dy*dy) + dz*dz, separate f32 multiplies / adds (as sonet_som_assign_f32), nodes in ascending id with
+ *            strict '<': ties go to the lowest id (torch.min, util/som.py:320);
+ *   mean_i   = (float)sum_i / ((float)count_i + 1e-5f) (f32 division), r_i = count_i > 0 (util/som.py:326-333);
+ *   update   node_j += sum_{i ascending} ((mean_i - node_j) * r_i * w[t][i][j] * lr[t]), all j from the OLD nodes (:339-352).
+ * Determinism: counts and coordinate sums are 64-bit fixed-point integers (scale 2^S per cloud from its largest |coordinate|,
+ *   quantisation 2^-(61 - ceil(log2 N)) of that magnitude): the result is bit-identical from run to run and does not depend on
+ *   which other clouds share the batch.  Non-finite coordinates give unspecified (but finite-time) results.
+ * Limits: 1 <= N <= SONET_SOM_TRAIN_MAX_POINTS (points are kept in LDS up to ~13k per cloud, re-read from L2 above that),
+ *   1 <= M <= SONET_SOM_TRAIN_MAX_NODES, B >= 1 (grid-stride over clouds), T >= 0; w / lr may be NULL only when T = 0.
+ * Status: SONET_ERR_INVALID_ARG for a NULL pointer, B / N / M < 1, T < 0, N or M above the limit -- returned before any HIP call.
+ * ---------------------------------------------------------------------------------------------- */
+#define SONET_SOM_TRAIN_MAX_NODES 1024
+#define SONET_SOM_TRAIN_MAX_POINTS (1 << 28)
+int sonet_som_train_f32(const float *x, const float *node0, int node0_shared, const float *w, const float *lr,
+                        int T, int B, int N, int M, float *node_out, sonet_stream_t stream);
+
 /* one-hot mask [B][kN][M] i32 from min_idx (util/som.py:254-265); materialised only on request
  * (the reference's Encoder.mask attribute, read by models/segmenter.py:90). */
 int sonet_som_mask_i32(const int32_t *min_idx_i32, int32_t *mask, int B, int kN, int M,

@@ -214,8 +214,12 @@ class Encoder(_PlainAttrs, nn.Module):
         return self._per_point("x_decentered")
 
     # ---- forward ------------------------------------------------------------------------------------
-    def forward(self, x, sn, node, node_knn_I, is_train=False, epoch=None):
+    def forward(self, x, sn, node=None, node_knn_I=None, is_train=False, epoch=None):
         """x, sn: B x 3 x N; node: B x 3 x M; node_knn_I: B x M x K' int64 -> B x feature_num.
+
+        Raw clouds: ``node=None`` builds the SOM nodes from x with ``som_builder.optimize`` (the reference's commented-out
+        models/networks.py:123, one som_train launch); ``node_knn_I=None`` takes the som_k nearest nodes of every node
+        (``ops.knn_self``, what the reference's loader computes with faiss).  Given both, nothing changes.
 
         ``is_train`` is the reference's own signal (models/networks.py:111; ``Model.test_model`` passes False,
         ``Model.optimize`` True -- models/classifier.py:90,104): ``is_train=False`` on an ``eval()`` encoder is an inference
@@ -223,6 +227,8 @@ class Encoder(_PlainAttrs, nn.Module):
         not), which is what selects the fused no-autograd kernels.  The outputs are tagged so that the heads that consume
         them (Classifier / Segmenter / Decoder layers in eval mode) do the same.  ``encoder.inference = False`` restores
         autograd for eval-mode forwards (e.g. fine-tuning with frozen BatchNorm statistics through ``is_train=False``)."""
+        if node is None or node_knn_I is None:
+            node, node_knn_I = self._raw_cloud_nodes(x, node, node_knn_I)
         infer = (not is_train) and (not self.training) and getattr(self, "inference", True) and not x.requires_grad
         if infer and torch.is_grad_enabled():
             with torch.no_grad():
@@ -235,6 +241,15 @@ class Encoder(_PlainAttrs, nn.Module):
             for t in (out, self.first_pn_out_masked_max, self.__dict__.get("_final_pn_out"), self.som_node, self.__dict__.get("_knn_feature_1")):
                 _ops.mark_inference(t)
         return out
+
+    def _raw_cloud_nodes(self, x, node, node_knn_I):
+        with torch.no_grad():
+            if node is None:
+                self.som_builder.optimize(x.detach())
+                node = self.som_builder.node
+            if node_knn_I is None:
+                node_knn_I = _ops.knn_self(node.detach().float().contiguous(), int(self.opt.som_k))
+        return node, node_knn_I
 
     def _wants_dense(self):
         """Does a head read first_pn_out per point copy?  ``want_first_pn_out`` when somebody set it, else: does a Segmenter exist."""

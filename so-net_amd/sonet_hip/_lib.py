@@ -36,6 +36,7 @@ SIGNATURES = {
     "sonet_index_max_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_index_max_gather_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_som_assign_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "sonet_som_train_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "sonet_som_assign_sort_ws_size": [_i, _i, _i, _i],
     "sonet_pointmlp_bf16_pool": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_pointmlp_bf16_pool_xaff": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],

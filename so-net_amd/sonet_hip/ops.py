@@ -293,6 +293,40 @@ def som_assign(x, node, k, want_i64=False):
     return r
 
 
+SOM_TRAIN_MAX_NODES = 1024             # include/sonet_hip.h SONET_SOM_TRAIN_MAX_NODES / _MAX_POINTS
+SOM_TRAIN_MAX_POINTS = 1 << 28
+
+
+def som_train_supported(N, M):
+    """Does ``som_train`` take clouds of N points and M nodes?"""
+    return 1 <= N <= SOM_TRAIN_MAX_POINTS and 1 <= M <= SOM_TRAIN_MAX_NODES
+
+
+def som_train(x, node0, w, lr):
+    """T SOM iterations (util/som.py:295-352) for every cloud in ONE launch (``sonet_som_train_f32``).
+
+    x B x 3 x N f32; node0 B x 3 x M (per cloud) or 3 x M (shared) f32; w T x M x M (or T x M x rows x cols) f32, w[t, i, j] = weight of
+    node j around centre node i; lr T f32 -> nodes B x 3 x M f32.  Bit-identical from run to run and independent of the batch."""
+    _chk(x, "x", torch.float32, 3)
+    _chk(node0, "node0", torch.float32)
+    _chk(w, "w", torch.float32)
+    _chk(lr, "lr", torch.float32, 1)
+    B, D, N = x.shape
+    shared = node0.dim() == 2
+    if D != 3 or node0.dim() not in (2, 3) or node0.shape[-2] != 3 or (not shared and node0.shape[0] != B):
+        raise SonetHipError("x must be B x 3 x N and node0 B x 3 x M or 3 x M, got %s and %s" % (tuple(x.shape), tuple(node0.shape)))
+    M = node0.shape[-1]
+    T = lr.shape[0]
+    if w.dim() < 3 or w.shape[0] != T or w.shape[1] != M or w.numel() != T * M * M:
+        raise SonetHipError("w must be T x M x M (or T x M x rows x cols) with T = len(lr) = %d, M = %d, got %s" % (T, M, tuple(w.shape)))
+    dev = _same_device(x, node0, w, lr)
+    out = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev), _timed("som_train"):
+        check(_lib.load().sonet_som_train_f32(ptr(x), ptr(node0), int(shared), ptr(w) if T else None, ptr(lr) if T else None, T, B, N, M,
+                                              ptr(out), stream_ptr()), "sonet_som_train_f32")
+    return out
+
+
 def som_group(x, sn, a, want_centers=False, want_decentered=False, want_augmented=False):
     """-> dict(som_node Bx3xM, row_max BxM i32, [centers], [x_decentered] Bx3xkN, [x_augmented] Bx6xkN)."""
     _chk(x, "x", torch.float32, 3)

@@ -12,8 +12,9 @@ models/networks.py:104-106,124-144 runs on it unchanged.  What differs is undern
   level-2 Encoder consumes directly; the dense one-hot ``mask`` of the reference API is only built
   when ``query_topk`` / ``query`` is called.
 
-The SOM *trainer* (``batch_update`` / ``optimize``, util/som.py:295-366) is restated on top of the
-same kernel in closed form: for the Gaussian neighbourhood weights w[i, j] the reference's
+The SOM *trainer*: ``optimize`` (util/som.py:355-366) runs the whole schedule in one launch of its own kernel
+(csrc/som_train.hip, ``sonet_som_train_f32``); ``batch_update`` (util/som.py:295-352) is restated on top of the
+assignment kernel in closed form: for the Gaussian neighbourhood weights w[i, j] the reference's
 B x 3 x M x rows x cols broadcast reduces to two M x M products,
     node[:, :, j] += lr * ( sum_i w[i,j] r[b,i] mean[b,:,i]  -  node[b,:,j] * sum_i w[i,j] r[b,i] ).
 """
@@ -70,17 +71,13 @@ class BatchSOM():
     # ------------------------------------------------------------------ node initialisation
     @property
     def node_init_value(self):
-        """dim x M initial node layout from the repulsive potential field (util/potential_field.py).
-
-        Built lazily: the models overwrite ``node`` with dataset nodes on every forward
-        (models/networks.py:124), so the 5 s initialiser only runs if ``node_init`` is used.  The
-        initialiser itself is outside the hot path and is taken from a reference checkout on sys.path.
-        """
+        """dim x M initial node layout from the repulsive potential field (util/potential_field.py, restated in
+        ``potential_field_nodes``).  Built lazily -- the models overwrite ``node`` with dataset nodes on every forward
+        (models/networks.py:124), so it only runs if ``node_init`` / ``optimize`` is used -- and shared by every instance
+        of the same layout."""
         if self._node_init_value is None:
-            from util import potential_field      # resolved through the overlay package path
-            pf = potential_field.PotentialField(self.node_num, self.dim)
-            pf.optimize()
-            self._node_init_value = torch.from_numpy(pf.node.transpose().astype(np.float32))
+            self._node_init_value = torch.from_numpy(potential_field_nodes(self.node_num, self.dim, self.rows, self.cols)
+                                                     .transpose().astype(np.float32))
         return self._node_init_value
 
     def node_init(self, batch_size):
@@ -137,10 +134,130 @@ class BatchSOM():
         mass = torch.matmul(r, w).unsqueeze(1)                                           # sum_i w[i,j] r_i
         self.node = self.node + learning_rate * (pull - self.node * mass)
 
-    def optimize(self, x):
-        self.node_init(x.size()[0])
+    def train_schedule(self):
+        """(lr_t, sigma_t) of optimize at the CURRENT attributes, util/som.py:355-366: int(max_iteration / 3) iterations at
+        (learning_rate, sigma), then max_iteration iterations at learning_rate / (1 + 2 it / max_iteration), sigma / (...)."""
+        lrs, sigmas = [], []
         for _ in range(int(self.max_iteration / 3)):
-            self.batch_update(x, self.learning_rate, self.sigma)
+            lrs.append(self.learning_rate)
+            sigmas.append(self.sigma)
         for it in range(self.max_iteration):
             decay = 1 + 2 * it / self.max_iteration
-            self.batch_update(x, self.learning_rate / decay, self.sigma / decay)
+            lrs.append(self.learning_rate / decay)
+            sigmas.append(self.sigma / decay)
+        return lrs, sigmas
+
+    def train_tables(self, device=None):
+        """-> (lr T, w T x M x M, node_init_value 3 x M), f32 on ``device``, for one som_train launch: w[t] is
+        get_weighting_matrix(sigma_t) (exp(log(w0) * scale_t) in f32 on the device, vectorised over t).  The last schedule,
+        layout and device are cached."""
+        device = torch.device(device) if device is not None else self.init_weighting_matrix.device
+        w0 = self.init_weighting_matrix
+        key = (self.rows, self.cols, self.sigma, self.learning_rate, self.max_iteration, device, w0.data_ptr(), w0._version)
+        cache = self.__dict__.setdefault("_train_tables", {})
+        if key not in cache:
+            lrs, sigmas = self.train_schedule()
+            scales = [1.0 / ((s / self.sigma) ** 2) for s in sigmas]                  # get_weighting_matrix
+            lr = torch.tensor(lrs, dtype=torch.float32, device=device)
+            sc = torch.tensor(scales, dtype=torch.float32, device=device).view(-1, 1, 1, 1)
+            w = torch.exp(torch.log(w0.to(device)).unsqueeze(0) * sc).reshape(len(lrs), self.node_num, self.node_num).contiguous()
+            cache.clear()
+            cache[key] = (lr, w, self.node_init_value.to(device).contiguous())
+        return cache[key]
+
+    def optimize(self, x):
+        """util/som.py:355-366: ``node_init`` then the whole schedule -- in ONE som_train launch (csrc/som_train.hip) when the
+        kernel takes the shape, else in the batch_update loop.  Afterwards ``node`` is B x 3 x M f32 and ``batch_size`` B."""
+        assert x.size()[1] == self.dim
+        xs = x.detach()
+        if xs.dtype != torch.float32 or not xs.is_contiguous():
+            xs = xs.float().contiguous()
+        B, _, N = xs.shape
+        if not _ops.som_train_supported(N, self.node_num):
+            self.node_init(B)
+            for lr, sigma in zip(*self.train_schedule()):
+                self.batch_update(xs, lr, sigma)
+            return
+        lr, w, node0 = self.train_tables(xs.device)
+        self.batch_size = B
+        self.node = _ops.som_train(xs, node0, w, lr)
+
+
+_PF_NODES = {}
+
+
+def potential_field_nodes(node_num, dim, rows=None, cols=None):
+    """M x dim float64 node layout of the reference's PotentialField (util/potential_field.py), restated:
+    a seed-2017 uniform draw in [-1, 1) (a private RandomState: numpy's global generator is left alone), 100 steps of
+    node += 0.01 * force with force_j = wall(node_j) + sum_{k = 0..M-1} (node_j - node_k) / n / n^2, n = |node_j - node_k| + 1e-5,
+    then the row / column reorder.  The per-node accumulation order is the reference's, and |f| is computed like the
+    np.linalg.norm of a 3-vector there (sqrt of BLAS ddot: x0*x0 then fused multiply-adds, emulated exactly below) and n^2 like
+    the power of a numpy scalar (libm pow, which is not always n * n), so the result is bit-identical to the reference's.  The reference reorders on a sqrt(M) x sqrt(M) grid only (it fails for other M); for
+    such M the grid here is rows x cols."""
+    key = (node_num, dim, rows, cols)
+    if key in _PF_NODES:
+        return _PF_NODES[key].copy()
+    M = node_num
+    node = np.random.RandomState(2017).rand(M, dim) * 2 - 1
+    for _ in range(100):
+        force = 0.0 + np.where(np.abs(node) < 0.01, 0.0, -1 * node * M / 1.5)             # wall force first
+        for k in range(M):
+            f = node - node[k]
+            sq = f[:, 0] * f[:, 0]
+            for d in range(1, dim):
+                sq = _fma(f[:, d], f[:, d], sq)
+            fn = np.sqrt(sq) + 0.00001
+            fn2 = np.array([math.pow(v, 2) for v in fn.tolist()])                          # f_norm ** 2 of a numpy scalar = libm pow
+            force += f / fn[:, None] / fn2[:, None]
+        node += force * 0.01
+    node = node[node[:, 0].argsort()]
+    r = int(math.sqrt(M))
+    r, c = (r, r) if r * r == M else (rows, cols)
+    node = node.reshape((r, c, dim))
+    for i in range(r):
+        node[i] = node[i][node[i][:, 1].argsort()]
+    node = node.reshape((M, dim))
+    _PF_NODES[key] = node
+    return node.copy()
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _split(a):
+    c = 134217729.0 * a                       # 2^27 + 1 (Veltkamp)
+    hi = c - (c - a)
+    return hi, a - hi
+
+
+def _fma(a, b, c):
+    """Correctly rounded a * b + c in float64 arrays (Boldo & Melquiond's emulation: exact product, exact sum, the low parts
+    added with round-to-odd, one final rounding)."""
+    p = a * b
+    ah, al = _split(a)
+    bh, bl = _split(b)
+    pe = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    th, tl = _two_sum(c, p)
+    v, e = _two_sum(tl, pe)
+    even = (v.view(np.int64) & 1) == 0
+    v = np.where((e != 0) & even, np.nextafter(v, np.where(e > 0, np.inf, -np.inf)), v)
+    return th + v
+
+
+_BUILDERS = {}
+
+
+def build_nodes(pc, rows=8, cols=8, max_iteration=60):
+    """SOM nodes of raw clouds: pc B x 3 x N (CUDA) -> B x 3 x (rows * cols) f32.  Every cloud gets the schedule of the
+    reference's single-cloud SOM.optimize (util/som.py:150-172, data/build_som), all of them in one launch."""
+    dev = pc.device
+    key = (rows, cols, dev)
+    s = _BUILDERS.get(key)
+    if s is None:
+        s = _BUILDERS[key] = BatchSOM(rows, cols, 3, dev.index if dev.index is not None else 0, pc.shape[0])
+    s.max_iteration = max_iteration
+    s.optimize(pc)
+    return s.node
