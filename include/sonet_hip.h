@@ -180,6 +180,63 @@ int sonet_knn_gather_f32(const float *x, const int64_t *knn_I, float *out,
  * (data/modelnet_shrec_loader.py:116-150,257-259) and KNNModule's dense fallback (models/layers.py:333-337).  K <= 16. */
 int sonet_knn_self_f32(const float *node, int64_t *knn_I, int B, int M, int K, sonet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * assemble_batch  -- replaces the DataLoader item + collate of the loaders (subsample, augment, node kNN)
+ *   reference: data/modelnet_shrec_loader.py:193-271, data/shapenet_loader.py:131-198, data/augmentation.py
+ * Dataset (device-resident): src [6][P] f32 planar (x, y, z, nx, ny, nz of every point of every cloud), offsets [S+1] i64 (CSR:
+ *   cloud s = points offsets[s] .. offsets[s+1]-1, n_s of them), nodes_src [S][M][3] f32 (the reference's som_nodes file layout).
+ * Batch: idx [B] i64, slot b <- cloud s = idx[b].  Outputs: pc, sn [B][3][N] f32; node [B][3][M] f32 (augmented); chosen [B][N] i64
+ *   (global source index of every output point, for per-point labels); knn_I [B][M][K] i64 = sonet_knn_self_f32 on the augmented
+ *   nodes (second launch, same stream), or arange(M) as [B][M][1] when K = 1 (the loaders' som_k < 2 branch).
+ * flags: SONET_BATCH_SHAPENET (recipe shapenet_loader.py, else modelnet / shrec), SONET_BATCH_TRAIN (augment; else only subsample,
+ *   bit-exact gathers), ROT_HORIZONTAL / ROT_PERTURBATION / TRANSLATION (opt.rot_horizontal, opt.rot_perturbation,
+ *   opt.translation_perturbation; modelnet / shrec only).
+ * seed, step: 64-bit values (two's complement bit patterns: a seed of 2^63 or more is passed as seed - 2^64).
+ * Subsample: modelnet / shrec: N of n_s without replacement (N > n_s: the slot is bad, see below); shapenet: N < n_s without
+ *   replacement, else all n_s in order followed by N - n_s draws with replacement.  Without replacement = the N smallest
+ *   (key, index) pairs, emitted in ascending source index (the reference: np.random.choice's order; the network is invariant to it).
+ * Augment (train), float64, one rounding to f32 at the store, row vectors (x @ R), in this order:
+ *   Rh = [[c,0,s],[0,1,0],[-s,0,c]], angle = u * 2 * pi (points, normals, nodes; ROT_HORIZONTAL);
+ *   Rp = Rz @ (Ry @ Rx), angles a_i = clip(0.06 z_i, +-0.18) for x, y, z (ROT_PERTURBATION);
+ *   jitter + clip(0.01 z, +-0.05) on points and normals, + clip(0.04 z, +-0.1) on nodes;  * scale on all three;
+ *   + shift on points and nodes (TRANSLATION).  The shapenet recipe: jitter and scale only.
+ * Random numbers: Philox4x32-10 (Random123 constants), key = (seed & 0xffffffff, seed >> 32), counter words
+ *   (c0, c1, c2, c3) = (step mod 2^32, b, stream, element); block = four u32 words w0..w3.  u32 -> uniform: u(w) = w * 2^-32 in [0, 1).
+ *   Normal triple of a block (Box-Muller, float64): z0 = r_a cos t_a, z1 = r_a sin t_a, z2 = r_b cos t_b with
+ *   r_a = sqrt(-2 log((w0 + 1) 2^-32)), t_a = 2pi u(w1), r_b = sqrt(-2 log((w2 + 1) 2^-32)), t_b = 2pi u(w3).
+ *   stream 0, element e: selection keys, key of source point i = word (i & 3) of element i >> 2;
+ *   stream 1, element e: shapenet extra draws, extra t (output column n_s + t) = word (t & 3) of element t >> 2, index = (w * n_s) >> 32;
+ *   stream 2, element 0: u(w0) = horizontal-angle uniform, scale = 0.8 + (1.2 - 0.8) u(w1);
+ *             element 1: the three perturbation normals (normal triple);
+ *             element 2: shift_c = -0.1 + (0.1 - -0.1) u(w_c), c = 0, 1, 2;
+ *   stream 3 / 4, element j: jitter normals of output point j / of its surface normal (normal triple -> x, y, z);
+ *   stream 5, element m: jitter normals of node m.
+ *   The draws of slot b depend only on (seed, step, b), never on B or the other slots.
+ * Draw record of a slot (float64, D = SONET_BATCH_DRAW_SCALARS + 6 N + 3 M values): [0] horizontal u, [1..3] raw perturbation
+ *   normals, [4] scale, [5..7] shift, then point jitter normals [N][3], normal jitter normals [N][3], node jitter normals [M][3] --
+ *   the values numpy's uniform() / randn(3) / uniform(.8, 1.2) / uniform(-.1, .1, (1, 3)) / randn(N,3) x2 / randn(M,3) return.
+ * Replay (all nullable): replay_idx [B][N] i64 local source indices, in output order; replay_draws [B][D] f64.  Given, they replace
+ *   the generator and run the same code.  draws_out [B][D] f64 receives the draws the launch used (train mode only).
+ * Validation: host-visible arguments are checked before any launch (SONET_ERR_INVALID_ARG: NULL pointer, size < 1, unknown flag,
+ *   rotation / shift flags with the shapenet recipe, K outside [1, M]; SONET_ERR_UNSUPPORTED: K > SONET_BATCH_MAX_K).  idx and offsets
+ *   are device data: the kernel checks them and N <= n_s (modelnet / shrec) per slot, and a replayed index against n_s per point; a
+ *   bad slot / point is written as NaN with chosen = -1 and bad[b] = 1 (nullable; bad[b] = 0 for a good slot).  The python wrapper
+ *   checks idx against the host copy of the offsets before it launches.
+ * ---------------------------------------------------------------------------------------------- */
+#define SONET_BATCH_SHAPENET 1
+#define SONET_BATCH_TRAIN 2
+#define SONET_BATCH_ROT_HORIZONTAL 4
+#define SONET_BATCH_ROT_PERTURBATION 8
+#define SONET_BATCH_TRANSLATION 16
+#define SONET_BATCH_FLAG_MASK 31
+#define SONET_BATCH_DRAW_SCALARS 8
+#define SONET_BATCH_MAX_K 16
+int sonet_assemble_batch_f32(const float *src, long long P, const int64_t *offsets, int S, const float *nodes_src,
+                             const int64_t *idx, int B, int N, int M, int K, int flags, long long seed,
+                             long long step, const int64_t *replay_idx, const double *replay_draws, double *draws_out,
+                             float *pc, float *sn, float *node, int64_t *chosen, int64_t *knn_I, int32_t *bad,
+                             sonet_stream_t stream);
+
 /* KNNModule input in one pass (models/layers.py:313-350): out [B][3+C][M][K] = cat(coord[:, I] - center, feat[:, I]),
  * center [B][3][M] = mean of the K neighbour coordinates (center_avg != 0) or the node itself.  knn_I [B][M][K] i64. */
 int sonet_knn_group_f32(const float *coord, const float *feat, const int64_t *knn_I, int B, int C, int M, int K,

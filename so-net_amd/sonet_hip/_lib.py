@@ -37,6 +37,8 @@ SIGNATURES = {
     "sonet_index_max_gather_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_som_assign_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "sonet_som_train_f32": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "sonet_assemble_batch_f32": [_vp, ctypes.c_longlong, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sonet_som_assign_sort_ws_size": [_i, _i, _i, _i],
     "sonet_pointmlp_bf16_pool": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_pointmlp_bf16_pool_xaff": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],

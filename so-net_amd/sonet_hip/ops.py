@@ -2,6 +2,7 @@
 current stream.  Everything here requires CUDA (ROCm) tensors on an MI355X and raises otherwise
 (mirroring the reference's CHECK_CUDA / CHECK_CONTIGUOUS -> RuntimeError convention,
 models/index_max_ext/index_max.cpp:119-121)."""
+import numpy as np
 import torch
 
 from . import _lib
@@ -570,6 +571,72 @@ def knn_self(node, K):
     with _lib.on_device(dev), _timed("knn_self"):
         check(_lib.load().sonet_knn_self_f32(ptr(node), ptr(out), B, M, int(K), stream_ptr()), "sonet_knn_self_f32")
     return out
+
+
+BATCH_SHAPENET, BATCH_TRAIN, BATCH_ROT_HORIZONTAL, BATCH_ROT_PERTURBATION, BATCH_TRANSLATION = 1, 2, 4, 8, 16   # SONET_BATCH_*
+BATCH_DRAW_SCALARS = 8
+BATCH_MAX_K = 16
+
+
+def _i64(v):
+    v = int(v) & (2 ** 64 - 1)                  # the 64-bit pattern, as the signed long long of the C entry
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def batch_draw_size(N, M):
+    """float64 values in one slot's draw record (include/sonet_hip.h, sonet_assemble_batch_f32)."""
+    return BATCH_DRAW_SCALARS + 6 * N + 3 * M
+
+
+def assemble_batch(src, offsets, nodes_src, idx, N, K, flags, seed, step, replay_idx=None, replay_draws=None, want_draws=False,
+                   sizes=None):
+    """Subsample + augment B clouds of a device-resident dataset in one launch, then the node self-kNN (``sonet_assemble_batch_f32``).
+
+    src 6 x P f32 (planar x, y, z, nx, ny, nz); offsets S+1 i64 (CSR); nodes_src S x M x 3 f32; idx B i64 -> dict(pc, sn B x 3 x N f32,
+    node B x 3 x M f32, chosen B x N i64 (global source index), knn_I B x M x K i64, bad B i32 [, draws B x D f64]).
+    replay_idx B x N i64 (local indices) / replay_draws B x D f64 replace the generator.  ``sizes`` (host: the S cloud sizes) makes idx
+    and N <= n_s (modelnet / shrec) checked here before the launch; idx is then read back to the host when it lives on the device."""
+    _chk(src, "src", torch.float32, 2)
+    _chk(offsets, "offsets", torch.int64, 1)
+    _chk(nodes_src, "nodes_src", torch.float32, 3)
+    _chk(idx, "idx", torch.int64, 1)
+    S, M = nodes_src.shape[0], nodes_src.shape[1]
+    B, N, K, flags = idx.shape[0], int(N), int(K), int(flags)
+    if src.shape[0] != 6 or nodes_src.shape[2] != 3 or offsets.shape[0] != S + 1:
+        raise SonetHipError("src must be 6 x P, nodes_src S x M x 3 and offsets S+1, got %s, %s, %s"
+                            % (tuple(src.shape), tuple(nodes_src.shape), tuple(offsets.shape)))
+    if B < 1 or N < 1 or not 1 <= K <= min(M, BATCH_MAX_K):
+        raise SonetHipError("need B >= 1, N >= 1 and 1 <= K <= min(M, %d), got B=%d N=%d K=%d M=%d" % (BATCH_MAX_K, B, N, K, M))
+    if sizes is not None:
+        ii, sizes = idx.cpu().numpy(), np.asarray(sizes)
+        if ii.min() < 0 or ii.max() >= S:
+            raise SonetHipError("idx out of range [0, %d): min %d max %d" % (S, ii.min(), ii.max()))
+        smallest = int(sizes[ii].min())
+        if not flags & BATCH_SHAPENET and smallest < N:
+            raise SonetHipError("N=%d > n_s=%d points of a cloud in the batch (modelnet / shrec sample without replacement)" % (N, smallest))
+    dev = _same_device(src, offsets, nodes_src, idx, replay_idx, replay_draws)
+    D = batch_draw_size(N, M)
+    if replay_idx is not None:
+        _chk(replay_idx, "replay_idx", torch.int64)
+        if tuple(replay_idx.shape) != (B, N):
+            raise SonetHipError("replay_idx must be B x N = %s, got %s" % ((B, N), tuple(replay_idx.shape)))
+    if replay_draws is not None:
+        _chk(replay_draws, "replay_draws", torch.float64)
+        if tuple(replay_draws.shape) != (B, D):
+            raise SonetHipError("replay_draws must be B x D = %s, got %s" % ((B, D), tuple(replay_draws.shape)))
+    f32 = dict(dtype=torch.float32, device=dev)
+    r = dict(pc=torch.empty((B, 3, N), **f32), sn=torch.empty((B, 3, N), **f32), node=torch.empty((B, 3, M), **f32),
+             chosen=torch.empty((B, N), dtype=torch.int64, device=dev), knn_I=torch.empty((B, M, K), dtype=torch.int64, device=dev),
+             bad=torch.empty((B,), dtype=torch.int32, device=dev))
+    if want_draws:
+        r["draws"] = torch.zeros((B, D), dtype=torch.float64, device=dev)
+    with _lib.on_device(dev), _timed("assemble_batch"):
+        check(_lib.load().sonet_assemble_batch_f32(
+            ptr(src), src.shape[1], ptr(offsets), S, ptr(nodes_src), ptr(idx), B, N, M, K, flags, _i64(seed), _i64(step), ptr(replay_idx) if replay_idx is not None else None,
+            ptr(replay_draws) if replay_draws is not None else None, ptr(r["draws"]) if want_draws else None,
+            ptr(r["pc"]), ptr(r["sn"]), ptr(r["node"]), ptr(r["chosen"]), ptr(r["knn_I"]), ptr(r["bad"]), stream_ptr()),
+            "sonet_assemble_batch_f32")
+    return r
 
 
 def knn_group(coord, feat, knn_I, center_avg):
