@@ -355,7 +355,10 @@ def test_classifier_training_step_bf16(fixture):
     # sub-gradient, not a noisy copy of the float64 one (0.73-0.81 at N=5000, where a node's pool has ~700 candidates).  Bar here:
     # same direction (cosine above the fixture's measured floor, below).  What pins the bf16 backward arithmetic itself are test_bf16_layer_backward_vs_float64 (1-2e-2
     # per layer) and test_bf16_first_pointnet_backward_with_fixed_routing_vs_float64 (the whole first PointNet incl. the sparse
-    # pooled dgrad / wgrad, gathered at the same winners) above.
+    # pooled dgrad / wgrad, gathered at the same winners) above.  The end-to-end gate of every bf16 gradient is
+    # tests/test_gpu_bf16_forced_routing.py: this run's routing, ReLU patterns and stored bf16 tensors forced on the float64 twin,
+    # each stored tensor within bf16 rounding of the twin's exact value and every parameter gradient within 3e-4 rel-rms.  A 1 % error
+    # in an input-gradient launch, a weight gradient 2^-7 too large or a dropped BatchNorm-backward term fails there and passes here.
     cosines = {}
     for k in [k[7:] for k in g.files if k.startswith("grad64/") and not k.startswith("grad64/cls.")]:
         truth = g["grad64/" + k].astype(np.float64)

@@ -782,10 +782,20 @@ def _capture_stage(enc):
     return cap
 
 
+def _lastdim_max_node(t):
+    """The _LastDimMax autograd node that produced ``t`` -- through the casts behind it (bf16: ``feature.float()``, models/networks.py:436)."""
+    node = t.grad_fn
+    while node is not None and type(node).__name__ != "_LastDimMaxBackward":
+        assert type(node).__name__.startswith("ToCopyBackward"), type(node).__name__
+        node = node.next_functions[0][0]
+    assert node is not None, "no _LastDimMax node behind the tensor"
+    return node
+
+
 def _routing_of(enc, feat):
     """The arg-max positions this forward took at pools 2 and 3 (saved by the two _LastDimMax nodes; read BEFORE backward frees them)."""
-    p2 = enc.knn_feature_1.grad_fn.saved_tensors[0]
-    p3 = feat.grad_fn.saved_tensors[0]
+    p2 = _lastdim_max_node(enc.knn_feature_1).saved_tensors[0]
+    p3 = _lastdim_max_node(feat).saved_tensors[0]
     return dict(pool2=p2.detach().long().clone(), pool3=p3.detach().long().clone(), som_node=enc.som_node.detach().clone())
 
 
@@ -827,15 +837,18 @@ def _relu_masks_of(loss, enc, cls):
     return masks
 
 
-def _f64_step(enc, cls, g, cap, forced):
-    """tests/f64_classifier.py on the GPU in float64, fed with the SOM stage of the run under test; ``forced``: its routing too."""
+def _f64_step(enc, cls, g, cap, forced, rounding=None, stored=None, stored_grads=None, pooled_dgrad="mfma"):
+    """tests/f64_classifier.py on the GPU in float64, fed with the SOM stage of the run under test; ``forced``: its routing too;
+    ``rounding`` / ``stored`` / ``stored_grads`` / ``pooled_dgrad``: passed on (``"bf16"``: the twin rounds where the bf16 step rounds)."""
     import f64_classifier as F64
     assert "x_aug" in cap, "the training forward did not go through first_pointnet.forward_pooled"
     e64 = F64.leaf_params(enc.state_dict(), DEV)
     c64 = F64.leaf_params(cls.state_dict(), DEV)
     stage = dict(x_aug=cap["x_aug"], min_idx=cap["min_idx"], row_max=cap["row_max"], som_node=cap["som_node"], pos0=cap["pos0"])
     route = dict(pool1=cap["pool1"], pool2=cap["pool2"], pool3=cap["pool3"]) if forced else None
-    return F64.train_step(e64, c64, cu(g["label"]), cu(g["node_knn_I"]), stage=stage, route=route, masks=cap.get("masks") if forced else None)
+    return F64.train_step(e64, c64, cu(g["label"]), cu(g["node_knn_I"]), stage=stage, route=route, masks=cap.get("masks") if forced else None,
+                          rounding=rounding, stored=stored,
+                          stored_grads=stored_grads, pooled_dgrad=pooled_dgrad)
 
 
 @pytest.mark.parametrize("fixture", ["train_step_b16_n512", "train_step_b8_n5000"])       # the second: configs[1] / configs[4] point count

@@ -4,6 +4,11 @@
 the table behind tests/test_gpu_parity.py::test_training_gradients_with_forced_routing.
 
     python tools/grad_forced_routing.py [--modes h3,x3,f32] [--fixtures train_step_b16_n512,train_step_b8_n5000] [--env KEY=VAL ...]
+
+``--modes bf16``: the bf16 step against the twin with ``rounding="bf16"`` and the run's rounding decisions forced (and, for scale, against
+the plain float64 twin with the routing forced), for every bf16
+switch setting of ``--fusions`` (default: every fusion on; off: tests/test_gpu_bf16_forced_routing.py FUSIONS) -- the table behind
+tests/test_gpu_bf16_forced_routing.py::test_bf16_training_gradients_with_forced_routing (``synthetic_b36_n5000`` is its third case).
 """
 import argparse
 import os
@@ -17,6 +22,7 @@ sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
 ap.add_argument("--modes", default="h3,x3,f32")
 ap.add_argument("--fixtures", default="train_step_b16_n512,train_step_b8_n5000")
+ap.add_argument("--fusions", default="default,off", help="bf16 mode: the switch settings")
 ap.add_argument("--set", nargs="*", default=[], help="ops switches, e.g. DEFER_WGRAD_JOIN=0 BNB_ON_LOAD=0")
 args = ap.parse_args()
 
@@ -32,10 +38,50 @@ for kv in args.set:
     setattr(ops, k, v not in ("0", "False", "false"))
     print("ops.%s = %s" % (k, getattr(ops, k)))
 DEV = T.DEV
+
+
+def bf16_case(fixture, fusions):
+    """The bf16 step against the bf16 twin (and the plain float64 twin): the per-parameter table, loss, feature and running statistics."""
+    import test_gpu_bf16_forced_routing as BF
+    res = BF.run_bf16_forced(fixture, fusions)
+    r, cap = res["r"], res["cap"]
+    rel = BF.grad_residuals(res)
+    plain = BF.grad_residuals(dict(res, r=T._f64_step(res["enc"], res["cls"], res["g"], cap, forced=True)))
+    print("\n== %s  bf16 %s  carry=%s  loss %.9f (bf16 twin %.9f, rel %.2e)  masks %d layers" % (
+        fixture, "default" if fusions else "fusions_off", res["carry"], float(res["loss"]), float(r["loss"]),
+        abs(float(res["loss"]) - float(r["loss"])) / abs(float(r["loss"])), len(cap["masks"])))
+    print("   kernels:", " ".join(sorted(res["names"])))
+    print("   stored bf16 tensors vs the twin's exact values: worst ulps of max(|value|, rms) / rel-rms / relative scale error")
+    for k, v in sorted(r["snap"].items()):
+        print("     %-32s %6.3f  %.3e  %+.2e" % (k, v["ulps"], v["rel"], v["scale"]))
+    for what, f_got, f_ref in (("pool1", res["stages"]["pool1"], r["sites"]["pool1"]), ("pool2", res["stages"]["pool2"], r["sites"]["pool2"]),
+                               ("feature", res["feature"], r["feature"])):
+        f_got = f_got.double()
+        d = (f_got - f_ref).abs()
+        print("   %-8s rel-rms %.3e  worst |d| / max(|ref|, rms) %.3e  elements that differ %d / %d" % (
+            what, float((f_got - f_ref).norm() / f_ref.norm()), float((d / torch.maximum(f_ref.abs(), f_ref.pow(2).mean().sqrt())).max()),
+            int((d > 0).sum()), d.numel()))
+    worst_run = ("", 0.0)
+    for k, (want, got) in BF.expected_running(res).items():
+        want, got = want.double(), got.double()
+        e = float(((got - want).abs() / torch.maximum(want.abs(), want.pow(2).mean().sqrt())).max())
+        worst_run = max(worst_run, (k, e), key=lambda kv: kv[1])
+    print("   running statistics: worst err / max(|ref|, rms) %.3e (%s)" % (worst_run[1], worst_run[0]))
+    print("   %-45s %-11s %s" % ("parameter (rel-rms vs)", "bf16 twin", "plain f64 twin"))
+    for k, v in sorted(rel.items(), key=lambda kv: -kv[1]):
+        print("   %-45s %.3e   %.3e" % (k, v, plain.get(k, float("nan"))))
+    print("   worst %.3e over %d parameters (plain f64 twin: %.3e)" % (max(rel.values()), len(rel), max(plain.values())))
+
+
 for fixture in args.fixtures.split(","):
-    g = T.golden(fixture)
-    B, N, seed = int(g["B"]), int(g["N"]), int(g["seed"])
     for mode in args.modes.split(","):
+        if mode == "bf16":
+            for fu in args.fusions.split(","):
+                bf16_case(fixture, fu == "default")
+                torch.cuda.empty_cache()
+            continue
+        g = T.golden(fixture)
+        B, N, seed = int(g["B"]), int(g["N"]), int(g["seed"])
         opt = Namespace(gpu_id=0, device=torch.device(DEV), batch_size=B, input_pc_num=N, surface_normal=True, feature_num=1024,
                         activation="relu", normalization="batch", dropout=0.0, node_num=64, k=3, som_k=9, som_k_type="avg",
                         bn_momentum=0.1, bn_momentum_decay_step=None, bn_momentum_decay=0.6, classes=40)
