@@ -391,6 +391,12 @@ int sonet_lastdim_max_bwd_bf16(const uint16_t *g, const int32_t *idx, uint16_t *
 size_t sonet_knn_gather_bwd_ws_size(int B, int M, int K);
 int sonet_knn_gather_bwd_f32(const float *g, const int64_t *knn_I, float *gx, void *ws, int B, int C, int M, int K, sonet_stream_t stream);
 int sonet_knn_gather_bwd_bf16(const uint16_t *g, const int64_t *knn_I, float *gx, void *ws, int B, int C, int M, int K, sonet_stream_t stream);
+/* sonet_node_gather_bwd_*: backward of the segmenter's back-broadcast (models/segmenter.py:96-98, sonet_node_gather_f32): gx[b][c][m] = sum of
+ *   g[b][c][j] over the columns j with ids[b][j] == m, in ascending j (f32 accumulation, bitwise reproducible); g B x C x L, ids B x L,
+ *   gx B x C x M; ws: sonet_node_gather_bwd_ws_size(B, M, L) bytes; M <= 1024; ids outside [0, M) contribute nowhere. */
+size_t sonet_node_gather_bwd_ws_size(int B, int M, int L);
+int sonet_node_gather_bwd_f32(const float *g, const int32_t *ids, float *gx, void *ws, int B, int C, int M, int L, sonet_stream_t stream);
+int sonet_node_gather_bwd_bf16(const uint16_t *g, const int32_t *ids, float *gx, void *ws, int B, int C, int M, int L, sonet_stream_t stream);
 
 /* The same layer with bf16 STORAGE and bf16 MFMA (BASELINE configs[1] "bf16"; the reference is f32-only, so this is the
  * reduced-precision twin of models/layers.py:282-296, not a bit-compatible replacement): x1, x2, y are bfloat16 bit

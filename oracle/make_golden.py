@@ -337,6 +337,108 @@ def golden_segmenter(ref, tag, B, N, seed):
          segmenter_keys=np.array(sorted(model.segmenter.state_dict().keys())))
 
 
+SEG_GRAD_KEYS = GRAD_KEYS + ["seg.layer%d.%s" % (i, p) for i in range(1, 6)
+                             for p in (("conv.weight", "conv.bias", "norm.weight", "norm.bias") if i < 5 else ("conv.weight", "conv.bias"))]
+SEG_SUB = 2048                                    # values kept per gradient tensor: the fixture stays under 1 MiB
+
+
+def golden_seg_train_step(ref, tag, B, N, seed):
+    """One part-segmentation training step of the reference (models/segmenter.py:113-124, ``Model.optimize``) with the part-seg defaults
+    (part-seg/options.py: classes 50, som_k_type "center", k 3, som_k 9, surface normals), dropout off so it is deterministic, run twice:
+    as it is in float32 and the SAME code in float64.  Inputs as ``golden_segmenter`` draws them (a part label per cloud, a part id per
+    point).  Recorded as ``golden_train_step`` records the classifier step: loss / ``loss64``, the positions of the three pools
+    (``route64/pool{1,2,3}``; the float32 run's as ``route32/pool*_at`` / ``_val``: the flat indices where it took another position and
+    the position it took there -- the full arrays would push the fixture over 1 MiB), ``grad/`` / ``grad64/`` / ``after/`` (parameters after the Adam steps) / ``ref32_dev/`` for
+    ``SEG_GRAD_KEYS`` (segmenter keys prefixed "seg."; strided samples of at most ~``SEG_SUB`` values), ``bn/`` running statistics and
+    ``dead_grad_count`` (encoder and segmenter parameters left without a gradient).
+
+    The recorder tells the two 3-D float ``torch.max`` calls apart: the global max over the nodes (models/networks.py:197, pool 3) and
+    the ``encoder.mask`` argmax of models/segmenter.py:90, which comes after it and is not a pool.
+    Shims of the float64 run (dtypes only, no arithmetic): the modules and the input placeholders are cast with ``.double()`` as in
+    ``golden_train_step``; the index_max extension reads float32 (cast at the shim, indices only).  ``Segmenter.forward`` builds
+    ``label_onehot`` as a FloatTensor (networks.py:289); its 0 / 1 values are exact in float32 and ``torch.cat`` promotes it to float64,
+    so it needs none."""
+    def run(dtype):
+        log = {}
+        orig_max = torch.max
+        opt = ref_harness.make_opt(batch_size=B, input_pc_num=N, dropout=0.0, classes=50, som_k_type="center", k=3, som_k=9,
+                                   surface_normal=True)
+        model = ref.segmenter.Model(opt)
+
+        def recording_max(*a, **k):
+            r = orig_max(*a, **k)
+            if (isinstance(r, tuple) and a and torch.is_tensor(a[0]) and a[0].is_floating_point() and a[0].dim() in (3, 4)
+                    and a[0] is not getattr(model.encoder, "mask", None)):
+                log["pool2" if a[0].dim() == 4 else "pool3"] = r[1].clone()
+            return r
+        synth.fill_state_dict_(model.encoder.state_dict(), seed=seed)
+        synth.fill_state_dict_(model.segmenter.state_dict(), seed=seed + 1)
+        inp = synth.make_inputs(B, N, M=opt.node_num, som_k=opt.som_k, seed=seed, node_kind="som")
+        g = torch.Generator().manual_seed(seed)
+        label = torch.randint(0, 16, (B,), generator=g)
+        seg = torch.randint(0, 50, (B, N), generator=g)
+        if dtype == torch.float64:
+            model.encoder.double(); model.segmenter.double()
+            model.input_pc, model.input_sn, model.input_node = model.input_pc.double(), model.input_sn.double(), model.input_node.double()
+            model.encoder.som_builder.node = model.encoder.som_builder.node.double()
+            model.optimizer_encoder = torch.optim.Adam(model.encoder.parameters(), lr=0.001, betas=(0.9, 0.999), weight_decay=0)
+            model.optimizer_segmenter = torch.optim.Adam(model.segmenter.parameters(), lr=0.001, betas=(0.9, 0.999), weight_decay=0)
+        ext = ref.index_max
+        fwd = ext.forward_cpu
+        ref.networks.index_max = type(ext)("index_max")
+
+        def forward_cuda(d, i, K):
+            out = fwd(d.float().contiguous(), i, K)
+            log["pool1_raw"] = out.clone()
+            return out
+        ref.networks.index_max.forward_cuda = forward_cuda
+        model.set_input(inp["pc"].to(dtype), inp["sn"].to(dtype), label, seg, inp["node"].to(dtype), inp["node_knn_I"])
+        torch.max = recording_max
+        try:
+            with ref_harness.sorted_topk():
+                model.optimize(epoch=0)
+        finally:
+            torch.max = orig_max
+            ref.networks.index_max = ref.index_max
+        row_max = orig_max(model.encoder.mask, dim=1)[0]                            # util/som.py:267
+        log["pool1"] = log.pop("pool1_raw").long() * row_max.unsqueeze(1).long()    # models/networks.py:185
+        return model, dict(inp, label=label, seg=seg), log
+
+    model, inp, route32 = run(torch.float32)
+    model64, _, route64 = run(torch.float64)
+    arrays = dict(B=B, N=N, seed=seed, sub_n=SEG_SUB, pc=inp["pc"], sn=inp["sn"], node=inp["node"], node_knn_I=inp["node_knn_I"],
+                  label=inp["label"], seg=inp["seg"], loss=model.loss_segmenter.detach(), loss64=model64.loss_segmenter.detach())
+    assert int(route64["pool1"].max()) < 32768 and int(route64["pool2"].max()) < 128 and int(route64["pool3"].max()) < 128
+    for pool, dt in (("pool1", torch.int16), ("pool2", torch.int8), ("pool3", torch.int8)):
+        arrays["route64/" + pool] = route64[pool].to(dt)
+        at = (route32[pool] != route64[pool]).flatten().nonzero().flatten()         # route32/: where it differs from route64/ (lossless)
+        arrays["route32/%s_at" % pool] = at.to(torch.int32)
+        arrays["route32/%s_val" % pool] = route32[pool].flatten()[at].to(dt)
+
+    def params(m):
+        return dict([(k, p) for k, p in m.encoder.named_parameters()] + [("seg." + k, p) for k, p in m.segmenter.named_parameters()])
+
+    def sub(t):
+        f = t.detach().flatten()
+        return f[::max(1, f.numel() // SEG_SUB)]
+    p32, p64 = params(model), params(model64)
+    for k in SEG_GRAD_KEYS:
+        arrays["grad/" + k] = sub(p32[k].grad)
+        arrays["grad64/" + k] = sub(p64[k].grad)
+        arrays["after/" + k] = sub(p32[k])
+        a, r = p32[k].grad.double(), p64[k].grad
+        arrays["ref32_dev/" + k] = ((a - r).pow(2).mean().sqrt() / r.pow(2).mean().sqrt().clamp_min(1e-300)).item()
+        print("   %-45s float32 reference vs its own float64 run: rel-rms %.2e" % (k, arrays["ref32_dev/" + k]))
+    arrays["dead_grad_count"] = sum(1 for p in p32.values() if p.grad is None)
+    sd = dict(model.encoder.state_dict())
+    sd.update({"seg." + k: v for k, v in model.segmenter.state_dict().items()})
+    for k in ("first_pointnet.layers.1.norm.running_mean", "first_pointnet.layers.1.norm.running_var", "knnlayer.layers.0.norm.running_var",
+              "final_pointnet.layers.0.norm.running_mean", "seg.layer1.norm.running_mean", "seg.layer1.norm.running_var",
+              "seg.layer4.norm.running_mean", "seg.layer4.norm.running_var"):
+        arrays["bn/" + k] = sd[k]
+    save("seg_train_step_" + tag, **arrays)
+
+
 def golden_autoencoder(ref, tag, B, N, seed):
     """Reference autoencoder (models/autoencoder.py:62-125): encoder -> FC + conv decoder -> multi-resolution Chamfer
     loss, eval forward plus the gradient of the loss w.r.t. the predicted clouds.  The nearest-neighbour search is the
@@ -399,6 +501,11 @@ def main():
         torch.manual_seed(0)
         torch.set_num_threads(8)
         golden_train_step(ref_harness.import_reference(), "b8_n5000", B=8, N=5000, seed=203)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "seg_train":       # own mode: the part-segmentation training step (part-seg's batch of 8)
+        torch.manual_seed(0)
+        torch.set_num_threads(8)
+        golden_seg_train_step(ref_harness.import_reference(), "b8_n512", B=8, N=512, seed=501)
         return
     torch.manual_seed(0)
     torch.set_num_threads(8)

@@ -98,6 +98,9 @@ class MyBatchNorm2d(_DecayingBatchNorm):
 # ---------------------------------------------------------------------------------------------------
 # fused conv1x1 + affine + relu
 # ---------------------------------------------------------------------------------------------------
+_F32_DGRAD_ROWS = 1024                                # output rows of one exact-f32 input-gradient launch (the kernel's pass table)
+
+
 def _pack_transposed(weight2d, C1, C2):
     """Packed W[:, :C1]^T (and W[:, C1:]^T) for the dgrad launches: g_x = W^T g_raw is the same fused 1x1-conv
     kernel with the roles of the channel axes swapped."""
@@ -133,7 +136,12 @@ def _pack_transposed(weight2d, C1, C2):
             wt = weight2d[:, lo:lo + Ci].t().contiguous().float()              # Ci x Cout
             if Cp != Ci:
                 wt = torch.cat((wt, wt.new_zeros(Cp - Ci, wt.shape[1])), dim=0)
-            out.append((_ops.pointmlp_pack(wt, m), Ci, Cp))
+            if m == "f32" and Cp > _F32_DGRAD_ROWS:
+                # the exact-f32 kernel holds at most 1024 output channels per pass (32 tiles): a wider input gradient -- the segmenter's
+                # 3356-channel layer 1 -- is one launch per block of 1024 rows (``_dgrad`` concatenates them)
+                out.append(([_ops.pointmlp_pack(wt[r:r + _F32_DGRAD_ROWS].contiguous(), m) for r in range(0, Cp, _F32_DGRAD_ROWS)], Ci, Cp))
+            else:
+                out.append((_ops.pointmlp_pack(wt, m), Ci, Cp))
         lo += Ci
     return out
 
@@ -142,6 +150,10 @@ def _dgrad(g_raw, pack, acc=None):
     """W^T . g_raw through the fused 1x1-conv kernel (pack from _pack_transposed).  acc (bf16 packs; the caller checked ``_dgrad_acc_ok``):
     another gradient of the same tensor, added by the store of the launch."""
     wpt, Ci, Cp = pack
+    if isinstance(wpt, list):                         # exact-f32 pack in blocks of _F32_DGRAD_ROWS output rows (_pack_transposed)
+        y = torch.cat([_dgrad(g_raw, (w, w_rows, w_rows))
+                       for w, w_rows in zip(wpt, [min(_F32_DGRAD_ROWS, Cp - r) for r in range(0, Cp, _F32_DGRAD_ROWS)])], dim=1)
+        return y if Cp == Ci else y[:, :Ci]
     want = torch.bfloat16 if wpt.dtype == torch.int16 else torch.float32
     if g_raw.dtype != want:
         g_raw = g_raw.to(want)
@@ -151,7 +163,7 @@ def _dgrad(g_raw, pack, acc=None):
 
 def _dgrad_acc_ok(g_raw, pack, acc):
     wpt, Ci, Cp = pack
-    return (wpt.dtype == torch.int16 and Cp == Ci and acc.dtype == torch.bfloat16 and acc.is_contiguous() and g_raw.shape[2] % 2 == 0
+    return (not isinstance(wpt, list) and wpt.dtype == torch.int16 and Cp == Ci and acc.dtype == torch.bfloat16 and acc.is_contiguous() and g_raw.shape[2] % 2 == 0
             and tuple(acc.shape) == (g_raw.shape[0], Cp, g_raw.shape[2]))
 
 
@@ -579,7 +591,11 @@ class _PooledLastLayerFn(torch.autograd.Function):
         if not sparse:
             G = g_y.contiguous().clone() if g_mm is not None else g_y.contiguous()
             if g_mm is not None:
-                G.scatter_add_(2, gi.long(), g_mm.to(G.dtype))            # the gather's backward (duplicates accumulate)
+                # the gather's backward: the occupied nodes' positions are distinct; every channel of an EMPTY node gathers position 0,
+                # and those are added as one fixed-order sum (an atomic scatter of several values onto one element is not reproducible)
+                occ = row_max.unsqueeze(1) > 0
+                G.scatter_add_(2, gi.long(), (g_mm * occ).to(G.dtype))
+                G[:, :, 0] += (g_mm * (~occ)).sum(dim=2).to(G.dtype)
         g_bias = None
         if ctx.needs_input_grad[3]:
             # sparse: the gradient of first_pn_out is the scatter of g_mm and nothing else (never built): its sum is the sum of g_mm

@@ -42,9 +42,16 @@ class CrossEntropyLossSeg(nn.Module):
     def __init__(self, weight=None, size_average=True):
         super().__init__()
         self.nll_loss = nn.NLLLoss(weight, reduction="mean" if size_average else "sum")
+        self.size_average = size_average
 
     def forward(self, inputs, targets):
-        return self.nll_loss(F.log_softmax(inputs.unsqueeze(3), dim=1), targets.unsqueeze(2))
+        logp = F.log_softmax(inputs.unsqueeze(3), dim=1)
+        if logp.is_cuda and self.nll_loss.weight is None:
+            # the same sum as a gather + a plain reduction: on the GPU NLLLoss's 4-D forward adds its block partials atomically, so its
+            # last bit changes from run to run (the gather's backward writes every element once: deterministic)
+            picked = -torch.gather(logp, 1, targets.unsqueeze(1).unsqueeze(3)).squeeze(1)
+            return picked.mean() if self.size_average else picked.sum()
+        return self.nll_loss(logp, targets.unsqueeze(2))
 
 
 class ChamferLoss(nn.Module):

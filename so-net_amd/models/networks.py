@@ -624,7 +624,7 @@ def segmentation_forward(encoder, segmenter, pc, sn, label, node, node_knn_I, is
     """Model.forward of the part-segmentation task (models/segmenter.py:79-109) on the level-2 encoder:
     the reference recovers the node of every point copy with argmax over the one-hot mask and gathers three
     node-level feature maps back to the kN copies; here the int32 ids are already there and one kernel does
-    each gather (autograd falls back to torch.gather when gradients are needed)."""
+    each gather (in training with a fixed-order backward: ops.node_gather_autograd)."""
     encoder.want_first_pn_out = True                  # layer 1 consumes first_pn_out per point copy
     # ... pre-split when the head runs its third-generation chain (the fused first PointNet then writes the P16 planes itself)
     encoder.first_pointnet.emit_p16 = bool(segmenter._nodewise_ok() and getattr(segmenter, "nodewise", True) and segmenter.layer1._p16_ok()
@@ -653,10 +653,11 @@ def _segmentation_head(encoder, segmenter, pc, sn, label, feature):
                                           first_pn_out_p16=p16)
     need_grad = torch.is_grad_enabled() and encoder.first_pn_out_masked_max.requires_grad
     if need_grad:
-        idx = encoder.min_idx.unsqueeze(1)
-        g1 = torch.gather(encoder.first_pn_out_masked_max, 2, idx.expand(-1, 384, -1))
-        g2 = torch.gather(encoder.knn_feature_1, 2, idx.expand(-1, encoder.knn_feature_1.shape[1], -1))
-        g3 = torch.gather(encoder.final_pn_out, 2, idx.expand(-1, encoder.final_pn_out.shape[1], -1))
+        # (a fixed-order backward: torch.gather's scatter-adds the ~kN / M copies of a node atomically, in an order that changes per run)
+        ids = st["a"].min_idx_i32
+        g1 = _ops.node_gather_autograd(encoder.first_pn_out_masked_max, ids)
+        g2 = _ops.node_gather_autograd(encoder.knn_feature_1, ids)
+        g3 = _ops.node_gather_autograd(encoder.final_pn_out, ids)
     else:
         ids = st["a"].min_idx_i32
         # (node-level maps are bf16 under precision "bf16": the gather kernel is f32, the maps are B x C x 64)

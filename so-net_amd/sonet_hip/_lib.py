@@ -100,6 +100,9 @@ SIGNATURES = {
     "sonet_knn_gather_bwd_ws_size": [_i, _i, _i],
     "sonet_knn_gather_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_knn_gather_bwd_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sonet_node_gather_bwd_ws_size": [_i, _i, _i],
+    "sonet_node_gather_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sonet_node_gather_bwd_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_p16_size": [_i, _i, _i],
     "sonet_p16_from_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
     "sonet_p16_to_f32": [_vp, _vp, _i, _i, _i, _vp],
@@ -171,6 +174,7 @@ _RESTYPES = {
     "sonet_knn_stage_columns": ctypes.c_size_t,
     "sonet_node_stage_columns": ctypes.c_size_t,
     "sonet_knn_gather_bwd_ws_size": ctypes.c_size_t,
+    "sonet_node_gather_bwd_ws_size": ctypes.c_size_t,
     "sonet_pointmlp_h3p_pack_size": ctypes.c_size_t,
     "sonet_pointmlp_h3p_stats_ws_size": ctypes.c_size_t,
     "sonet_pointmlp_bf16_pack_size": ctypes.c_size_t,

@@ -456,6 +456,52 @@ def node_gather(feat, min_idx_i32):
     return out
 
 
+def node_gather_bwd(g, min_idx_i32, M):
+    """Backward of ``node_gather``: g B x C x kN (f32 / bf16), min_idx B x kN i32 -> B x C x M f32, every node's columns summed in
+    ascending column order (bitwise reproducible: torch.gather's backward scatter-adds atomically)."""
+    if g.dtype not in (torch.float32, torch.bfloat16):
+        raise SonetHipError("node_gather_bwd: f32 or bf16 gradient")
+    _chk(g, "g", g.dtype, 3)
+    _chk(min_idx_i32, "min_idx", torch.int32, 2)
+    dev = _same_device(g, min_idx_i32)
+    B, C, L = g.shape
+    if tuple(min_idx_i32.shape) != (B, L):
+        raise SonetHipError("node_gather_bwd: min_idx must be B x kN with the kN of the gradient")
+    lib = _lib.load()
+    gx = torch.empty((B, C, M), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.sonet_node_gather_bwd_ws_size(B, M, L),), dtype=torch.uint8, device=dev)
+    fn = lib.sonet_node_gather_bwd_bf16 if g.dtype == torch.bfloat16 else lib.sonet_node_gather_bwd_f32
+    with _lib.on_device(dev), _timed("node_gather_bwd"):
+        check(fn(ptr(g), ptr(min_idx_i32), ptr(gx), ptr(ws), B, C, M, L, stream_ptr()), "sonet_node_gather_bwd")
+    return gx
+
+
+class _NodeGather(torch.autograd.Function):
+    """feat[:, :, min_idx] (models/segmenter.py:96-98) with a fixed-order backward (``node_gather_bwd``)."""
+
+    @staticmethod
+    def forward(ctx, feat, min_idx_i32):
+        ctx.save_for_backward(min_idx_i32)
+        ctx.M, ctx.dtype = feat.shape[2], feat.dtype
+        if feat.dtype == torch.float32:
+            return node_gather(feat.contiguous(), min_idx_i32)
+        # (bf16 node-level maps: the gather moves values, torch.gather's forward is exact)
+        return torch.gather(feat, 2, min_idx_i32.long().unsqueeze(1).expand(-1, feat.shape[1], -1))
+
+    @staticmethod
+    def backward(ctx, g):
+        (ids,) = ctx.saved_tensors
+        g = g.contiguous()
+        if g.dtype not in (torch.float32, torch.bfloat16):
+            g = g.float()
+        return node_gather_bwd(g, ids, ctx.M).to(ctx.dtype), None
+
+
+def node_gather_autograd(feat, min_idx_i32):
+    """Differentiable ``node_gather``: B x C x M, B x kN i32 -> B x C x kN; its backward sums every node's copies in a fixed order."""
+    return _NodeGather.apply(feat, min_idx_i32.contiguous())
+
+
 def node_add_affine_act_(t, z, min_idx_i32, scale, shift, relu):
     """t B x C x L <- act((t + z[:, :, min_idx]) * scale + shift) in place; z B x C x M."""
     _chk(t, "t", torch.float32, 3)

@@ -256,10 +256,28 @@ def train_step(enc, cls, label, node_knn_I, som_k=9, pc=None, sn=None, node=None
     -> dict(loss, feature, score, grads {key: tensor}, route {pool1, pool2, pool3}, masks {layer prefix: the ReLU pattern a free run took},
     bn {layer prefix: (batch mean, biased batch variance, element count)}, sites {site: the forward value / the gradient it rounded}
     (rounding="bf16"; empty otherwise), snap {forced site: dict(ulps, rel, scale), see ``_snap_stats``})."""
-    dt = next(iter(enc.values())).dtype
     _TAKEN.clear()
     _STATS.clear()
     R = _Rounder(rounding, stored, stored_grads) if rounding is not None else None
+    e = encoder_forward(enc, node_knn_I, som_k, pc, sn, node, k, stage, route, masks, R, pooled_dgrad)
+    feature = e["feature"]
+    s = _linear(_linear(feature, cls, "fc1", True, True, masks), cls, "fc2", True, True, masks)
+    score = _linear(s, cls, "fc3", False, False)
+    loss = F.cross_entropy(score, label.long())
+    leaves = {k_: v for k_, v in list(enc.items()) + [("cls." + k_, v) for k_, v in cls.items()] if v.requires_grad}
+    gr = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
+    sites = {} if R is None else dict(R.fwd_sites, **R.bwd_sites)
+    return dict(loss=loss.detach(), feature=feature.detach(), score=score.detach(), grads={k_: g for k_, g in zip(leaves, gr) if g is not None},
+                route=dict(pool1=e["pool1"], pool2=e["pool2"], pool3=e["pool3"]), masks=dict(_TAKEN), bn=dict(_STATS), sites=sites,
+                snap={} if R is None else dict(R.snap))
+
+
+def encoder_forward(enc, node_knn_I, som_k, pc, sn, node, k, stage, route, masks, R, pooled_dgrad="mfma", som_k_type="avg"):
+    """The encoder part of ``train_step`` (models/networks.py:111-199), arguments as there; ``R``: its ``_Rounder`` or None.
+    ``som_k_type``: the KNNModule's neighbourhood centre (models/layers.py:340-343), "avg" (the neighbour mean) or "center" (the node).
+    -> dict(min_idx, row_max, som_node, x_aug (the stage, detached), first (first_pn_out, B x 384 x kN), pool1, masked_max, knn_center,
+    knn_feature (B x 512 x M), pool2, final (final_pn_out, B x 1024 x M), pool3, feature)."""
+    dt = next(iter(enc.values())).dtype
     fw = (lambda name, t: t) if R is None else R.fwd
     bw = (lambda name, t: t) if R is None else R.bwd
     if stage is None:
@@ -301,7 +319,12 @@ def train_step(enc, cls, label, node_knn_I, som_k=9, pc=None, sn=None, node=None
         C = x.shape[1]
         return x.gather(2, knn_I.reshape(B, 1, -1).expand(B, C, M * som_k)).reshape(B, C, M, som_k)
     nb = knn_gather(som_node)
-    center = nb.mean(dim=3, keepdim=True)
+    if som_k_type == "avg":
+        center = nb.mean(dim=3, keepdim=True)
+    elif som_k_type == "center":
+        center = som_node.unsqueeze(3)
+    else:
+        raise ValueError("som_k_type must be 'avg' or 'center', got %r" % (som_k_type,))
     h = torch.cat(((nb - center).detach(), knn_gather(masked_max)), dim=1)
     h = bw("knnlayer.layers.0.g_in", fw("knnlayer.layers.0.input", h))
     h = _conv(h, enc, "knnlayer.layers.0", True, True, masks, R)
@@ -314,12 +337,5 @@ def train_step(enc, cls, label, node_knn_I, som_k=9, pc=None, sn=None, node=None
     final = _conv(bw("final_pointnet.layers.1.g_in", final), enc, "final_pointnet.layers.1", False, False, None, R)
     pool3 = final.max(dim=2)[1] if route is None else route["pool3"].long()
     feature = bw("feature.g", fw("pool3", final.gather(2, pool3.unsqueeze(2)).squeeze(2)))
-    s = _linear(_linear(feature, cls, "fc1", True, True, masks), cls, "fc2", True, True, masks)
-    score = _linear(s, cls, "fc3", False, False)
-    loss = F.cross_entropy(score, label.long())
-    leaves = {k_: v for k_, v in list(enc.items()) + [("cls." + k_, v) for k_, v in cls.items()] if v.requires_grad}
-    gr = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
-    sites = {} if R is None else dict(R.fwd_sites, **R.bwd_sites)
-    return dict(loss=loss.detach(), feature=feature.detach(), score=score.detach(), grads={k_: g for k_, g in zip(leaves, gr) if g is not None},
-                route=dict(pool1=pool1, pool2=pool2, pool3=pool3), masks=dict(_TAKEN), bn=dict(_STATS), sites=sites,
-                snap={} if R is None else dict(R.snap))
+    return dict(min_idx=min_idx, row_max=row_max, som_node=som_node, x_aug=x_aug, first=first, pool1=pool1, masked_max=masked_max,
+                knn_center=center.squeeze(3).detach(), knn_feature=knn_feature, pool2=pool2, final=final, pool3=pool3, feature=feature)

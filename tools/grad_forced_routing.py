@@ -9,6 +9,10 @@ the table behind tests/test_gpu_parity.py::test_training_gradients_with_forced_r
 the plain float64 twin with the routing forced), for every bf16
 switch setting of ``--fusions`` (default: every fusion on; off: tests/test_gpu_bf16_forced_routing.py FUSIONS) -- the table behind
 tests/test_gpu_bf16_forced_routing.py::test_bf16_training_gradients_with_forced_routing (``synthetic_b36_n5000`` is its third case).
+
+``--head segmenter``: the part-segmentation step (``networks.segmentation_forward``) against tests/f64_segmenter.py with its routing and
+ten ReLU patterns forced, every gradient listed -- the table behind tests/test_gpu_seg_training.py::test_seg_training_gradients_with_forced_routing
+(fixtures default to ``seg_train_step_b8_n512,synthetic_b16_n1024``).
 """
 import argparse
 import os
@@ -21,10 +25,14 @@ sys.path.insert(0, ROOT)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--modes", default="h3,x3,f32")
-ap.add_argument("--fixtures", default="train_step_b16_n512,train_step_b8_n5000")
+ap.add_argument("--fixtures", default=None, help="default: train_step_b16_n512,train_step_b8_n5000 (segmenter: seg_train_step_b8_n512,"
+                                                  "synthetic_b16_n1024)")
+ap.add_argument("--head", default="classifier", choices=("classifier", "segmenter"))
 ap.add_argument("--fusions", default="default,off", help="bf16 mode: the switch settings")
 ap.add_argument("--set", nargs="*", default=[], help="ops switches, e.g. DEFER_WGRAD_JOIN=0 BNB_ON_LOAD=0")
 args = ap.parse_args()
+if args.fixtures is None:
+    args.fixtures = "train_step_b16_n512,train_step_b8_n5000" if args.head == "classifier" else "seg_train_step_b8_n512,synthetic_b16_n1024"
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -73,8 +81,39 @@ def bf16_case(fixture, fusions):
     print("   worst %.3e over %d parameters (plain f64 twin: %.3e)" % (max(rel.values()), len(rel), max(plain.values())))
 
 
+def seg_case(case, mode):
+    """The segmentation step against the forced float64 segmenter twin: loss, scores, running statistics, every gradient."""
+    import test_gpu_seg_training as S
+    g = S._inputs(case)
+    res = S.run_seg_step(g, mode)
+    r = S.f64_seg_step(res, g, forced=True)
+    free = S.f64_seg_step(res, g, forced=False)
+    cap = res["cap"]
+    fl = [int((free["route"][p] != cap[p]).sum()) for p in ("pool1", "pool2", "pool3")]
+    rel = S.grad_residuals(res, r)
+    sc, sr = res["score"].double(), r["score"]
+    print("\n== %s  %s  dense=%s  loss %.9f (f64 forced %.9f, rel %.2e)  score rel-rms %.2e  flips vs free f64 run: pool1 %d pool2 %d "
+          "pool3 %d  masks %d layers" % (case, mode, cap["need_dense"], float(res["loss"]), float(r["loss"]),
+                                        abs(float(res["loss"]) - float(r["loss"])) / abs(float(r["loss"])),
+                                        float((sc - sr).norm() / sr.norm()), fl[0], fl[1], fl[2], len(cap["masks"])))
+    worst_run = ("", 0.0)
+    for k, (want, got) in S.expected_running(res, r).items():
+        want, got = want.double(), got.double()
+        e = float(((got - want).abs() / torch.maximum(want.abs(), want.pow(2).mean().sqrt())).max())
+        worst_run = max(worst_run, (k, e), key=lambda kv: kv[1])
+    print("   running statistics: worst err / max(|ref|, rms) %.3e (%s)" % (worst_run[1], worst_run[0]))
+    print("   kernels:", " ".join(sorted(res["names"])))
+    for k, v in sorted(rel.items(), key=lambda kv: -kv[1]):
+        print("   %-45s %.3e" % (k, v))
+    print("   worst %.3e over %d parameters" % (max(rel.values()), len(rel)))
+
+
 for fixture in args.fixtures.split(","):
     for mode in args.modes.split(","):
+        if args.head == "segmenter":
+            seg_case(fixture, mode)
+            torch.cuda.empty_cache()
+            continue
         if mode == "bf16":
             for fu in args.fusions.split(","):
                 bf16_case(fixture, fu == "default")
