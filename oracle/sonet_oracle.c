@@ -77,6 +77,7 @@ void oracle_som_query_topk_f32(const float *x, const float *node, int B, int N, 
             for (int m = 0; m < M; ++m) {
                 float dx = px - nb[m], dy = py - nb[M + m], dz = pz - nb[2 * M + m];
                 float d = (dx * dx + dy * dy) + dz * dz;
+                if (d != d) d = INFINITY;   /* NaN orders as +inf (torch.topk puts NaN last); else it would block what follows */
                 /* insertion into the ascending (d, m) list; m ascends so ties keep the lower id */
                 int pos = filled;
                 while (pos > 0 && d < bd[pos - 1]) --pos;

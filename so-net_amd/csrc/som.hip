@@ -15,12 +15,19 @@
 // FMA contraction can change a comparison.  Selection is a k-deep insertion list kept in VGPRs,
 // nodes visited in ascending id with strict '<', so ties keep the lower id and slots come out in
 // ascending (distance, id) order -- the canonical order of torch.topk(sorted=True).
+// Distances that are not finite (a coordinate around 1.3e19 or more overflows the square to +inf; a NaN coordinate) order as
+// +inf, ties by id like any other: a list that fewer than k finite distances can fill takes the lowest ids among the
+// non-finite ones behind them, so a point always reports k DISTINCT nodes, as torch.topk and the oracle do.  The list
+// therefore tracks which slots are filled (visiting ids in ascending order, slot s is unfilled exactly while s >= id).
 #include "common.hpp"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int SA_THREADS = 256;
+
+// what the insertion lists order by: NaN counts as +inf
+__device__ __forceinline__ float order_dist(float d) { return d != d ? __builtin_inff() : d; }
 
 __device__ __forceinline__ float sqdist(float px, float py, float pz, const float4 nd) {
     const float dx = __fsub_rn(px, nd.x), dy = __fsub_rn(py, nd.y), dz = __fsub_rn(pz, nd.z);
@@ -59,10 +66,10 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_kernel(
         for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
 #pragma unroll 4
         for (int m = 0; m < M; ++m) {
-            const float d = sqdist(px, py, pz, nodes[m]);
+            const float d = order_dist(sqdist(px, py, pz, nodes[m]));
             bool c[KSEL];
 #pragma unroll
-            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s];
+            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= m;      // (s >= m: slot s is still unfilled)
 #pragma unroll
             for (int s = KSEL - 1; s >= 1; --s) {
                 bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
@@ -103,7 +110,7 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_kernel(
 // operations at k = 3, and the winners' ids are simply the keys' low bits -- no second pass, no distances kept.  Truncation can
 // only reorder two candidates whose distances agree in all the kept bits (within 2^IB ulp of each other): a lane sees that as
 // equal high parts among its KSEL + 1 smallest keys (the extra one guards the boundary of the list) and then -- like a lane
-// whose list reaches +inf / NaN, where the reference leaves id 0 -- redoes its point with the exact insertion list.  Bit-exact
+// whose list reaches +inf / NaN, where the slots take the lowest non-finite ids -- redoes its point with the exact insertion list.  Bit-exact
 // with som_assign_kernel by construction; the slow branch runs for ~1e-4 of the points.
 template <int KSEL, int IB>
 __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
         }
         for (; m < M; ++m) visit(m);
         int bi[KSEL];
-        bool exact = t[KSEL - 1] >= 0x7F800000u;                            // the list reaches +inf / NaN: the reference keeps id 0 there
+        bool exact = t[KSEL - 1] >= 0x7F800000u;                            // the list reaches +inf / NaN: the exact list fills those slots
 #pragma unroll
         for (int s = 0; s < KSEL; ++s) {
             bi[s] = (int)(t[s] & IMASK);
@@ -164,10 +171,10 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
 #pragma unroll
             for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
             for (int m = 0; m < M; ++m) {
-                const float d = sqdist(px, py, pz, nodes[m]);
+                const float d = order_dist(sqdist(px, py, pz, nodes[m]));
                 bool c[KSEL];
 #pragma unroll
-                for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s];
+                for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= m;
 #pragma unroll
                 for (int s = KSEL - 1; s >= 1; --s) {
                     bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
@@ -640,7 +647,7 @@ __device__ __forceinline__ void som_select_keys(float px, float py, float pz, co
     int m = 0;
     for (; m + 8 <= M; m += 8) { visit(m); visit(m + 1); visit(m + 2); visit(m + 3); visit(m + 4); visit(m + 5); visit(m + 6); visit(m + 7); }
     for (; m < M; ++m) visit(m);
-    bool exact = t[KSEL - 1] >= 0x7F800000u;                                // the list reaches +inf / NaN: the reference keeps id 0 there
+    bool exact = t[KSEL - 1] >= 0x7F800000u;                                // the list reaches +inf / NaN: the exact list fills those slots
 #pragma unroll
     for (int s = 0; s < KSEL; ++s) {
         bi[s] = (int)(t[s] & IMASK);
@@ -651,10 +658,10 @@ __device__ __forceinline__ void som_select_keys(float px, float py, float pz, co
 #pragma unroll
         for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
         for (int mm = 0; mm < M; ++mm) {
-            const float d = sqdist(px, py, pz, nodes[mm]);
+            const float d = order_dist(sqdist(px, py, pz, nodes[mm]));
             bool c[KSEL];
 #pragma unroll
-            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s];
+            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= mm;
 #pragma unroll
             for (int s = KSEL - 1; s >= 1; --s) {
                 bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);

@@ -353,3 +353,32 @@ def test_training_step_with_backward_sums_from_the_dgrad_epilogue():
     _compare_steps(res[True], res[False])
 
 
+def _edge_som_cases():
+    import edge_clouds as E
+    out = [("lattice_B%d_N%d_M%d_k%d_q%d" % c,) + E.lattice_case(c) for c in E.LATTICE_CASES]
+    out += [("near_ties_B%d_M%d_k%d_s%d" % c,) + E.near_tie_case(c)[:3] for c in E.NEAR_TIE_CASES]
+    return out + E.occupancy_cases() + E.overflow_cases() + E.nan_cases()
+
+
+EDGE_SOM_CASES = _edge_som_cases()
+
+
+@pytest.mark.parametrize("i", range(len(EDGE_SOM_CASES)), ids=[c[0] for c in EDGE_SOM_CASES])
+def test_insertion_list_som_assign_on_edge_clouds(i, monkeypatch):
+    """som_assign_kernel (the insertion-list kernel, SONET_SOM_KEYS=0: dispatched by this build only) on the edge inputs of
+    tests/edge_clouds.py -- ties, near ties, degenerate occupancy, overflowing and NaN distances: ids and counts equal the oracle's and
+    the packed-key kernel's."""
+    from oracle import cpu_oracle as O
+    from sonet_hip import ops
+    name, x, node, k = EDGE_SOM_CASES[i]
+    ref_idx, ref_cnt, _ = O.som_query_topk(x, node, k)
+    keys = ops.som_assign(cu(x), cu(node), k, want_i64=True)
+    monkeypatch.setenv("SONET_SOM_KEYS", "0")
+    a = ops.som_assign(cu(x), cu(node), k, want_i64=True)
+    for r in (a, keys):
+        np.testing.assert_array_equal(r.min_idx_i64.cpu().numpy(), ref_idx)
+        np.testing.assert_array_equal(r.min_idx_i32.cpu().numpy(), ref_idx.astype(np.int32))
+        np.testing.assert_array_equal(r.count.cpu().numpy(), ref_cnt)
+    if np.isfinite(x).all() and np.isfinite(node).all():
+        g = ops.som_group(cu(x), None, a)
+        assert_close_rms(g["som_node"].cpu().numpy(), O.som_group(x, ref_idx, node.shape[2], k)[0], 1e-6, "som_node")
