@@ -127,5 +127,8 @@ __device__ __forceinline__ void p16_split_pair(float x0, float x1, unsigned &h, 
     h = __builtin_bit_cast(unsigned, hv);
     m = __builtin_bit_cast(unsigned, __builtin_convertvector(R, sonet_h2_t));
 }
+// cluster mean of the SOM stage (models/networks.py:142): sum / (count + 1e-5), every step rounded to f32 (no reciprocal, no FMA)
+__device__ __forceinline__ float cluster_mean(float sum, float count) { return __fdiv_rn(sum, __fadd_rn(count, 1e-5f)); }
+
 // groups (nodes) per 128-column block of the K-level tensor of the flat node-level stage (node_stage.hip): as many as fit, at most 16
 static inline int knn_stage_groups(int K) { const int g = 128 / K; return g > 16 ? 16 : g; }

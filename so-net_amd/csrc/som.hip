@@ -21,6 +21,7 @@
 // therefore tracks which slots are filled (visiting ids in ascending order, slot s is unfilled exactly while s >= id).
 #include "common.hpp"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -34,76 +35,33 @@ __device__ __forceinline__ float sqdist(float px, float py, float pz, const floa
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
-// LDS layout (dynamic): float4 nodes[M] | double sums[3][M] | unsigned cnt[M]
+// The exact selection (the contract above): the KSEL nearest of the M nodes in LDS, ascending (distance, id), into bi.
+// The node loop is unrolled by 4 in the redo branch of the packed keys too: only ~1e-4 of the points take it, but a launch ends
+// with its slowest workgroup, and a rolled loop there (one LDS round trip per node) measured 23.5 instead of 19.9 us for
+// som_assign_rank_kernel at B = 64.
 template <int KSEL>
-__global__ __launch_bounds__(SA_THREADS) void som_assign_kernel(
-    const float *__restrict__ x, const float *__restrict__ node, int N, int M,
-    int32_t *__restrict__ min32, int64_t *__restrict__ min64, int32_t *__restrict__ count,
-    double *__restrict__ sum_ws)
+__device__ __forceinline__ void som_select_exact(float px, float py, float pz, const float4 *nodes, int M, int (&bi)[KSEL])
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float4 *nodes = reinterpret_cast<float4 *>(smem);
-    double *sums = reinterpret_cast<double *>(smem + (size_t)M * sizeof(float4));
-    unsigned *cnt = reinterpret_cast<unsigned *>(smem + (size_t)M * (sizeof(float4) + 3 * sizeof(double)));
-
-    const int tid = threadIdx.x;
-    const int b = blockIdx.y;
-    const float *xb = x + (size_t)b * 3 * N;
-    const float *nb = node + (size_t)b * 3 * M;
-    for (int m = tid; m < M; m += SA_THREADS) {
-        nodes[m] = make_float4(nb[m], nb[M + m], nb[2 * M + m], 0.f);
-        sums[m] = 0.0; sums[M + m] = 0.0; sums[2 * M + m] = 0.0;
-        cnt[m] = 0u;
-    }
-    __syncthreads();
-
-    const int n = blockIdx.x * SA_THREADS + tid;
-    if (n < N) {
-        const float px = xb[n], py = xb[N + n], pz = xb[2 * (size_t)N + n];
-        float bd[KSEL];
-        int bi[KSEL];
+    float bd[KSEL];
 #pragma unroll
-        for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
+    for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
 #pragma unroll 4
-        for (int m = 0; m < M; ++m) {
-            const float d = order_dist(sqdist(px, py, pz, nodes[m]));
-            bool c[KSEL];
+    for (int m = 0; m < M; ++m) {
+        const float d = order_dist(sqdist(px, py, pz, nodes[m]));
+        bool c[KSEL];
 #pragma unroll
-            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= m;      // (s >= m: slot s is still unfilled)
+        for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= m;          // (s >= m: slot s is still unfilled)
 #pragma unroll
-            for (int s = KSEL - 1; s >= 1; --s) {
-                bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
-                bi[s] = c[s - 1] ? bi[s - 1] : (c[s] ? m : bi[s]);
-            }
-            bd[0] = c[0] ? d : bd[0];
-            bi[0] = c[0] ? m : bi[0];
+        for (int s = KSEL - 1; s >= 1; --s) {
+            bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
+            bi[s] = c[s - 1] ? bi[s - 1] : (c[s] ? m : bi[s]);
         }
-        const size_t kN = (size_t)KSEL * N;
-#pragma unroll
-        for (int s = 0; s < KSEL; ++s) {
-            const size_t o = (size_t)b * kN + (size_t)s * N + n;
-            min32[o] = bi[s];
-            if (min64 != nullptr) min64[o] = bi[s];
-            atomicAdd(&cnt[bi[s]], 1u);
-            atomicAdd(&sums[bi[s]], (double)px);
-            atomicAdd(&sums[M + bi[s]], (double)py);
-            atomicAdd(&sums[2 * M + bi[s]], (double)pz);
-        }
-    }
-    __syncthreads();
-    for (int m = tid; m < M; m += SA_THREADS) {
-        const unsigned c = cnt[m];
-        if (c != 0u) {
-            atomicAdd(&count[(size_t)b * M + m], (int)c);
-            double *ws = sum_ws + (size_t)b * 3 * M;
-            unsafeAtomicAdd(&ws[m], sums[m]);
-            unsafeAtomicAdd(&ws[M + m], sums[M + m]);
-            unsafeAtomicAdd(&ws[2 * M + m], sums[2 * M + m]);
-        }
+        bd[0] = c[0] ? d : bd[0];
+        bi[0] = c[0] ? m : bi[0];
     }
 }
 
-// ---- the same assignment, selection on packed keys ------------------------------------------------------------------------
+// ---- the same selection on packed keys ------------------------------------------------------------------------------------
 // The insertion list above costs ~13 vector operations per (point, node) pair on top of the 8 of the exact distance.  Here the
 // distance's bit pattern (d >= 0: it orders like the value) gives up its low IB bits to the node id, key = (bits(d) & ~mask) | m,
 // and the KSEL + 1 smallest keys are kept by an unsigned min / median-of-three chain: v_and_or + v_min + KSEL x v_med3 = 5
@@ -111,9 +69,45 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_kernel(
 // only reorder two candidates whose distances agree in all the kept bits (within 2^IB ulp of each other): a lane sees that as
 // equal high parts among its KSEL + 1 smallest keys (the extra one guards the boundary of the list) and then -- like a lane
 // whose list reaches +inf / NaN, where the slots take the lowest non-finite ids -- redoes its point with the exact insertion list.  Bit-exact
-// with som_assign_kernel by construction; the slow branch runs for ~1e-4 of the points.
+// with som_select_exact by construction; the slow branch runs for ~1e-4 of the points.
 template <int KSEL, int IB>
-__global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
+__device__ __forceinline__ void som_select_keys(float px, float py, float pz, const float4 *nodes, int M, int (&bi)[KSEL])
+{
+    constexpr unsigned IMASK = (1u << IB) - 1u;
+    unsigned t[KSEL + 1];
+#pragma unroll
+    for (int s = 0; s <= KSEL; ++s) t[s] = 0xFFFFFFFFu;
+    const unsigned hi_mask = ~IMASK;
+    auto visit = [&](int m) {
+        unsigned key;                                                   // (bits(d) & ~IMASK) | m in one instruction
+        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(__float_as_uint(sqdist(px, py, pz, nodes[m]))), "v"(hi_mask), "s"((unsigned)m));   // (one scalar operand per VOP3)
+        // sorted insertion of key into t[0] <= t[1] <= ... : new t[s] = median(t[s-1], t[s], key), new t[0] = min(t[0], key)
+#pragma unroll
+        for (int s = KSEL; s >= 1; --s) {
+            unsigned md;                                                // (hipcc does not form v_med3_u32 from the selects)
+            asm("v_med3_u32 %0, %1, %2, %3" : "=v"(md) : "v"(t[s - 1]), "v"(t[s]), "v"(key));
+            t[s] = md;
+        }
+        t[0] = key < t[0] ? key : t[0];
+    };
+    int m = 0;
+    for (; m + 8 <= M; m += 8) {                                       // (unrolled by hand: the asm statements keep the pragma from doing it)
+        visit(m); visit(m + 1); visit(m + 2); visit(m + 3); visit(m + 4); visit(m + 5); visit(m + 6); visit(m + 7);
+    }
+    for (; m < M; ++m) visit(m);
+    bool exact = t[KSEL - 1] >= 0x7F800000u;                            // the list reaches +inf / NaN: the exact list fills those slots
+#pragma unroll
+    for (int s = 0; s < KSEL; ++s) {
+        bi[s] = (int)(t[s] & IMASK);
+        exact = exact || ((t[s] & ~IMASK) == (t[s + 1] & ~IMASK));     // a pair the truncation may have ordered by id instead of by distance
+    }
+    if (exact) som_select_exact(px, py, pz, nodes, M, bi);
+}
+
+// som_assign: the body of som_assign_kernel (IB = 0: the exact insertion list) and of som_assign_keys_kernel (IB id bits in the
+// packed keys).  LDS layout (dynamic): float4 nodes[M] | double sums[3][M] | unsigned cnt[M]
+template <int KSEL, int IB>
+__device__ __forceinline__ void som_assign_body(
     const float *__restrict__ x, const float *__restrict__ node, int N, int M,
     int32_t *__restrict__ min32, int64_t *__restrict__ min64, int32_t *__restrict__ count,
     double *__restrict__ sum_ws)
@@ -122,7 +116,6 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
     float4 *nodes = reinterpret_cast<float4 *>(smem);
     double *sums = reinterpret_cast<double *>(smem + (size_t)M * sizeof(float4));
     unsigned *cnt = reinterpret_cast<unsigned *>(smem + (size_t)M * (sizeof(float4) + 3 * sizeof(double)));
-    constexpr unsigned IMASK = (1u << IB) - 1u;
 
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
@@ -138,52 +131,9 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
     const int n = blockIdx.x * SA_THREADS + tid;
     if (n < N) {
         const float px = xb[n], py = xb[N + n], pz = xb[2 * (size_t)N + n];
-        unsigned t[KSEL + 1];
-#pragma unroll
-        for (int s = 0; s <= KSEL; ++s) t[s] = 0xFFFFFFFFu;
-        const unsigned hi_mask = ~IMASK;
-        auto visit = [&](int m) {
-            unsigned key;                                                   // (bits(d) & ~IMASK) | m in one instruction
-            asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(__float_as_uint(sqdist(px, py, pz, nodes[m]))), "v"(hi_mask), "s"((unsigned)m));   // (one scalar operand per VOP3)
-            // sorted insertion of key into t[0] <= t[1] <= ... : new t[s] = median(t[s-1], t[s], key), new t[0] = min(t[0], key)
-#pragma unroll
-            for (int s = KSEL; s >= 1; --s) {
-                unsigned md;                                                // (hipcc does not form v_med3_u32 from the selects)
-                asm("v_med3_u32 %0, %1, %2, %3" : "=v"(md) : "v"(t[s - 1]), "v"(t[s]), "v"(key));
-                t[s] = md;
-            }
-            t[0] = key < t[0] ? key : t[0];
-        };
-        int m = 0;
-        for (; m + 8 <= M; m += 8) {                                       // (unrolled by hand: the asm statements keep the pragma from doing it)
-            visit(m); visit(m + 1); visit(m + 2); visit(m + 3); visit(m + 4); visit(m + 5); visit(m + 6); visit(m + 7);
-        }
-        for (; m < M; ++m) visit(m);
         int bi[KSEL];
-        bool exact = t[KSEL - 1] >= 0x7F800000u;                            // the list reaches +inf / NaN: the exact list fills those slots
-#pragma unroll
-        for (int s = 0; s < KSEL; ++s) {
-            bi[s] = (int)(t[s] & IMASK);
-            exact = exact || ((t[s] & ~IMASK) == (t[s + 1] & ~IMASK));     // a pair the truncation may have ordered by id instead of by distance
-        }
-        if (exact) {
-            float bd[KSEL];
-#pragma unroll
-            for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
-            for (int m = 0; m < M; ++m) {
-                const float d = order_dist(sqdist(px, py, pz, nodes[m]));
-                bool c[KSEL];
-#pragma unroll
-                for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= m;
-#pragma unroll
-                for (int s = KSEL - 1; s >= 1; --s) {
-                    bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
-                    bi[s] = c[s - 1] ? bi[s - 1] : (c[s] ? m : bi[s]);
-                }
-                bd[0] = c[0] ? d : bd[0];
-                bi[0] = c[0] ? m : bi[0];
-            }
-        }
+        if constexpr (IB == 0) som_select_exact(px, py, pz, nodes, M, bi);
+        else som_select_keys<KSEL, IB>(px, py, pz, nodes, M, bi);
         const size_t kN = (size_t)KSEL * N;
 #pragma unroll
         for (int s = 0; s < KSEL; ++s) {
@@ -209,8 +159,49 @@ __global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
     }
 }
 
+template <int KSEL>
+__global__ __launch_bounds__(SA_THREADS) void som_assign_kernel(
+    const float *__restrict__ x, const float *__restrict__ node, int N, int M,
+    int32_t *__restrict__ min32, int64_t *__restrict__ min64, int32_t *__restrict__ count,
+    double *__restrict__ sum_ws)
+{
+    som_assign_body<KSEL, 0>(x, node, N, M, min32, min64, count, sum_ws);
+}
+
+template <int KSEL, int IB>
+__global__ __launch_bounds__(SA_THREADS) void som_assign_keys_kernel(
+    const float *__restrict__ x, const float *__restrict__ node, int N, int M,
+    int32_t *__restrict__ min32, int64_t *__restrict__ min64, int32_t *__restrict__ count,
+    double *__restrict__ sum_ws)
+{
+    som_assign_body<KSEL, IB>(x, node, N, M, min32, min64, count, sum_ws);
+}
+
+
 constexpr int SG_THREADS = 256;
 constexpr int SG_PER_THREAD = 4;
+
+// Prologue of the grouping kernels (SG_THREADS threads): the cluster means of cloud b into LDS, mean[3][M]; the cloud's workgroup 0
+// also writes them to som_node and the "node is occupied" flags to row_max where asked.  The caller's barrier publishes the means.
+__device__ __forceinline__ void som_means_to_lds(const int32_t *__restrict__ count, const double *__restrict__ sum_ws, int b, int M,
+                                                 float *mean, float *__restrict__ som_node, int32_t *__restrict__ row_max)
+{
+    const double *ws = sum_ws + (size_t)b * 3 * M;
+    for (int m = threadIdx.x; m < M; m += SG_THREADS) {
+        const int c = count[(size_t)b * M + m];
+        const float mx = cluster_mean((float)ws[m], (float)c);
+        const float my = cluster_mean((float)ws[M + m], (float)c);
+        const float mz = cluster_mean((float)ws[2 * M + m], (float)c);
+        mean[m] = mx; mean[M + m] = my; mean[2 * M + m] = mz;
+        if (blockIdx.x == 0) {
+            if (som_node != nullptr) {
+                float *o = som_node + (size_t)b * 3 * M;
+                o[m] = mx; o[M + m] = my; o[2 * M + m] = mz;
+            }
+            if (row_max != nullptr) row_max[(size_t)b * M + m] = c > 0;
+        }
+    }
+}
 
 __global__ __launch_bounds__(SG_THREADS) void som_group_kernel(
     const float *__restrict__ x, const float *__restrict__ sn, const int32_t *__restrict__ min32,
@@ -221,22 +212,7 @@ __global__ __launch_bounds__(SG_THREADS) void som_group_kernel(
     extern __shared__ __attribute__((aligned(16))) float mean[];  // [3][M]
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
-    const double *ws = sum_ws + (size_t)b * 3 * M;
-    for (int m = tid; m < M; m += SG_THREADS) {
-        const int c = count[(size_t)b * M + m];
-        const float denom = __fadd_rn((float)c, 1e-5f);          // networks.py:142
-        const float mx = __fdiv_rn((float)ws[m], denom);
-        const float my = __fdiv_rn((float)ws[M + m], denom);
-        const float mz = __fdiv_rn((float)ws[2 * M + m], denom);
-        mean[m] = mx; mean[M + m] = my; mean[2 * M + m] = mz;
-        if (blockIdx.x == 0) {
-            if (som_node != nullptr) {
-                float *o = som_node + (size_t)b * 3 * M;
-                o[m] = mx; o[M + m] = my; o[2 * M + m] = mz;
-            }
-            if (row_max != nullptr) row_max[(size_t)b * M + m] = c > 0;
-        }
-    }
+    som_means_to_lds(count, sum_ws, b, M, mean, som_node, row_max);
     __syncthreads();
     if (centers == nullptr && x_dec == nullptr && x_aug == nullptr) return;
 
@@ -417,8 +393,7 @@ __global__ __launch_bounds__(256) void knn_self_kernel(const float *__restrict__
 #pragma unroll
     for (int j = 0; j < KS_MAX; ++j) { bd[j] = __builtin_inff(); bi[j] = 0x7FFFFFFF; }
     for (int i = 0; i < M; ++i) {
-        const float dx = __fsub_rn(qx, nb[i]), dy = __fsub_rn(qy, nb[M + i]), dz = __fsub_rn(qz, nb[2 * M + i]);
-        float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        float d = sqdist(qx, qy, qz, make_float4(nb[i], nb[M + i], nb[2 * M + i], 0.f));
         int id = i;
 #pragma unroll
         for (int j = 0; j < KS_MAX; ++j) {                               // insert, pushing the larger one down the chain
@@ -506,18 +481,8 @@ __global__ __launch_bounds__(SG_THREADS) void som_sort_group_kernel(
     int *base = hist + M;
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
-    const double *ws = sum_ws + (size_t)b * 3 * M;
-    for (int m = tid; m < M; m += SG_THREADS) {
-        const int c = count[(size_t)b * M + m];
-        const float denom = __fadd_rn((float)c, 1e-5f);
-        const float mx = __fdiv_rn((float)ws[m], denom), my = __fdiv_rn((float)ws[M + m], denom), mz = __fdiv_rn((float)ws[2 * M + m], denom);
-        mean[m] = mx; mean[M + m] = my; mean[2 * M + m] = mz;
-        hist[m] = 0;
-        if (blockIdx.x == 0) {
-            if (som_node != nullptr) { float *o = som_node + (size_t)b * 3 * M; o[m] = mx; o[M + m] = my; o[2 * M + m] = mz; }
-            if (row_max != nullptr) row_max[(size_t)b * M + m] = c > 0;
-        }
-    }
+    som_means_to_lds(count, sum_ws, b, M, mean, som_node, row_max);
+    for (int m = tid; m < M; m += SG_THREADS) hist[m] = 0;
     if (tid == 0) {                                                          // exclusive prefix of the node counts
         int acc = 0;
         for (int m = 0; m < M; ++m) {
@@ -559,23 +524,17 @@ __global__ __launch_bounds__(SG_THREADS) void som_sort_group_kernel(
 // Phase B: one thread per sorted position: coalesced stores of the six channels; the gathers hit the cloud's 120 KB of
 // x / sn in L2.  (Four positions per thread with 16-byte index loads and stores measured SLOWER: 26.7 vs 22.1 us at B = 64 --
 // a quarter of the threads to hide the load -> gather -> store chain; r02zc.)
-__global__ __launch_bounds__(256) void som_sort_fill_kernel(
+__global__ __launch_bounds__(SG_THREADS) void som_sort_fill_kernel(
     const float *__restrict__ x, const float *__restrict__ sn, const int32_t *__restrict__ count,
     const double *__restrict__ sum_ws, const int32_t *__restrict__ ids_sorted, int N, int M, int k, float *__restrict__ x_aug_sorted)
 {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];          // mean[3][M]
     float *mean = smem_f;
     const int b = blockIdx.y;
-    const double *ws = sum_ws + (size_t)b * 3 * M;
-    for (int m = threadIdx.x; m < M; m += 256) {
-        const float denom = __fadd_rn((float)count[(size_t)b * M + m], 1e-5f);
-        mean[m] = __fdiv_rn((float)ws[m], denom);
-        mean[M + m] = __fdiv_rn((float)ws[M + m], denom);
-        mean[2 * M + m] = __fdiv_rn((float)ws[2 * M + m], denom);
-    }
+    som_means_to_lds(count, sum_ws, b, M, mean, nullptr, nullptr);
     __syncthreads();
     const size_t kN = (size_t)k * N;
-    const size_t pos = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t pos = (size_t)blockIdx.x * SG_THREADS + threadIdx.x;
     if (pos >= kN) return;
     float *ob = x_aug_sorted + (size_t)b * 6 * kN;
     const int j = reinterpret_cast<const int32_t *>(ob + 5 * kN)[pos];
@@ -622,54 +581,6 @@ __device__ __forceinline__ void lds_exclusive_scan(const int *in, int *out, int 
         for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (tid >= o) incl += t; }
         if (m < M) out[m] = carry + incl - v;
         carry += __shfl(incl, 63, 64);
-    }
-}
-
-template <int KSEL, int IB>
-__device__ __forceinline__ void som_select_keys(float px, float py, float pz, const float4 *nodes, int M, int (&bi)[KSEL])
-{
-    constexpr unsigned IMASK = (1u << IB) - 1u;
-    unsigned t[KSEL + 1];
-#pragma unroll
-    for (int s = 0; s <= KSEL; ++s) t[s] = 0xFFFFFFFFu;
-    const unsigned hi_mask = ~IMASK;
-    auto visit = [&](int m) {
-        unsigned key;
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(__float_as_uint(sqdist(px, py, pz, nodes[m]))), "v"(hi_mask), "s"((unsigned)m));
-#pragma unroll
-        for (int s = KSEL; s >= 1; --s) {
-            unsigned md;
-            asm("v_med3_u32 %0, %1, %2, %3" : "=v"(md) : "v"(t[s - 1]), "v"(t[s]), "v"(key));
-            t[s] = md;
-        }
-        t[0] = key < t[0] ? key : t[0];
-    };
-    int m = 0;
-    for (; m + 8 <= M; m += 8) { visit(m); visit(m + 1); visit(m + 2); visit(m + 3); visit(m + 4); visit(m + 5); visit(m + 6); visit(m + 7); }
-    for (; m < M; ++m) visit(m);
-    bool exact = t[KSEL - 1] >= 0x7F800000u;                                // the list reaches +inf / NaN: the exact list fills those slots
-#pragma unroll
-    for (int s = 0; s < KSEL; ++s) {
-        bi[s] = (int)(t[s] & IMASK);
-        exact = exact || ((t[s] & ~IMASK) == (t[s + 1] & ~IMASK));         // a pair the truncation may have ordered by id instead of by distance
-    }
-    if (exact) {
-        float bd[KSEL];
-#pragma unroll
-        for (int s = 0; s < KSEL; ++s) { bd[s] = __builtin_inff(); bi[s] = 0; }
-        for (int mm = 0; mm < M; ++mm) {
-            const float d = order_dist(sqdist(px, py, pz, nodes[mm]));
-            bool c[KSEL];
-#pragma unroll
-            for (int s = 0; s < KSEL; ++s) c[s] = d < bd[s] || s >= mm;
-#pragma unroll
-            for (int s = KSEL - 1; s >= 1; --s) {
-                bd[s] = c[s - 1] ? bd[s - 1] : (c[s] ? d : bd[s]);
-                bi[s] = c[s - 1] ? bi[s - 1] : (c[s] ? mm : bi[s]);
-            }
-            bd[0] = c[0] ? d : bd[0];
-            bi[0] = c[0] ? mm : bi[0];
-        }
     }
 }
 
@@ -804,12 +715,12 @@ __global__ __launch_bounds__(SP_THREADS) void som_assign_rank_kernel(
 // (node_stage.hip, knn_stage_prepare_kernel -- same records, same arithmetic), computed by the cloud's last workgroup from the cluster
 // means it already holds in LDS: the no-grad forward needs no launch for it.
 struct KnnPrep {
-    const int64_t *I;                     // [B][M][KI] neighbour table (NULL: no rider)
-    int KI, K, avg, G;
-    long long BM, Lm;
-    float *center;                        // [B][3][M]
-    uint4 *center_p16;                    // one-chunk P16 panel, Lm columns
-    int4 *rec;                            // [Lp] (source column | -1 | -2, three de-centred coordinates)
+    const int64_t *I = nullptr;           // [B][M][KI] neighbour table (NULL: no rider)
+    int KI = 0, K = 0, avg = 0, G = 0;
+    long long BM = 0, Lm = 0;
+    float *center = nullptr;              // [B][3][M]
+    uint4 *center_p16 = nullptr;          // one-chunk P16 panel, Lm columns
+    int4 *rec = nullptr;                  // [Lp] (source column | -1 | -2, three de-centred coordinates)
 };
 
 __global__ __launch_bounds__(SP_THREADS) void som_sort_fill2_kernel(
@@ -866,8 +777,7 @@ __global__ __launch_bounds__(SP_THREADS) void som_sort_fill2_kernel(
     __syncthreads();
     for (int t = tid; t < 3 * M; t += SP_THREADS) {
         const int c = t / M, m = t - c * M;
-        const float denom = __fadd_rn((float)tot[m], 1e-5f);                 // networks.py:142
-        const float mv = __fdiv_rn((float)tsum[t], denom);
+        const float mv = cluster_mean((float)tsum[t], (float)tot[m]);
         mean[t] = mv;
         if (w == 0) {
             if (som_node != nullptr) som_node[(size_t)b * 3 * M + t] = mv;
@@ -974,6 +884,26 @@ __global__ __launch_bounds__(SP_THREADS) void som_sort_fill2_kernel(
     }
 }
 
+// Host dispatch of the selection kernels: f(k, id bits) with both as compile-time constants (std::integral_constant) -- k = 1..4
+// (checked by the callers) and the id bits of the packed keys, 6 for M <= 64 nodes, else 10 (M <= 1024).
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F>
+int som_dispatch(int k, int M, F f)
+{
+    auto bits = [&](auto kk) { return M <= 64 ? f(kk, int_c<6>{}) : f(kk, int_c<10>{}); };
+    switch (k) { case 1: return bits(int_c<1>{}); case 2: return bits(int_c<2>{}); case 3: return bits(int_c<3>{}); default: return bits(int_c<4>{}); }
+}
+
+// launch with `lds` bytes of dynamic LDS: above 48 KB the kernel has to be allowed it first
+template <class... P, class... A>
+int launch_lds(const char *what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args)
+{
+    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return sonet::fail(SONET_ERR_LAUNCH, "%s: LDS", what);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return SONET_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sonet_som_assign_sort_ws_size(int B, int N, int M, int k)
@@ -1002,17 +932,14 @@ static int som_assign_sort_impl(const char *what, const float *x, const float *s
     dim3 grid((unsigned)nW, (unsigned)B), block(SP_THREADS);
     const size_t lds1 = (size_t)M * (sizeof(float4) + 2 * sizeof(int)) + (size_t)3 * k * SP_T * sizeof(float) + (det ? (size_t)(SP_THREADS / 64) * M * sizeof(int) : 0);
     const size_t lds2 = (size_t)M * (3 * sizeof(double) + 3 * sizeof(float) + 5 * sizeof(int)) + (size_t)8 * k * SP_T * sizeof(float);
-#define SP_LAUNCH(KK) do { \
-        if (M <= 64) { if (lds1 > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(som_assign_rank_kernel<KK, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) != hipSuccess) return sonet::fail(SONET_ERR_LAUNCH, "%s: LDS", what); \
-                       hipLaunchKernelGGL((som_assign_rank_kernel<KK, 6>), grid, block, lds1, st, x, node, N, M, nW, min_idx_i32, min_idx_i64, rank16, cnt_part, sum_part, det); } \
-        else         { if (lds1 > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(som_assign_rank_kernel<KK, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) != hipSuccess) return sonet::fail(SONET_ERR_LAUNCH, "%s: LDS", what); \
-                       hipLaunchKernelGGL((som_assign_rank_kernel<KK, 10>), grid, block, lds1, st, x, node, N, M, nW, min_idx_i32, min_idx_i64, rank16, cnt_part, sum_part, det); } } while (0)
-    switch (k) { case 1: SP_LAUNCH(1); break; case 2: SP_LAUNCH(2); break; case 3: SP_LAUNCH(3); break; default: SP_LAUNCH(4); }
-#undef SP_LAUNCH
-    if (lds2 > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(som_sort_fill2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-        return sonet::fail(SONET_ERR_LAUNCH, "%s: LDS", what);
-    hipLaunchKernelGGL(som_sort_fill2_kernel, grid, block, lds2, st, x, sn, min_idx_i32, rank16, cnt_part, sum_part, N, M, k, nW,
-                       count, sum_ws, som_node, row_max, x_aug_sorted, ids_sorted, pos0, node_off, kp);
+    int rc = som_dispatch(k, M, [&](auto kk, auto ib) {
+        return launch_lds(what, som_assign_rank_kernel<decltype(kk)::value, decltype(ib)::value>, grid, block, lds1, st,
+                          x, node, N, M, nW, min_idx_i32, min_idx_i64, rank16, cnt_part, sum_part, det);
+    });
+    if (rc == SONET_OK)
+        rc = launch_lds(what, som_sort_fill2_kernel, grid, block, lds2, st, x, sn, min_idx_i32, rank16, cnt_part, sum_part, N, M, k, nW,
+                        count, sum_ws, som_node, row_max, x_aug_sorted, ids_sorted, pos0, node_off, kp);
+    if (rc != SONET_OK) return rc;
     return sonet::launched(what);
 }
 
@@ -1021,10 +948,8 @@ extern "C" int sonet_som_assign_sort_f32(const float *x, const float *sn, const 
                                          float *som_node, int32_t *row_max, float *x_aug_sorted, int32_t *ids_sorted,
                                          int32_t *pos0, int32_t *node_off, void *ws, sonet_stream_t stream)
 {
-    KnnPrep kp;
-    kp.I = nullptr; kp.KI = kp.K = kp.avg = kp.G = 0; kp.BM = kp.Lm = 0; kp.center = nullptr; kp.center_p16 = nullptr; kp.rec = nullptr;
     return som_assign_sort_impl("sonet_som_assign_sort_f32", x, sn, node, B, N, M, k, min_idx_i32, min_idx_i64, count, sum_ws, som_node, row_max,
-                                x_aug_sorted, ids_sorted, pos0, node_off, ws, kp, stream);
+                                x_aug_sorted, ids_sorted, pos0, node_off, ws, KnnPrep{}, stream);
 }
 
 /* sonet_som_assign_sort_f32 with a sort whose order INSIDE a node does not depend on the arrival order of atomics (wave, slot, lane order
@@ -1035,10 +960,8 @@ extern "C" int sonet_som_assign_sort_det_f32(const float *x, const float *sn, co
                                              float *som_node, int32_t *row_max, float *x_aug_sorted, int32_t *ids_sorted,
                                              int32_t *pos0, int32_t *node_off, void *ws, sonet_stream_t stream)
 {
-    KnnPrep kp;
-    kp.I = nullptr; kp.KI = kp.K = kp.avg = kp.G = 0; kp.BM = kp.Lm = 0; kp.center = nullptr; kp.center_p16 = nullptr; kp.rec = nullptr;
     return som_assign_sort_impl("sonet_som_assign_sort_det_f32", x, sn, node, B, N, M, k, min_idx_i32, min_idx_i64, count, sum_ws, som_node, row_max,
-                                x_aug_sorted, ids_sorted, pos0, node_off, ws, kp, stream, 1);
+                                x_aug_sorted, ids_sorted, pos0, node_off, ws, KnnPrep{}, stream, 1);
 }
 
 /* sonet_som_assign_sort_f32 whose second launch also does sonet_knn_stage_prepare_f32 on the cluster means it computes (KNNModule's index /
@@ -1081,7 +1004,7 @@ extern "C" int sonet_som_sort_group_f32(const float *x, const float *sn, const i
     dim3 grid((unsigned)sonet::ceil_div64(kN, SG_THREADS * SG_PER_THREAD), B), block(SG_THREADS);
     hipLaunchKernelGGL(som_sort_group_kernel, grid, block, (size_t)M * (3 * sizeof(float) + 3 * sizeof(int)), st,
                        x, sn, min_idx_i32, count, sum_ws, N, M, k, som_node, row_max, x_aug_sorted, ids_sorted, pos0, cursor_ws, node_off);
-    hipLaunchKernelGGL(som_sort_fill_kernel, dim3((unsigned)sonet::ceil_div64(kN, 256), B), dim3(256), (size_t)M * 3 * sizeof(float), st,
+    hipLaunchKernelGGL(som_sort_fill_kernel, dim3((unsigned)sonet::ceil_div64(kN, SG_THREADS), B), dim3(SG_THREADS), (size_t)M * 3 * sizeof(float), st,
                        x, sn, count, sum_ws, ids_sorted, N, M, k, x_aug_sorted);
     return sonet::launched(what);
 }
@@ -1120,11 +1043,12 @@ extern "C" int sonet_som_assign_f32(const float *x, const float *node, int B, in
     const size_t lds = (size_t)M * (sizeof(float4) + 3 * sizeof(double) + sizeof(unsigned));
     const char *ek = sonet::knob("SONET_SOM_KEYS");                  // bench / test switch: 0 = the insertion-list kernel
     const bool keys = !(ek && atoi(ek) == 0);
-#define SA_LAUNCH(KK) do { if (keys && M <= 64) hipLaunchKernelGGL((som_assign_keys_kernel<KK, 6>), grid, block, lds, st, x, node, N, M, min_idx_i32, min_idx_i64, count, sum_ws); \
-                           else if (keys) hipLaunchKernelGGL((som_assign_keys_kernel<KK, 10>), grid, block, lds, st, x, node, N, M, min_idx_i32, min_idx_i64, count, sum_ws); \
-                           else hipLaunchKernelGGL((som_assign_kernel<KK>), grid, block, lds, st, x, node, N, M, min_idx_i32, min_idx_i64, count, sum_ws); } while (0)
-    switch (k) { case 1: SA_LAUNCH(1); break; case 2: SA_LAUNCH(2); break; case 3: SA_LAUNCH(3); break; default: SA_LAUNCH(4); }
-#undef SA_LAUNCH
+    som_dispatch(k, M, [&](auto kk, auto ib) {
+        constexpr int K = decltype(kk)::value;
+        if (keys) hipLaunchKernelGGL((som_assign_keys_kernel<K, decltype(ib)::value>), grid, block, lds, st, x, node, N, M, min_idx_i32, min_idx_i64, count, sum_ws);
+        else hipLaunchKernelGGL((som_assign_kernel<K>), grid, block, lds, st, x, node, N, M, min_idx_i32, min_idx_i64, count, sum_ws);
+        return SONET_OK;
+    });
     return sonet::launched(what);
 }
 

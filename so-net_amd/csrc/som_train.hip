@@ -144,11 +144,10 @@ __global__ __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
             // ---- cluster means (networks.py:140-142 arithmetic), accumulators cleared for the next iteration
             for (int m = tid; m < M; m += ST_THREADS) {
                 const unsigned c = cnt[m];
-                const float denom = __fadd_rn((float)c, 1e-5f);
                 const float sx = (float)((double)(long long)sums[m] * unscale);
                 const float sy = (float)((double)(long long)sums[M + m] * unscale);
                 const float sz = (float)((double)(long long)sums[2 * M + m] * unscale);
-                mean[m] = make_float4(__fdiv_rn(sx, denom), __fdiv_rn(sy, denom), __fdiv_rn(sz, denom), c > 0u ? 1.f : 0.f);
+                mean[m] = make_float4(cluster_mean(sx, (float)c), cluster_mean(sy, (float)c), cluster_mean(sz, (float)c), c > 0u ? 1.f : 0.f);
                 sums[m] = 0ull; sums[M + m] = 0ull; sums[2 * M + m] = 0ull;
                 cnt[m] = 0u;
             }
