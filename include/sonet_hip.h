@@ -63,7 +63,7 @@ int sonet_diag_mfma_f16_rate(int random_operands, int iters, double *tflops_out,
  *   slot[1] = bits of max |w| (recorded by the pack kernels in the packed weight's trailer),
  *   slot[2] = fused kernels only: bits of the largest post-BatchNorm-affine activation entering layers 2-4.
  * The caller zeroes the slot, launches, and reads it back at its next synchronisation point; a word above
- * bits(2047.0f) (slot[1]: bits(65504.0f)) or a non-zero slot[0] / slot[1] below bits(2^-6) means the launch's
+ * bits(2047.0f) (slot[1]: bits(65504.0f)) or a non-zero slot[0] / slot[1] below bits(2^-2) (slot[1]: bits(2^-8)) means the launch's
  * results are not f32-class and must be recomputed with sonet_pointmlp_x3_f32 (f32 range).  sonet_hip/ops.py does
  * exactly that (ops.range_scope; Encoder.forward falls back to the x3 arithmetic for the batch). */
 int sonet_range_log_set(uint32_t *slot);

@@ -55,7 +55,7 @@ def _h3_layer(x, Cout=64, seed=0):
 
 
 @pytest.mark.parametrize("what,expect", [("normal", None), ("big", "exceeds 2047"), ("neg_big", "exceeds 2047"), ("nan", "exceeds 2047"),
-                                         ("neg_nan", "exceeds 2047"), ("inf", "exceeds 2047"), ("tiny", "below 2^-6"), ("zero", None)])
+                                         ("neg_nan", "exceeds 2047"), ("inf", "exceeds 2047"), ("tiny", "is below 0.25"), ("zero", None)])
 def test_h3_layer_reports_operand_range(what, expect):
     """Every h3 launch logs max |x| and max |w|; the scope names the launches that left the fp16-split range."""
     from sonet_hip import ops
@@ -122,10 +122,13 @@ def test_fused_kernel_reports_hidden_activation_range():
 
 
 # ------------------------------------------------------------------------------------------ range guard: model level
-@pytest.mark.parametrize("case", ["act_1e4", "act_1e5_bn", "input_3e4", "nan_input", "weight_5e3"])
+@pytest.mark.parametrize("case", ["act_1e4", "act_1e5_bn", "input_3e4", "nan_input", "weight_5e3", "act_1e-4", "input_1e-3", "xyz_columns_100x"])
 def test_encoder_out_of_range_activations_fall_back_to_x3(case):
     """Weights / inputs scaled so that activations leave the fp16-split range: the default (h3) forward must still match
-    the oracle at 1e-5 -- through the guard's x3 recomputation -- and say so once."""
+    the oracle at 1e-5 -- through the guard's x3 recomputation -- and say so once.
+    The small-side cases (act_1e-4, input_1e-3, xyz_columns_100x) may get there on h3 or through the fallback (launch log or weight-side
+    test): what they pin is that the 1e-5 is never lost silently."""
+    small_side = case in ("act_1e-4", "input_1e-3", "xyz_columns_100x")
     from oracle import cpu_oracle as O
     from sonet_hip import ops, synth
     B, N = 2, 600
@@ -148,16 +151,31 @@ def test_encoder_out_of_range_activations_fall_back_to_x3(case):
             inp[key] = inp[key] * 3.0e4
     elif case == "nan_input":
         inp["sn"][1, 2, 77] = float("nan")
+    elif case == "act_1e-4":                                 # layer 1's activations 2^-12 of their usual size (the fused kernel logs only the upper side)
+        for sd in (enc.state_dict(), enc_sd):
+            sd["first_pointnet.layers.0.norm.weight"].mul_(2.0 ** -12)
+            sd["first_pointnet.layers.1.conv.weight"].mul_(2.0 ** 12)
+    elif case == "input_1e-3":                               # coordinates ~1e-3 and nothing beside them (the normals' channels carry zeros)
+        for key in ("pc", "node"):
+            inp[key] = inp[key] * 1.0e-3
+        inp["sn"] = torch.zeros_like(inp["sn"])
+    elif case == "xyz_columns_100x":                         # a corner family of tests/h3_model.py: clouds 0.05 wide beside unit normals,
+        for key in ("pc", "node"):                           # the weights' xyz columns 100 x the normals' columns
+            inp[key] = inp[key] * 0.05
+        for sd in (enc.state_dict(), enc_sd):
+            sd["first_pointnet.layers.0.conv.weight"][:, :3].mul_(100.0)
     enc.to(DEV).eval()
     cls.to(DEV).eval()
     ops._range_warned = False
     old = ops.POINTMLP_PRECISION
     ops.POINTMLP_PRECISION = "h3"
     try:
-        with torch.no_grad(), warnings.catch_warnings(record=True) as w:
+        with torch.no_grad(), warnings.catch_warnings(record=True) as w, ops.kernel_timing() as rec:
             warnings.simplefilter("always")
             feat = enc(inp["pc"].to(DEV), inp["sn"].to(DEV), inp["node"].to(DEV), inp["node_knn_I"].to(DEV))
-        assert any("x3" in str(x.message) for x in w), "the guard did not report the fallback"
+        assert small_side or any("x3" in str(x.message) for x in w), "the guard did not report the fallback"
+        if case == "act_1e-4":                               # the weights' columns stay in range: it is the FUSED kernel that meets this case
+            assert any(n.startswith("pointresnet_fused") for n, _, _ in rec.records), [n for n, _, _ in rec.records]
     finally:
         ops.POINTMLP_PRECISION = old
     ref = O.encoder_forward(enc_sd, inp["pc"], inp["sn"], inp["node"], inp["node_knn_I"])
