@@ -90,6 +90,20 @@ def _chk(t, name, dtype=None, dim=None):
         raise SonetHipError("%s must be %d-D, got shape %s" % (name, dim, tuple(t.shape)))
 
 
+def _chk_cvec(C, **vecs):
+    """Per-channel operands of the BatchNorm / ReLU passes: the kernels index them by channel with no length of their own, so each must be a
+    contiguous float32 tensor of exactly C elements (attribute checks only: no launch, no sync)."""
+    for name, t in vecs.items():
+        _chk(t, name, torch.float32)
+        if t.numel() != C:
+            raise SonetHipError("%s must hold C = %d elements, got %d" % (name, C, t.numel()))
+
+
+def _chk_f32_or_bf16(t, name):
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise SonetHipError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
+
+
 def _same_device(*ts):
     dev = ts[0].device
     for t in ts[1:]:
@@ -2063,8 +2077,9 @@ def channel_stats(y):
 
 def channel_affine_act_(y, scale, shift, relu):
     _chk(y, "y", torch.float32, 3)
-    dev = _same_device(y, scale, shift)
     B, C, L = y.shape
+    _chk_cvec(C, scale=scale, shift=shift)
+    dev = _same_device(y, scale, shift)
     with _lib.on_device(dev), _timed("channel_affine_act"):
         check(_lib.load().sonet_channel_affine_act_f32(ptr(y), ptr(scale), ptr(shift), int(bool(relu)), B, C, L, stream_ptr()),
               "sonet_channel_affine_act_f32")
@@ -2074,8 +2089,10 @@ def channel_affine_act_(y, scale, shift, relu):
 def channel_affine_act(x, scale, shift, relu):
     """y = act(x * scale[c] + shift[c]) out of place, x B x C x L (f32 or bf16 storage)."""
     _chk(x, "x", dim=3)
-    dev = _same_device(x, scale, shift)
+    _chk_f32_or_bf16(x, "x")
     B, C, L = x.shape
+    _chk_cvec(C, scale=scale, shift=shift)
+    dev = _same_device(x, scale, shift)
     y = torch.empty_like(x)
     lib = _lib.load()
     fn = lib.sonet_channel_affine_act_out_f32 if x.dtype == torch.float32 else lib.sonet_channel_affine_act_out_bf16
@@ -2143,8 +2160,10 @@ def bn_rider(gamma, beta, eps, running_mean=None, running_var=None, momentum=0.0
 
 def bn_fwd_coeffs(mean, var, gamma, beta, eps):
     """-> (invstd, scale, shift) of training BatchNorm, one launch."""
-    dev = _same_device(mean, var, gamma, beta)
+    _chk(mean, "mean")
     C = mean.numel()
+    _chk_cvec(C, mean=mean, var=var, gamma=gamma, beta=beta)
+    dev = _same_device(mean, var, gamma, beta)
     out = torch.empty((3, C), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
         check(_lib.load().sonet_bn_fwd_coeffs_f32(ptr(mean), ptr(var), ptr(gamma.detach().contiguous()), ptr(beta.detach().contiguous()),
@@ -2154,8 +2173,13 @@ def bn_fwd_coeffs(mean, var, gamma, beta, eps):
 
 def bn_bwd_coeffs(sums, mean, invstd, gamma, n):
     """sums [2C] f64 of pointwise_bwd_stats -> (a, b, c0, g_gamma, g_beta), one launch."""
-    dev = _same_device(sums, mean, invstd, gamma)
+    _chk(mean, "mean")
     C = mean.numel()
+    _chk_cvec(C, mean=mean, invstd=invstd, gamma=gamma)
+    _chk(sums, "sums", torch.float64)
+    if sums.numel() != 2 * C:
+        raise SonetHipError("sums must hold 2 C = %d elements, got %d" % (2 * C, sums.numel()))
+    dev = _same_device(sums, mean, invstd, gamma)
     out = torch.empty((5, C), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
         check(_lib.load().sonet_bn_bwd_coeffs_f32(ptr(sums), ptr(mean), ptr(invstd), ptr(gamma.detach().contiguous()), float(n), C,
@@ -2167,9 +2191,13 @@ def bn_bwd_coeffs(sums, mean, invstd, gamma, n):
 def pointwise_bwd_stats(gy, raw, scale, shift, relu, want_sums=False):
     """-> (s1, s2) float64 [C]: sum gy*mask, sum gy*mask*raw over (b, l); mask = (raw*scale+shift > 0) if relu."""
     _chk(gy, "gy", dim=3)
+    _chk_f32_or_bf16(gy, "gy")
     _chk(raw, "raw", gy.dtype, 3)
-    dev = _same_device(gy, raw, scale, shift)
+    if raw.shape != gy.shape:
+        raise SonetHipError("raw must have gy's shape %s, got %s" % (tuple(gy.shape), tuple(raw.shape)))
     B, C, L = gy.shape
+    _chk_cvec(C, scale=scale, shift=shift)
+    dev = _same_device(gy, raw, scale, shift)
     sums = torch.empty((2 * C,), dtype=torch.float64, device=dev)
     lib = _lib.load()
     fn = lib.sonet_pointwise_bwd_stats_f32 if gy.dtype == torch.float32 else lib.sonet_pointwise_bwd_stats_bf16
@@ -2183,9 +2211,13 @@ def pointwise_bwd_stats(gy, raw, scale, shift, relu, want_sums=False):
 def pointwise_bwd_apply(gy, raw, scale, shift, relu, a, b, c0):
     """g_raw = a[c] * (gy * mask) + b[c] * raw + c0[c]."""
     _chk(gy, "gy", dim=3)
+    _chk_f32_or_bf16(gy, "gy")
     _chk(raw, "raw", gy.dtype, 3)
-    dev = _same_device(gy, raw, scale, shift, a, b, c0)
+    if raw.shape != gy.shape:
+        raise SonetHipError("raw must have gy's shape %s, got %s" % (tuple(gy.shape), tuple(raw.shape)))
     B, C, L = gy.shape
+    _chk_cvec(C, scale=scale, shift=shift, a=a, b=b, c0=c0)
+    dev = _same_device(gy, raw, scale, shift, a, b, c0)
     out = torch.empty_like(gy)
     lib = _lib.load()
     fn = lib.sonet_pointwise_bwd_apply_f32 if gy.dtype == torch.float32 else lib.sonet_pointwise_bwd_apply_bf16
@@ -2445,6 +2477,7 @@ def bn_running_update_(running_mean, running_var, mean, var, momentum, unbias):
     """running = running*(1-momentum) + momentum*stat in place (variance entering as var*unbias): F.batch_norm's update."""
     for t, n in ((running_mean, "running_mean"), (running_var, "running_var"), (mean, "mean"), (var, "var")):
         _chk(t, n, torch.float32, 1)
+    _chk_cvec(running_mean.numel(), running_var=running_var, mean=mean, var=var)
     dev = _same_device(running_mean, running_var, mean, var)
     with _lib.on_device(dev):
         check(_lib.load().sonet_bn_running_update_f32(ptr(running_mean), ptr(running_var), ptr(mean), ptr(var), float(momentum), float(unbias),
