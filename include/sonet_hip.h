@@ -746,6 +746,35 @@ int sonet_channel_affine_act_f32(float *y, const float *scale, const float *shif
 int sonet_chamfer_nn_f32(const float *q, const float *db, int32_t *nn, int B, int Nq, int Nd,
                          sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * seg_metrics  -- everything the part-segmentation test loop reports, from one read of the score tensor
+ *   reference: part-seg/train.py:87-104 (loss, accuracy, IoU per test batch), models/losses.py:119-189 (compute_iou)
+ * score [B][C][N] f32 (the layout of score_segmenter), seg [B][N] i64 per-point part labels, label [B] i64 category of every cloud,
+ * part_offsets [n_cat + 1] i32 ON THE DEVICE: category c owns the parts part_offsets[c] .. part_offsets[c + 1] - 1.
+ * Outputs (per cloud b):
+ *   pred_out [B][N] i32 (nullable): argmax over the C scores as torch.max(dim=1) on CPU tensors -- the first of equal maxima,
+ *     a NaN beats every number, the first NaN wins;
+ *   correct [B] i32: points with pred == seg;
+ *   nll_sum [B] f64: sum over the points of lse - score[seg], lse = m + log(sum exp(x - m)) with m the maximum, per point in f32
+ *     (one pass: the running sum is rescaled when the running maximum moves; evaluated as (m - score[seg]) + log1p(sum without the
+ *     maximum's own term), two non-negative terms, so that a confident point keeps its relative precision), summed in f64 in a fixed
+ *     order -- lanes, waves, workgroups (partials in ws, added in index order).  No floating-point atomics: two runs give the same bits;
+ *   inter, pred_cnt, gt_cnt [B][C] i32: points with pred == seg == p, pred == p, seg == p; union = pred_cnt + gt_cnt - inter.
+ *     All C bins are kept: a prediction outside the cloud's category lands in its own bin;
+ *   iou [B] f64: over the parts of category label[b] in ascending order, 1.0 where the union is 0, else
+ *     inter / (union + 0.0001); summed sequentially, divided by the number of parts (models/losses.py:162-185, bit for bit);
+ *   bad [B] i32: number of seg values outside [0, C) -- such a point counts as incorrect and enters no gt bin -- plus 1 when label[b]
+ *     is outside [0, n_cat) (or its table entry is not a non-empty range inside [0, C]), which also makes iou[b] NaN.
+ *     bad[b] != 0 makes nll_sum[b] NaN.  Neither case reads out of bounds.
+ *   Non-finite scores are not bad inputs: a point whose scores hold a NaN, a +inf, or nothing but -inf makes its cloud's nll_sum NaN
+ *     (as log_softmax does) with bad[b] == 0; the counts and the IoU follow the arg-max rule above.
+ * The entry zeroes its counters itself on the stream.  ws: sonet_seg_metrics_ws_size bytes (0 for non-positive sizes).
+ * C <= 256, B <= 65535.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sonet_seg_metrics_ws_size(int B, int C, int N);
+int sonet_seg_metrics_f32(const float *score, const int64_t *seg, const int64_t *label, const int32_t *part_offsets, int n_cat,
+                          int32_t *pred_out /* may be NULL */, int32_t *correct, double *nll_sum, int32_t *inter, int32_t *pred_cnt,
+                          int32_t *gt_cnt, double *iou, int32_t *bad, void *ws, int B, int C, int N, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * VARIANTS build only (make -C so-net_amd/csrc variants -> libsonet_hip_variants.so, -DSONET_VARIANTS): kernels that measured
  * slower than what the product dispatches, kept as tested records of the experiments (tests/variants).  The product library
  * does not export them and reads no environment variable.

@@ -1,0 +1,80 @@
+"""Part-segmentation evaluation on the device: loss, accuracy and IoU per epoch with one host transfer at its end.
+
+The reference's test loop (part-seg/train.py:75-104) copies every batch's B x 50 x N score tensor to the host and runs
+``losses.compute_iou``, a Python double loop over clouds and parts.  Here one ``sonet_seg_metrics_f32`` call per batch reads the
+scores once (``ops.seg_metrics``) and ``SegEvaluator`` keeps the epoch's totals in a few device words.
+
+In part-seg/train.py the test loop becomes
+
+    evaluator = SegEvaluator()                                                         # before the loop, reset() per epoch
+    evaluator.update(model.score_segmenter, model.input_seg, model.input_label)         # instead of lines 87-96
+
+and ``evaluator.result()`` after the loop gives the three numbers of lines 102-104.
+"""
+import torch
+
+from . import ops
+from ._lib import SonetHipError
+
+
+def seg_iou(score, seg, label, part_offsets=None):
+    """Per-cloud mean IoU, B float64 on the device: the counterpart of models/losses.py:73-116 (compute_iou_np_array)."""
+    return ops.seg_metrics(score, seg, label, part_offsets).iou
+
+
+class SegEvaluator:
+    """Epoch totals of the segmentation test loop.  ``update`` launches and returns (no sync, no ``.item()``); ``result`` makes the one
+    device-to-host transfer and returns the names of models/segmenter.py:166-168, each as total / count."""
+
+    def __init__(self, part_offsets=None):
+        self.part_offsets = part_offsets
+        self._sums = None              # f64 [3]: sum over clouds of nll_sum / N, correct / N, iou
+        self._ints = None              # i64 [3]: clouds, clouds with bad != 0, sum of bad
+
+    def reset(self):
+        if self._sums is not None:
+            self._sums.zero_()
+            self._ints.zero_()
+
+    def update(self, score, seg, label):
+        m = ops.seg_metrics(score, seg, label, self.part_offsets)
+        if self._sums is None or self._sums.device != score.device:
+            self._sums = torch.zeros(3, dtype=torch.float64, device=score.device)
+            self._ints = torch.zeros(3, dtype=torch.int64, device=score.device)
+        self._sums += torch.stack([m.nll_sum.sum() / m.N, m.correct.sum(dtype=torch.float64) / m.N, m.iou.sum()])
+        self._ints[0] += score.shape[0]
+        self._ints[1:] += torch.stack([(m.bad != 0).sum(), m.bad.sum()])
+        return m
+
+    def result(self):
+        if self._sums is None:
+            raise SonetHipError("SegEvaluator.result() before any update()")
+        host = torch.cat([self._sums, self._ints.to(torch.float64)]).cpu().tolist()       # the one transfer (counts < 2^53: exact)
+        loss, acc, iou = host[:3]
+        count, bad_clouds, bad = (int(v) for v in host[3:])
+        if bad_clouds:
+            raise SonetHipError("segmentation evaluation: %d bad cloud(s) of %d (%d part label(s) outside [0, C) or categories outside "
+                                "the part table)" % (bad_clouds, count, bad))
+        if count == 0:
+            raise SonetHipError("SegEvaluator.result() without any cloud")
+        if loss != loss:
+            raise SonetHipError("segmentation evaluation: the loss of %d clouds is NaN (non-finite scores; no bad label)" % count)
+        return {"test_loss_seg": loss / count, "test_acc_seg": acc / count, "test_iou": iou / count, "count": count}
+
+
+def evaluate_segmentation(encoder, segmenter, assembler, batch_size, evaluator=None):
+    """One pass over the split of a test-mode shapenet ``BatchAssembler``: forward + metrics per batch, no host sync inside the loop;
+    returns ``SegEvaluator.result()``."""
+    from models import networks
+    if assembler.recipe != "shapenet" or assembler.mode == "train":
+        raise SonetHipError("evaluate_segmentation needs a test-mode shapenet BatchAssembler, got recipe %r mode %r"
+                            % (assembler.recipe, assembler.mode))
+    ev = SegEvaluator() if evaluator is None else evaluator
+    ev.reset()
+    encoder.eval()
+    segmenter.eval()
+    with torch.no_grad():
+        for pc, sn, label, seg, node, node_knn_I in assembler.epoch(0, batch_size, shuffle=False):
+            score = networks.segmentation_forward(encoder, segmenter, pc, sn, label, node, node_knn_I)
+            ev.update(score.float().contiguous(), seg.contiguous(), label.contiguous())
+    return ev.result()

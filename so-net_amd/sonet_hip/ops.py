@@ -2423,6 +2423,71 @@ def chamfer_nn(q, db):
     return nn
 
 
+# ------------------------------------------------------------------------------------------ segmentation metrics
+SHAPENET_PART_OFFSETS = (0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47, 50)    # models/losses.py:126-143 as a CSR table
+SEG_METRICS_MAX_C = 256
+_part_tables = {}
+
+
+class SegMetrics:
+    """Device tensors of one ``seg_metrics`` call: pred B x N i32 (None unless asked for), correct B i32, nll_sum B f64, inter / pred_cnt /
+    gt_cnt B x C i32, iou B f64, bad B i32; N the points per cloud."""
+    __slots__ = ("pred", "correct", "nll_sum", "inter", "pred_cnt", "gt_cnt", "iou", "bad", "N")
+
+    @property
+    def union(self):
+        return self.pred_cnt + self.gt_cnt - self.inter
+
+
+def _part_offsets(part_offsets, C):
+    off = tuple(int(v) for v in (SHAPENET_PART_OFFSETS if part_offsets is None else part_offsets))
+    if len(off) < 2 or off[0] != 0 or any(b <= a for a, b in zip(off, off[1:])) or off[-1] > C:
+        raise SonetHipError("part_offsets must start at 0, increase strictly (no empty category) and end at most at C = %d, got %s"
+                            % (C, off))
+    return off
+
+
+def _part_table(off, dev):
+    key = (off, dev.index if dev.index is not None else torch.cuda.current_device())
+    t = _part_tables.get(key)
+    if t is None:
+        t = _part_tables[key] = torch.tensor(off, dtype=torch.int32).to(dev)
+    return t
+
+
+def seg_metrics(score, seg, label, part_offsets=None, want_pred=False):
+    """score B x C x N f32 (score_segmenter's layout), seg B x N i64, label B i64 -> ``SegMetrics`` (include/sonet_hip.h:
+    sonet_seg_metrics_f32).  part_offsets: host sequence of n_cat + 1 part boundaries (default: the ShapeNet-part table)."""
+    if not isinstance(score, torch.Tensor) or score.dim() != 3:
+        raise SonetHipError("score must be a B x C x N torch.Tensor")
+    off = _part_offsets(part_offsets, score.shape[1])         # (host data: checked first, no device needed)
+    _chk(score, "score", torch.float32, 3)
+    _chk(seg, "seg", torch.int64, 2)
+    _chk(label, "label", torch.int64, 1)
+    B, C, N = score.shape
+    if tuple(seg.shape) != (B, N) or label.shape[0] != B:
+        raise SonetHipError("seg must be B x N = %s and label B, got %s and %s" % ((B, N), tuple(seg.shape), tuple(label.shape)))
+    if B < 1 or C < 1 or N < 1 or C > SEG_METRICS_MAX_C or B > 65535:
+        raise SonetHipError("seg_metrics: need 1 <= B <= 65535, 1 <= C <= %d, N >= 1, got B=%d C=%d N=%d" % (SEG_METRICS_MAX_C, B, C, N))
+    dev = _same_device(score, seg, label)
+    table, n_cat = _part_table(off, dev), len(off) - 1
+    lib = _lib.load()
+    r = SegMetrics()
+    r.N = N
+    r.pred = torch.empty((B, N), dtype=torch.int32, device=dev) if want_pred else None
+    ints = torch.empty((2 + 3 * C, B), dtype=torch.int32, device=dev)
+    r.correct, r.bad = ints[0], ints[1]
+    r.inter, r.pred_cnt, r.gt_cnt = (ints[2 + k * C:2 + (k + 1) * C].view(B, C) for k in range(3))
+    f64 = torch.empty((2, B), dtype=torch.float64, device=dev)
+    r.nll_sum, r.iou = f64[0], f64[1]
+    ws = torch.empty((max(1, lib.sonet_seg_metrics_ws_size(B, C, N) // 8),), dtype=torch.float64, device=dev)
+    with _lib.on_device(dev), _timed("seg_metrics"):
+        check(lib.sonet_seg_metrics_f32(ptr(score), ptr(seg), ptr(label), ptr(table), n_cat, ptr(r.pred), ptr(r.correct), ptr(r.nll_sum),
+                                        ptr(r.inter), ptr(r.pred_cnt), ptr(r.gt_cnt), ptr(r.iou), ptr(r.bad), ptr(ws), B, C, N,
+                                        stream_ptr()), "sonet_seg_metrics_f32")
+    return r
+
+
 def mfma_f16_sustained_rate(random_operands=True, iters=4000, device=None):
     """(TFLOP/s, shader GHz) a pure fp16 MFMA loop holds on the whole chip -- the measuring stick beside the nominal
     matrix peak (``sonet_diag_mfma_f16_rate``; with random operands the rate is power-limited, DESIGN.md finding 8)."""
