@@ -775,6 +775,38 @@ int sonet_seg_metrics_f32(const float *score, const int64_t *seg, const int64_t 
                           int32_t *pred_out /* may be NULL */, int32_t *correct, double *nll_sum, int32_t *inter, int32_t *pred_cnt,
                           int32_t *gt_cnt, double *iou, int32_t *bad, void *ws, int B, int C, int N, sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * retrieval_lists  -- class-restricted ranked neighbour lists: for every query shape the members of its own class, nearest first
+ *   reference: shrec16/test.py:68-99 (per test shape: torch.eq + torch.nonzero over the predicted labels, torch.norm of the gathered
+ *   K x 55 rows, torch.sort, the first 1000 rows written to a file)
+ * feat [N][D] f32 one feature row per gallery shape (the 55 class scores there; any width up to 1024 here), label [N] i64 (nullable),
+ * ids [N] i64 what a list names its members by (nullable: the gallery index itself), query [Q] i32 gallery indices ON THE DEVICE
+ * (nullable: every shape in order, and then Q must be N).
+ * Labels: with label == NULL the label of shape j is the arg-max of feat[j][0..D) as torch.max(dim=1) on CPU tensors -- the first of
+ *   equal maxima, a NaN beats every number, the first NaN wins -- and n_label must be D.  label_out [N] i32 (nullable) receives the labels
+ *   used, -1 for a label outside [0, n_label).
+ * Gallery of query i: every j with label[j] == label[i], in ascending j (torch.nonzero's order); i itself is a member.  The position of
+ *   j in that list is its "pos".
+ * Distance: d2 = sum over c ascending of t_c * t_c, t_c = feat[i][c] - feat[j][c], every operation rounded to f32, accumulator from +0,
+ *   no contraction; nn_dist = sqrtf(d2), correctly rounded.
+ * Order: ascending by the 64-bit key (bits of d2) << 32 | pos, every NaN d2 canonicalised to 0x7FC00000 (after +inf; its nn_dist is that
+ *   pattern too).  d2 >= +0, so the order of the bits is the order of the values: a total, deterministic order, exact ties in ascending
+ *   gallery index.  The first count[q] = min(K, top) entries are kept:
+ *   nn_id [Q][top] i64 ids[j] (or j), nn_dist [Q][top] f32, nn_pos [Q][top] i32 (nullable) pos; unused slots hold -1, +inf, -1.
+ * Bad inputs: a shape whose label is outside [0, n_label) is in no class -- as a query it gets count 0, it appears in no list; a query
+ *   index outside [0, N) gets count 0.  bad [1] i32 counts both kinds.  Neither reads out of bounds.
+ * Classes larger than sonet_retrieval_chunk_keys() keys are consumed in chunks of that many keys with the best `top` carried: the same
+ *   list as one sort of everything.  No floating-point atomics: two runs give the same bits.
+ * The entry zeroes its counters itself on the stream.  ws: sonet_retrieval_ws_size bytes (0 for non-positive sizes), 4-byte aligned.
+ * 1 <= N < 2^24, 1 <= D <= 1024, 1 <= top <= 1024, 1 <= n_label <= 65535, 1 <= Q.  The prologue reads the N labels once per non-empty
+ *   class.
+ * ---------------------------------------------------------------------------------------------- */
+int sonet_retrieval_chunk_keys(void);
+size_t sonet_retrieval_ws_size(int N, int D, int Q, int top);
+int sonet_retrieval_lists_f32(const float *feat, const int64_t *label /* may be NULL */, const int64_t *ids /* may be NULL */,
+                              const int32_t *query /* may be NULL */, int n_label, int top, int64_t *nn_id, float *nn_dist,
+                              int32_t *nn_pos /* may be NULL */, int32_t *count, int32_t *label_out /* may be NULL */, int32_t *bad,
+                              void *ws, int N, int D, int Q, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * VARIANTS build only (make -C so-net_amd/csrc variants -> libsonet_hip_variants.so, -DSONET_VARIANTS): kernels that measured
  * slower than what the product dispatches, kept as tested records of the experiments (tests/variants).  The product library
  * does not export them and reads no environment variable.

@@ -161,6 +161,9 @@ SIGNATURES = {
     "sonet_chamfer_nn_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_seg_metrics_ws_size": [_i, _i, _i],
     "sonet_seg_metrics_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_retrieval_chunk_keys": [],
+    "sonet_retrieval_ws_size": [_i, _i, _i, _i],
+    "sonet_retrieval_lists_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 _RESTYPES = {
     "sonet_build_arch": ctypes.c_char_p,
@@ -189,6 +192,7 @@ _RESTYPES = {
     "sonet_som_assign_sort_ws_size": ctypes.c_size_t,
     "sonet_chamfer_nn2_ws_size": ctypes.c_size_t,
     "sonet_seg_metrics_ws_size": ctypes.c_size_t,
+    "sonet_retrieval_ws_size": ctypes.c_size_t,
 }
 
 # entry points that only the variants build exports (bound when present)

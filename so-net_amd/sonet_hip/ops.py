@@ -2488,6 +2488,85 @@ def seg_metrics(score, seg, label, part_offsets=None, want_pred=False):
     return r
 
 
+# ------------------------------------------------------------------------------------------ retrieval lists
+RETRIEVAL_MAX_TOP = 1024
+RETRIEVAL_MAX_D = 1024
+RETRIEVAL_MAX_LABEL = 65535
+RETRIEVAL_MAX_N = (1 << 24) - 1
+
+
+class RetrievalLists:
+    """Device tensors of one ``retrieval_lists`` call: nn_id Q x top i64, nn_dist Q x top f32, nn_pos Q x top i32 (None unless asked
+    for), count Q i32, labels N i32 (the labels used, -1 for one outside [0, n_label)), bad 1 i32; top the list length."""
+    __slots__ = ("nn_id", "nn_dist", "nn_pos", "count", "labels", "bad", "top")
+
+
+def retrieval_lists(feat, labels=None, ids=None, query=None, top=1000, n_label=None, want_pos=False):
+    """feat N x D f32, labels N i64 (None: the arg-max of every row, and n_label = D), ids N i64 (None: the gallery index), query: a
+    device i32 tensor of gallery indices (values checked by the kernel, which counts the bad ones), or a host sequence / CPU tensor
+    (values checked here, then copied), or None for every shape -> ``RetrievalLists`` (include/sonet_hip.h: sonet_retrieval_lists_f32).
+    Nothing is read back: the call returns with the launches queued."""
+    if not isinstance(feat, torch.Tensor) or feat.dim() != 2:
+        raise SonetHipError("feat must be an N x D torch.Tensor")
+    N, D = feat.shape
+    # attribute and host-value checks first (no device needed), then _chk: CUDA and contiguous
+    for name, t, dtype in (("feat", feat, torch.float32), ("labels", labels, torch.int64), ("ids", ids, torch.int64)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise SonetHipError("%s must be a %s torch.Tensor, got %s" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+        if name != "feat" and tuple(t.shape) != (N,):
+            raise SonetHipError("%s must hold N = %d elements, got shape %s" % (name, N, tuple(t.shape)))
+    if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= RETRIEVAL_MAX_TOP:
+        raise SonetHipError("top must be an int in [1, %d], got %r" % (RETRIEVAL_MAX_TOP, top))
+    if not 1 <= N <= RETRIEVAL_MAX_N or not 1 <= D <= RETRIEVAL_MAX_D:
+        raise SonetHipError("retrieval_lists: need 1 <= N < 2^24 and 1 <= D <= %d, got N=%d D=%d" % (RETRIEVAL_MAX_D, N, D))
+    if labels is None:
+        if n_label is not None and n_label != D:
+            raise SonetHipError("n_label=%r but labels derived from the features are the arg-max over D = %d columns" % (n_label, D))
+        n_label = D
+    elif n_label is None:
+        raise SonetHipError("n_label is needed with given labels")
+    if isinstance(n_label, bool) or not isinstance(n_label, int) or not 1 <= n_label <= RETRIEVAL_MAX_LABEL:
+        raise SonetHipError("n_label must be an int in [1, %d], got %r" % (RETRIEVAL_MAX_LABEL, n_label))
+    host_query = None
+    if isinstance(query, torch.Tensor) and query.is_cuda:
+        if query.dtype != torch.int32 or query.dim() != 1 or query.shape[0] < 1:
+            raise SonetHipError("a device query must be a non-empty 1-D int32 tensor, got %s %s" % (tuple(query.shape), query.dtype))
+    elif query is not None:
+        host_query = np.asarray(query.numpy() if isinstance(query, torch.Tensor) else query)
+        if host_query.ndim != 1 or host_query.size < 1 or host_query.dtype.kind not in "iu":
+            raise SonetHipError("query must be a non-empty 1-D sequence of integers")
+        if host_query.min() < 0 or host_query.max() >= N:
+            raise SonetHipError("query index outside [0, N = %d): min %d max %d" % (N, host_query.min(), host_query.max()))
+    _chk(feat, "feat")
+    if labels is not None:
+        _chk(labels, "labels")
+    if ids is not None:
+        _chk(ids, "ids")
+    dev = _same_device(feat, labels, ids)
+    if host_query is not None:
+        query = torch.from_numpy(host_query.astype(np.int32)).to(dev)
+    if query is not None:
+        _chk(query, "query")
+        _same_device(feat, query)
+    Q = N if query is None else query.shape[0]
+    lib = _lib.load()
+    r = RetrievalLists()
+    r.top = top
+    r.nn_id = torch.empty((Q, top), dtype=torch.int64, device=dev)
+    r.nn_dist = torch.empty((Q, top), dtype=torch.float32, device=dev)
+    r.nn_pos = torch.empty((Q, top), dtype=torch.int32, device=dev) if want_pos else None
+    ints = torch.empty((Q + N + 1,), dtype=torch.int32, device=dev)
+    r.count, r.labels, r.bad = ints[:Q], ints[Q:Q + N], ints[Q + N:]
+    ws = torch.empty((lib.sonet_retrieval_ws_size(N, D, Q, top) // 4,), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev), _timed("retrieval_lists"):
+        check(lib.sonet_retrieval_lists_f32(ptr(feat), ptr(labels), ptr(ids), ptr(query), n_label, top, ptr(r.nn_id), ptr(r.nn_dist),
+                                            ptr(r.nn_pos), ptr(r.count), ptr(r.labels), ptr(r.bad), ptr(ws), N, D, Q, stream_ptr()),
+              "sonet_retrieval_lists_f32")
+    return r
+
+
 def mfma_f16_sustained_rate(random_operands=True, iters=4000, device=None):
     """(TFLOP/s, shader GHz) a pure fp16 MFMA loop holds on the whole chip -- the measuring stick beside the nominal
     matrix peak (``sonet_diag_mfma_f16_rate``; with random operands the rate is power-limited, DESIGN.md finding 8)."""
