@@ -746,6 +746,36 @@ int sonet_channel_affine_act_f32(float *y, const float *scale, const float *shif
 int sonet_chamfer_nn_f32(const float *q, const float *db, int32_t *nn, int B, int Nq, int Nd,
                          sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * chamfer_loss / chamfer_grad -- the Chamfer loss as one fused operator with its own gradient
+ *   reference: models/losses.py:237-290 (ChamferLoss.forward), :17-27 (robust_norm)
+ * pred [B][3][M] f32 the predicted cloud, gt [B][3][N] f32 the ground truth.
+ * sonet_chamfer_loss_f32: both directions in one launch (the search of sonet_chamfer_nn_f32: same indices), then a small launch for
+ * the sums.  Outputs:
+ *   nn_pg [B][M] i32 nearest gt point of every predicted point, nn_gp [B][N] i32 nearest predicted point of every gt point;
+ *   elem_fwd [B][M] f32, elem_bwd [B][N] f32: robust_norm of (chosen neighbour - point): d = sel - q per coordinate, then
+ *     sqrt(((dx*dx + dy*dy) + dz*dz) + 1e-8f), every operation rounded to f32, the root correctly rounded.  Computed from the chosen
+ *     neighbour's coordinates: a point with a NaN coordinate has index 0 and a NaN element;
+ *   sums [B][2] f64: per cloud the sum of elem_fwd and of elem_bwd, added in float64 in a fixed order (no floating-point atomics:
+ *     two runs give the same bits).
+ * Each of nn_pg, nn_gp, elem_fwd, elem_bwd may be NULL and is then not written; sums is always written.
+ * ws: sonet_chamfer_loss_ws_size bytes (0 for non-positive sizes).
+ * sonet_chamfer_grad_f32: dpred [B][3][M] f32 = d(gf * forward_loss + gb * backward_loss) / d pred at the given indices, where
+ * forward_loss = mean of elem_fwd, backward_loss = mean of elem_bwd, and gscale = {gf, gb} are two f32 ON THE DEVICE:
+ *   dpred[b][c][m] = f32( gf/(B M) (p[c][m] - gt[c][nn_pg[m]]) / elem_fwd[m]
+ *                         + sum over n with nn_gp[n] == m, ascending n, of gb/(B N) (p[c][m] - gt[c][n]) / elem_bwd[n] ),
+ * the differences, quotients and the sum in float64, rounded once.  Only the predicted cloud gets a gradient.  The index arrays are
+ * the caller's: an entry outside its range ([0, N) for nn_pg, [0, M) for nn_gp) contributes nothing, is never used as an address, and
+ * is counted in *bad (one i32, zeroed by the entry).
+ * B <= 65535.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sonet_chamfer_loss_ws_size(int B, int M, int N);
+int sonet_chamfer_loss_f32(const float *pred, const float *gt, int32_t *nn_pg /* may be NULL */, int32_t *nn_gp /* may be NULL */,
+                           float *elem_fwd /* may be NULL */, float *elem_bwd /* may be NULL */, double *sums, void *ws, int B, int M,
+                           int N, sonet_stream_t stream);
+int sonet_chamfer_grad_f32(const float *pred, const float *gt, const int32_t *nn_pg, const int32_t *nn_gp, const float *elem_fwd,
+                           const float *elem_bwd, const float *gscale, float *dpred, int32_t *bad, int B, int M, int N,
+                           sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * seg_metrics  -- everything the part-segmentation test loop reports, from one read of the score tensor
  *   reference: part-seg/train.py:87-104 (loss, accuracy, IoU per test batch), models/losses.py:119-189 (compute_iou)
  * score [B][C][N] f32 (the layout of score_segmenter), seg [B][N] i64 per-point part labels, label [B] i64 category of every cloud,

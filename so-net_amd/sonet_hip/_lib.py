@@ -159,6 +159,9 @@ SIGNATURES = {
     "sonet_pointwise_bwd_apply_bf16": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_channel_affine_act_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_chamfer_nn_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_chamfer_loss_ws_size": [_i, _i, _i],
+    "sonet_chamfer_loss_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_chamfer_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_seg_metrics_ws_size": [_i, _i, _i],
     "sonet_seg_metrics_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_retrieval_chunk_keys": [],
@@ -191,6 +194,7 @@ _RESTYPES = {
     "sonet_pooled_dgrad_tail_ws_size": ctypes.c_size_t,
     "sonet_som_assign_sort_ws_size": ctypes.c_size_t,
     "sonet_chamfer_nn2_ws_size": ctypes.c_size_t,
+    "sonet_chamfer_loss_ws_size": ctypes.c_size_t,
     "sonet_seg_metrics_ws_size": ctypes.c_size_t,
     "sonet_retrieval_ws_size": ctypes.c_size_t,
 }

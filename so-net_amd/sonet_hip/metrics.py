@@ -1,4 +1,5 @@
-"""Part-segmentation evaluation on the device: loss, accuracy and IoU per epoch with one host transfer at its end.
+"""Evaluation loops on the device: per-epoch totals with one host transfer at the end (part segmentation: loss, accuracy and IoU;
+autoencoder: the Chamfer test loss -- ``ChamferEvaluator`` / ``evaluate_autoencoder`` at the end of this file).
 
 The reference's test loop (part-seg/train.py:75-104) copies every batch's B x 50 x N score tensor to the host and runs
 ``losses.compute_iou``, a Python double loop over clouds and parts.  Here one ``sonet_seg_metrics_f32`` call per batch reads the
@@ -77,4 +78,64 @@ def evaluate_segmentation(encoder, segmenter, assembler, batch_size, evaluator=N
         for pc, sn, label, seg, node, node_knn_I in assembler.epoch(0, batch_size, shuffle=False):
             score = networks.segmentation_forward(encoder, segmenter, pc, sn, label, node, node_knn_I)
             ev.update(score.float().contiguous(), seg.contiguous(), label.contiguous())
+    return ev.result()
+
+
+class ChamferEvaluator:
+    """Epoch totals of the autoencoder test loop (autoencoder/train.py:79-99).  ``update`` launches ``ops.chamfer_terms`` without the
+    index and element outputs and adds each cloud's forward and backward loss into float64 device words (no sync, no ``.item()``);
+    ``result`` makes the one device-to-host transfer.  ``test_loss`` is the number of train.py:94-96, sum of (batch loss x batch size)
+    / clouds: all clouds of an epoch share M and N, so it equals the mean over clouds of the per-cloud loss."""
+
+    def __init__(self):
+        self._sums = None              # f64 [2]: sum over clouds of forward loss, of backward loss
+        self._ints = None              # i64 [2]: clouds, clouds whose loss is NaN
+
+    def reset(self):
+        if self._sums is not None:
+            self._sums.zero_()
+            self._ints.zero_()
+
+    def update(self, predicted_pc, gt):
+        t = ops.chamfer_terms(predicted_pc, gt, want_nn=False, want_elems=False)
+        if self._sums is None or self._sums.device != gt.device:
+            self._sums = torch.zeros(2, dtype=torch.float64, device=gt.device)
+            self._ints = torch.zeros(2, dtype=torch.int64, device=gt.device)
+        per_cloud = torch.stack([t.sums[:, 0] / t.M, t.sums[:, 1] / t.N], dim=1)          # B x 2 f64
+        self._sums += per_cloud.sum(dim=0)
+        self._ints[0] += gt.shape[0]
+        self._ints[1] += torch.isnan(per_cloud).any(dim=1).sum()
+        return per_cloud.sum(dim=1).float()                                                # loss_array (models/losses.py:289)
+
+    def result(self):
+        if self._sums is None:
+            raise SonetHipError("ChamferEvaluator.result() before any update()")
+        host = torch.cat([self._sums, self._ints.to(torch.float64)]).cpu().tolist()       # the one transfer (counts < 2^53: exact)
+        fwd, bwd = host[:2]
+        count, nan_clouds = int(host[2]), int(host[3])
+        if count == 0:
+            raise SonetHipError("ChamferEvaluator.result() without any cloud")
+        if nan_clouds or fwd != fwd or bwd != bwd:
+            raise SonetHipError("autoencoder evaluation: the Chamfer loss of %d cloud(s) of %d is NaN (non-finite coordinates)"
+                                % (nan_clouds, count))
+        return {"test_loss": (fwd + bwd) / count, "forward": fwd / count, "backward": bwd / count, "count": count}
+
+
+def evaluate_autoencoder(encoder, decoder, assembler, batch_size, evaluator=None):
+    """One pass over the split of a test-mode ``BatchAssembler``: encoder, decoder and ``ChamferEvaluator.update`` per batch under
+    ``no_grad`` (models/autoencoder.py:105-119 without the pyramid terms the test loss does not read), no host sync inside the loop, the
+    last batch may be short; returns ``ChamferEvaluator.result()``."""
+    if assembler.mode == "train":
+        raise SonetHipError("evaluate_autoencoder needs a test-mode BatchAssembler, got mode %r" % (assembler.mode,))
+    ev = ChamferEvaluator() if evaluator is None else evaluator
+    ev.reset()
+    encoder.eval()
+    decoder.eval()
+    shapenet = assembler.recipe == "shapenet"            # (pc, sn, label, seg, node, knn) there; (pc, sn, label, node, knn[, idx]) otherwise
+    with torch.no_grad():
+        for batch in assembler.epoch(0, batch_size, shuffle=False):
+            pc, sn = batch[0], batch[1]
+            node, node_knn_I = (batch[4], batch[5]) if shapenet else (batch[3], batch[4])
+            predicted_pc = decoder(encoder(pc, sn, node, node_knn_I, False, None))
+            ev.update(predicted_pc.float().contiguous(), pc.contiguous())
     return ev.result()

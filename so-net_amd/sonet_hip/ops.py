@@ -2423,6 +2423,107 @@ def chamfer_nn(q, db):
     return nn
 
 
+# ------------------------------------------------------------------------------------------ fused Chamfer loss
+class ChamferTerms:
+    """Device tensors of one ``chamfer_terms`` call: nn_pg B x M i32 and nn_gp B x N i32 (None unless asked for), elem_fwd B x M f32 and
+    elem_bwd B x N f32 (None unless asked for), sums B x 2 f64 (per cloud: sum of elem_fwd, sum of elem_bwd); M and N the point counts."""
+    __slots__ = ("nn_pg", "nn_gp", "elem_fwd", "elem_bwd", "sums", "M", "N")
+
+
+def _chk_clouds(pred, gt):
+    """pred B x 3 x M, gt B x 3 x N: contiguous f32 CUDA tensors on one device; only the predicted cloud may ask for a gradient."""
+    _chk(pred, "pred", torch.float32, 3)
+    _chk(gt, "gt", torch.float32, 3)
+    if pred.shape[1] != 3 or gt.shape[1] != 3:
+        raise SonetHipError("pred and gt must have 3 channels (B x 3 x points), got %s and %s" % (tuple(pred.shape), tuple(gt.shape)))
+    if pred.shape[0] != gt.shape[0]:
+        raise SonetHipError("pred and gt must hold the same number of clouds, got B = %d and %d" % (pred.shape[0], gt.shape[0]))
+    if gt.requires_grad:
+        raise SonetHipError("gt must not require a gradient: the Chamfer loss differentiates the predicted cloud only")
+    B, _, M = pred.shape
+    N = gt.shape[2]
+    if B < 1 or M < 1 or N < 1 or B > 65535:
+        raise SonetHipError("chamfer: need 1 <= B <= 65535, M >= 1, N >= 1, got B=%d M=%d N=%d" % (B, M, N))
+    return _same_device(pred, gt), B, M, N
+
+
+def chamfer_terms(pred, gt, want_nn=True, want_elems=True):
+    """pred B x 3 x M, gt B x 3 x N f32 -> ``ChamferTerms`` (include/sonet_hip.h: sonet_chamfer_loss_f32): both nearest-neighbour
+    directions, the robust_norm elements and their per-cloud float64 sums from one launch plus a small one for the sums."""
+    dev, B, M, N = _chk_clouds(pred, gt)
+    lib = _lib.load()
+    r = ChamferTerms()
+    r.M, r.N = M, N
+    r.nn_pg = r.nn_gp = r.elem_fwd = r.elem_bwd = None
+    if want_nn:
+        nn = torch.empty((B * (M + N),), dtype=torch.int32, device=dev)
+        r.nn_pg, r.nn_gp = nn[:B * M].view(B, M), nn[B * M:].view(B, N)
+    if want_elems:
+        el = torch.empty((B * (M + N),), dtype=torch.float32, device=dev)
+        r.elem_fwd, r.elem_bwd = el[:B * M].view(B, M), el[B * M:].view(B, N)
+    f64 = torch.empty((2 * B + lib.sonet_chamfer_loss_ws_size(B, M, N) // 8,), dtype=torch.float64, device=dev)
+    r.sums = f64[:2 * B].view(B, 2)
+    with _lib.on_device(dev), _timed("chamfer_loss"):
+        check(lib.sonet_chamfer_loss_f32(ptr(pred), ptr(gt), ptr(r.nn_pg), ptr(r.nn_gp), ptr(r.elem_fwd), ptr(r.elem_bwd), ptr(r.sums),
+                                         ptr(f64[2 * B:]), B, M, N, stream_ptr()), "sonet_chamfer_loss_f32")
+    return r
+
+
+def chamfer_grad(pred, gt, terms, gscale):
+    """d(gf * forward_loss + gb * backward_loss) / d pred at the indices and elements of ``terms``; gscale: the two f32 (gf, gb) on the
+    device -> (dpred B x 3 x M f32, bad 1 i32: index entries outside their range, which contribute nothing).  No host sync."""
+    dev, B, M, N = _chk_clouds(pred, gt)
+    if terms.nn_pg is None or terms.elem_fwd is None:
+        raise SonetHipError("chamfer_grad needs the indices and the elements (chamfer_terms(want_nn=True, want_elems=True))")
+    for t, name, dtype, shape in ((terms.nn_pg, "nn_pg", torch.int32, (B, M)), (terms.nn_gp, "nn_gp", torch.int32, (B, N)),
+                                  (terms.elem_fwd, "elem_fwd", torch.float32, (B, M)), (terms.elem_bwd, "elem_bwd", torch.float32, (B, N)),
+                                  (gscale, "gscale", torch.float32, (2,))):
+        _chk(t, name, dtype)
+        if tuple(t.shape) != shape:
+            raise SonetHipError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+    _same_device(pred, terms.nn_pg, terms.nn_gp, terms.elem_fwd, terms.elem_bwd, gscale)
+    dpred = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
+    bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev), _timed("chamfer_grad"):
+        check(_lib.load().sonet_chamfer_grad_f32(ptr(pred), ptr(gt), ptr(terms.nn_pg), ptr(terms.nn_gp), ptr(terms.elem_fwd),
+                                                 ptr(terms.elem_bwd), ptr(gscale), ptr(dpred), ptr(bad), B, M, N, stream_ptr()),
+              "sonet_chamfer_grad_f32")
+    return dpred, bad
+
+
+class _ChamferLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt):
+        t = chamfer_terms(pred, gt)
+        B = pred.shape[0]
+        tot = t.sums.sum(dim=0)                                       # f64 [2], on the device
+        forward_loss, backward_loss = (tot[0] / (B * t.M)).float(), (tot[1] / (B * t.N)).float()
+        forward_arr, backward_arr = (t.sums[:, 0] / t.M).float(), (t.sums[:, 1] / t.N).float()
+        ctx.save_for_backward(pred, gt, t.nn_pg, t.nn_gp, t.elem_fwd, t.elem_bwd)
+        ctx.mark_non_differentiable(forward_arr, backward_arr)
+        return forward_loss, backward_loss, forward_arr, backward_arr
+
+    @staticmethod
+    def backward(ctx, gf, gb, _ga, _gb):
+        pred, gt, nn_pg, nn_gp, elem_fwd, elem_bwd = ctx.saved_tensors
+        t = ChamferTerms()
+        t.nn_pg, t.nn_gp, t.elem_fwd, t.elem_bwd, t.M, t.N = nn_pg, nn_gp, elem_fwd, elem_bwd, pred.shape[2], gt.shape[2]
+        zero = None
+        if gf is None or gb is None:
+            zero = torch.zeros((), dtype=torch.float32, device=pred.device)
+        gscale = torch.stack([zero if gf is None else gf.float(), zero if gb is None else gb.float()])
+        dpred, _bad = chamfer_grad(pred, gt, t, gscale)
+        return dpred, None
+
+
+def chamfer_loss(pred, gt):
+    """The Chamfer loss of models/losses.py:237-290 as one operator: pred B x 3 x M (may require a gradient), gt B x 3 x N ->
+    (forward_loss, backward_loss: f32 scalars, differentiable with respect to pred; forward_loss_array, backward_loss_array: B f32, not
+    differentiable).  The sums are float64 on the device and rounded once; the backward is one ``sonet_chamfer_grad_f32`` call."""
+    _chk_clouds(pred, gt)
+    return _ChamferLoss.apply(pred, gt)
+
+
 # ------------------------------------------------------------------------------------------ segmentation metrics
 SHAPENET_PART_OFFSETS = (0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47, 50)    # models/losses.py:126-143 as a CSR table
 SEG_METRICS_MAX_C = 256
