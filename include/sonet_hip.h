@@ -837,6 +837,36 @@ int sonet_retrieval_lists_f32(const float *feat, const int64_t *label /* may be 
                               int32_t *nn_pos /* may be NULL */, int32_t *count, int32_t *label_out /* may be NULL */, int32_t *bad,
                               void *ws, int N, int D, int Q, sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * upconv3x3  -- the decoder's up-convolution layer as one launch (inference; so-net_amd/csrc/upconv.hip)
+ *   reference: models/layers.py:214-240 (UpConv: nn.Upsample(scale_factor=2), then Conv2d 3x3 pad 1 + BatchNorm + activation),
+ *   callers:   models/networks.py:393-431 (DecoderConv, six layers from 1 x 1 to 64 x 64)
+ * x [B][Cin][H][W] f32, W [Cout][Cin][3][3] f32, scale / shift [Cout] f32 (conv bias and eval-mode BatchNorm folded in by the caller),
+ * y [B][Cout][2H][2W] f32 (fully overwritten):
+ *   y = act(conv3x3_pad1(upsample2_nearest(x), W) * scale + shift),   act = ReLU when relu != 0, identity otherwise.
+ * Computed in the folded form: output pixel (2i + py, 2j + px) = sum over dy, dx in {0, 1} and the input channels of
+ * wf[py][px][dy][dx] x[i - 1 + py + dy][j - 1 + px + dx] (zeros outside the map), where in y the taps are {w[0], w[1] + w[2]} for py = 0 and
+ * {w[0] + w[1], w[2]} for py = 1, and the same in x; the sums are formed in float64 and rounded to f32 by the pack.  The upsampled tensor
+ * is never written.  Arithmetic: the three-term fp16 split of sonet_pointmlp_h3p (fp16(32 v) + fp16 residual of both operands, f32
+ * accumulation in chains of at most 1024 products): f32-class, with the fp16 operand range.  range_log (nullable): the 8-word slot of
+ * "Range log" above, passed explicitly -- word 0 = bits of max |x| over the launch's input (a NaN sorts above +inf), word 1 = bits of the
+ * largest magnitude among the weights and their folded sums (recorded by the pack); the limits are those of sonet_pointmlp_h3p
+ * (|x| <= 2047, |w| <= 2047).
+ * sonet_upconv3x3_pack_f32 writes sonet_upconv3x3_pack_size(Cin, Cout) bytes (0 for an unsupported shape), 16-byte aligned; a pack
+ * serves every B, H, W.
+ * Shapes: B >= 1, Cin >= 1 (any: the last 16-channel chunk is zero-filled), Cout a multiple of SONET_UPCONV_COUT_BLOCK,
+ * 1 <= H, W <= SONET_UPCONV_MAX_HW, B H W < 2^31 - 2^16; anything else returns SONET_ERR_INVALID_ARG / SONET_ERR_UNSUPPORTED before any
+ * launch.  A workgroup covers SONET_UPCONV_TILE_PIXELS consecutive low-resolution pixels of the flattened (b, i, j) axis and
+ * SONET_UPCONV_COUT_BLOCK output channels, and stages SONET_UPCONV_K_CHUNK input channels at a time.
+ * ---------------------------------------------------------------------------------------------- */
+#define SONET_UPCONV_TILE_PIXELS 128
+#define SONET_UPCONV_K_CHUNK 16
+#define SONET_UPCONV_COUT_BLOCK 32
+#define SONET_UPCONV_MAX_HW 64
+size_t sonet_upconv3x3_pack_size(int Cin, int Cout);
+int sonet_upconv3x3_pack_f32(const float *W, void *Wp, int Cin, int Cout, sonet_stream_t stream);
+int sonet_upconv3x3_f32(const float *x, const void *Wp, const float *scale, const float *shift, int relu, float *y,
+                        int B, int Cin, int Cout, int H, int W, uint32_t *range_log, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * VARIANTS build only (make -C so-net_amd/csrc variants -> libsonet_hip_variants.so, -DSONET_VARIANTS): kernels that measured
  * slower than what the product dispatches, kept as tested records of the experiments (tests/variants).  The product library
  * does not export them and reads no environment variable.

@@ -1117,13 +1117,20 @@ class MyConv2d(_FusedPointwise):
 
 
 class UpConv(nn.Module):
-    """Upsample x2 + 3x3 conv (models/layers.py:214-240); decoder only, stays on aten."""
+    """Upsample x2 + 3x3 conv (models/layers.py:214-240); decoder only.
+
+    ``fused`` (default False; ``DecoderConv`` sets it from ``opt.decoder_fused``): an eval-mode inference call on an f32 GPU tensor runs
+    upsample, conv, bias, BatchNorm and ReLU as ONE launch of the fused up-convolution (``sonet_hip.ops.upconv3x3``, fp16-split
+    arithmetic, range-guarded like the point-wise layers) -- when the precision is "h3", the normalization is 'batch' or None, the
+    activation 'relu' or None and the shape is one the operator takes.  Everything else -- training, autograd, another precision (the
+    range guard's re-run included), another normalization or shape -- runs the two aten lines below, as without the attribute."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, output_padding=0, bias=True,
                  activation=None, normalization=None):
         super().__init__()
         self.activation = activation
         self.normalization = normalization
+        self.fused = False
         self.up_sample = nn.Upsample(scale_factor=2)
         self.conv = MyConv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True,
                              activation=activation, normalization=normalization)
@@ -1137,7 +1144,28 @@ class UpConv(nn.Module):
                 if m.bias is not None:
                     m.bias.data.fill_(0.001)
 
+    def _fused_ok(self, x):
+        conv = self.conv.conv
+        return (self.fused and not self.training and _ops.POINTMLP_PRECISION == "h3" and x.dim() == 4 and x.is_cuda
+                and x.dtype == torch.float32 and not x.requires_grad and _ops.is_inference(x)
+                and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
+                and conv.weight.is_cuda and conv.weight.dtype == torch.float32
+                and _ops.upconv3x3_supported(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]))
+
+    def _packed_upconv(self):
+        """The up-convolution pack of the 3x3 weight, rebuilt when the weight's version counter (or storage) has moved."""
+        w = self.conv.conv.weight
+        key = (w._version, w.data_ptr(), w.device)
+        if getattr(self, '_wup_key', None) != key:
+            with torch.no_grad():
+                self._wup = _ops.upconv3x3_pack(w.detach().contiguous())
+            self._wup_key = key
+        return self._wup
+
     def forward(self, x):
+        if self._fused_ok(x):
+            scale, shift = self.conv._eval_affine()
+            return _ops.upconv3x3(x.contiguous(), self._packed_upconv(), scale, shift, self.activation == 'relu', self.conv.conv.out_channels)
         return self.conv(self.up_sample(x))
 
 

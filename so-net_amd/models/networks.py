@@ -719,8 +719,10 @@ class DecoderConv(nn.Module):
         self.output_point_num = opt.output_conv_pc_num
         chans = [F, int(F), int(F / 2), int(F / 4), int(F / 8), int(F / 8), int(F / 8)]
         for i in range(6):
-            setattr(self, "deconv%d" % (i + 1), UpConv(chans[i], chans[i + 1], activation=opt.activation,
-                                                         normalization=opt.normalization))
+            up = UpConv(chans[i], chans[i + 1], activation=opt.activation, normalization=opt.normalization)
+            # opt.decoder_fused: inference runs each up-convolution as one launch (ops.upconv3x3); absent = the aten layers
+            up.fused = bool(getattr(opt, "decoder_fused", False))
+            setattr(self, "deconv%d" % (i + 1), up)
             if i >= 3:
                 setattr(self, "conv2pc%d" % (i + 1), ConvToPC(chans[i + 1], opt))
 

@@ -924,14 +924,15 @@ class range_scope:
             elif low_ok and 0 < x < _B_XLOW:
                 out.append((name, "max |x| = %g is below %g (fp16 residuals go subnormal)" % (_bits_to_float(x), _bits_to_float(_B_XLOW))))
             # Weight side.  The second-generation layer keeps fp16(w) (limits 65504 and 2^-8).  The fused first PointNet and the third
-            # generation (pointmlph3p*) keep fp16(32 w) + fp16(32 w - hi): |w| <= 2047, and max |w| >= 2^-8 -- below that the residual
-            # piece is an fp16 subnormal with absolute error 2^-30 on w, i.e. up to 2^-22 relative (the fused kernel logs 32 |w|).
+            # generation (pointmlph3p*; the up-convolution upconv3x3* on its folded weights) keep fp16(32 w) + fp16(32 w - hi): |w| <= 2047,
+            # and max |w| >= 2^-8 -- below that the residual piece is an fp16 subnormal with absolute error 2^-30 on w, i.e. up to 2^-22
+            # relative (the fused kernel logs 32 |w|).
             if name.startswith("pointresnet_fused"):
                 if wt > _B_65504:
                     out.append((name, "max |w| = %g exceeds %g" % (_bits_to_float(wt) / 32.0, 65504.0 / 32.0)))
                 elif low_ok and 0 < wt < _B_WLOW32:
                     out.append((name, "max |w| = %g is below 2^-8" % (_bits_to_float(wt) / 32.0)))
-            elif name.startswith("pointmlph3p"):
+            elif name.startswith("pointmlph3p") or name.startswith("upconv3x3"):
                 if wt > _B_2047:
                     out.append((name, "max |w| = %g exceeds 2047" % _bits_to_float(wt)))
                 elif low_ok and 0 < wt < _B_WLOW:
@@ -2522,6 +2523,68 @@ def chamfer_loss(pred, gt):
     differentiable).  The sums are float64 on the device and rounded once; the backward is one ``sonet_chamfer_grad_f32`` call."""
     _chk_clouds(pred, gt)
     return _ChamferLoss.apply(pred, gt)
+
+
+# ------------------------------------------------------------------------------------------ upconv3x3
+# Tile extents of csrc/upconv.hip (include/sonet_hip.h SONET_UPCONV_*): a workgroup covers UPCONV_TILE_PIXELS consecutive low-resolution
+# pixels of the flattened (b, i, j) axis and UPCONV_COUT_BLOCK output channels, and stages UPCONV_K_CHUNK input channels at a time.
+UPCONV_TILE_PIXELS = 128
+UPCONV_K_CHUNK = 16
+UPCONV_COUT_BLOCK = 32
+UPCONV_MAX_HW = 64
+
+
+def upconv3x3_supported(Cin, Cout, H, W):
+    """Shapes the fused up-convolution takes: any Cin >= 1, Cout a multiple of UPCONV_COUT_BLOCK, 1 <= H, W <= UPCONV_MAX_HW."""
+    return Cin >= 1 and Cout >= UPCONV_COUT_BLOCK and Cout % UPCONV_COUT_BLOCK == 0 and 1 <= H <= UPCONV_MAX_HW and 1 <= W <= UPCONV_MAX_HW
+
+
+def upconv3x3_pack(weight4d):
+    """[Cout][Cin][3][3] f32 -> the up-convolution's pack (int32 tensor): the sixteen (parity, tap) 2x2 weights folded in float64, split
+    into fp16(32 w) + residual, in MFMA A-fragment order; its trailer carries the largest magnitude for the range guard."""
+    _chk(weight4d, "weight", torch.float32, 4)
+    Cout, Cin, kh, kw = weight4d.shape
+    if (kh, kw) != (3, 3):
+        raise SonetHipError("upconv3x3_pack: a 3x3 kernel, got %dx%d" % (kh, kw))
+    if not upconv3x3_supported(Cin, Cout, 1, 1):
+        raise SonetHipError("upconv3x3_pack: Cout = %d is not a multiple of %d" % (Cout, UPCONV_COUT_BLOCK))
+    dev = _same_device(weight4d)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        wp = torch.empty((lib.sonet_upconv3x3_pack_size(Cin, Cout) // 4,), dtype=torch.int32, device=dev)
+        check(lib.sonet_upconv3x3_pack_f32(ptr(weight4d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_upconv3x3_pack_f32")
+    return wp
+
+
+def upconv3x3(x, wp, scale, shift, relu, Cout):
+    """y = act(conv3x3_pad1(upsample2_nearest(x), w) * scale + shift) in one launch (models/layers.py:214-240, inference):
+    x B x Cin x H x W f32 -> B x Cout x 2H x 2W f32; wp from ``upconv3x3_pack``; scale / shift per output channel (bias and eval-mode
+    BatchNorm folded in).  fp16-split arithmetic: inside a ``range_scope`` the launch logs max |x| and the pack's max |w|."""
+    _chk(x, "x", torch.float32, 4)
+    B, Cin, H, W = x.shape
+    Cout = int(Cout)
+    if B < 1 or not upconv3x3_supported(Cin, Cout, H, W):
+        raise SonetHipError("upconv3x3: unsupported shape B=%d Cin=%d Cout=%d H=%d W=%d (Cout %% %d == 0, 1 <= H, W <= %d)"
+                            % (B, Cin, Cout, H, W, UPCONV_COUT_BLOCK, UPCONV_MAX_HW))
+    if not isinstance(wp, torch.Tensor) or wp.dtype != torch.int32:
+        raise SonetHipError("upconv3x3: an up-convolution pack (ops.upconv3x3_pack)")
+    _chk(wp, "wp", torch.int32, 1)
+    _chk_cvec(Cout, scale=scale, shift=shift)
+    dev = _same_device(x, wp, scale, shift)
+    lib = _lib.load()
+    if wp.numel() * 4 != lib.sonet_upconv3x3_pack_size(Cin, Cout):
+        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
+                            % (wp.numel() * 4, lib.sonet_upconv3x3_pack_size(Cin, Cout), Cin, Cout))
+    y = torch.empty((B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=dev)
+    name = "upconv3x3_%dx%d_%dx%d" % (Cin, Cout, H, W)
+    slot = None
+    if _range_active is not None:
+        import ctypes
+        slot = ctypes.c_void_p(_range_active._slot(name))
+    with _lib.on_device(dev), _timed(name):
+        check(lib.sonet_upconv3x3_f32(ptr(x), ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cin, Cout, H, W, slot,
+                                      stream_ptr()), "sonet_upconv3x3_f32")
+    return y
 
 
 # ------------------------------------------------------------------------------------------ segmentation metrics
