@@ -588,7 +588,7 @@ int sonet_pointmlp_bf16_pool(const uint16_t *x1, int C1, const uint16_t *x2, int
                              int32_t *out_idx, float *out_val, int B, int Cout, int L, int M, sonet_stream_t stream);
 /* Normalise-on-load (bf16 training forward, round 6): x1 / x2 hold the RAW (bf16) outputs of training-mode BatchNorm layers
  * (models/layers.py:60-70, :282-296) whose normalise + ReLU pass was never run.  The operand load computes act(raw * xs[c] + xh[c]) in f32 and
- * rounds to bf16 -- exactly what sonet_channel_affine_act_bf16 would have stored -- so the results equal the plain entry points on the
+ * rounds to bf16 -- exactly what sonet_channel_affine_act_out_bf16 would have stored -- so the results equal the plain entry points on the
  * normalised tensors bit for bit.  xs1, xh1 [C1] (xs2, xh2 [C2] when C2 > 0); xrelu bit 0 / 1: ReLU on x1 / x2.  Streaming-kernel shapes only
  * ((C1 + C2) % 64 == 0, even L, 4-byte aligned rows; the statistics form: >= 8192 column groups): SONET_ERR_UNSUPPORTED otherwise. */
 int sonet_pointmlp_bf16_stats_xaff(const uint16_t *x1, int C1, const uint16_t *x2, int C2, const void *Wp,
@@ -646,7 +646,7 @@ int sonet_wgrad_x3_xaff_f32(const float *g, const float *x, float *dw, void *ws,
 size_t sonet_wgrad_bf16_ws_size(int B, int Cout, int Cin, int L);
 int sonet_wgrad_bf16(const uint16_t *g, const uint16_t *x, float *dw, void *ws, int B, int Cout, int Cin, int L, sonet_stream_t stream);
 /* ... when x is the RAW (bf16) output of a BatchNorm layer whose normalise pass was never run (bf16 training, normalise-on-load): the x
- * fragments go through act(raw * xs[c] + xh[c]) rounded to bf16, bit for bit what sonet_channel_affine_act_bf16 would have stored; xs, xh
+ * fragments go through act(raw * xs[c] + xh[c]) rounded to bf16, bit for bit what sonet_channel_affine_act_out_bf16 would have stored; xs, xh
  * [Cin].  Streaming-kernel shapes only (L % 8 == 0, B * ceil(L / 64) >= 2048): SONET_ERR_UNSUPPORTED otherwise. */
 int sonet_wgrad_bf16_xaff(const uint16_t *g, const uint16_t *x, float *dw, void *ws, int B, int Cout, int Cin, int L,
                           const float *xs, const float *xh, int xrelu, sonet_stream_t stream);

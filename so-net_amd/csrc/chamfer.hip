@@ -14,7 +14,6 @@ constexpr int CH_TILE = 1024;
 // Two database points per step in packed f32 (v_pk_add_f32 / v_pk_mul_f32: each lane of a pair is an IEEE single operation, so the
 // distances are the bits of the scalar form): the tile holds PAIRS -- (x0, x1, y0, y1) and (z0, z1) -- and the 8 arithmetic operations of a
 // pair cost 8 instructions instead of 16; the two compare / select steps stay scalar and in order (ascending j, strict '<').
-typedef float ch_f2 __attribute__((ext_vector_type(2)));
 
 // The search loop, one copy for both kernels: the database cloud dbb [3][Nd] goes through the two LDS arrays in tiles of CH_TILE
 // points; every thread of the workgroup must call it (barriers inside), a thread without a query passes any finite point.
@@ -23,7 +22,7 @@ typedef float ch_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ int chamfer_search(const float *__restrict__ dbb, int Nd, float px, float py, float pz,
                                               float4 *__restrict__ txy, float2 *__restrict__ tz)
 {
-    const ch_f2 PX = {px, px}, PY = {py, py}, PZ = {pz, pz};
+    const f32x2_t PX = {px, px}, PY = {py, py}, PZ = {pz, pz};
     float best = __builtin_inff();
     int bi = 0;
     for (int t0 = 0; t0 < Nd; t0 += CH_TILE) {
@@ -43,9 +42,9 @@ __device__ __forceinline__ int chamfer_search(const float *__restrict__ dbb, int
         for (int t = 0; t < npair; ++t) {
             const float4 a = txy[t];
             const float2 c = tz[t];
-            const ch_f2 X = {a.x, a.y}, Y = {a.z, a.w}, Z = {c.x, c.y};
-            const ch_f2 dx = PX - X, dy = PY - Y, dz = PZ - Z;
-            const ch_f2 d = (dx * dx + dy * dy) + dz * dz;         // (-ffp-contract=off: no fused multiply-add)
+            const f32x2_t X = {a.x, a.y}, Y = {a.z, a.w}, Z = {c.x, c.y};
+            const f32x2_t dx = PX - X, dy = PY - Y, dz = PZ - Z;
+            const f32x2_t d = (dx * dx + dy * dy) + dz * dz;         // (-ffp-contract=off: no fused multiply-add)
             const bool lt0 = d[0] < best;
             best = lt0 ? d[0] : best;
             bi = lt0 ? t0 + 2 * t : bi;

@@ -1,4 +1,4 @@
-// common.hpp -- shared host-side helpers of libsonet_hip.so (gfx950 only).
+// common.hpp -- shared host-side helpers of libsonet_hip.so (gfx950 only); the device-side ones are in device.hpp, included at the end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,66 +69,21 @@ struct BnRider {
 };
 BnRider take_bn_rider();
 
+// Launch of a kernel whose dynamic LDS exceeds the 64 KB a kernel gets unasked: the limit is raised to MAX_LDS bytes ONCE per
+// kernel instantiation and process -- the initialiser of a function-local static, so concurrent first calls (autograd's worker
+// threads) are serialised by the language -- and never on a later launch: a runtime call per launch is not free on a host-bound step.
+template <auto KERNEL, int MAX_LDS, typename... Args>
+static inline int launch_lds_once(const char *what, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static const bool allowed =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS) == hipSuccess;
+    if (!allowed) return fail(SONET_ERR_UNSUPPORTED, "%s: cannot reserve the LDS", what);
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+    return SONET_OK;
+}
+
 }  // namespace sonet
-
-// sum over the 32 lanes of a half wave, result in every lane (all lanes must be active): xor-1, xor-2 inside a quad, mirror inside
-// 8 and 16 lanes (DPP modifiers of the add), then the other row of 16 through ds_swizzle (no LDS memory is touched)
-__device__ __forceinline__ float row32_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));                     // lane ^ 16
-    return v;
-}
-
-
-// Bijective XCD-aware remap of a 1-D block id: consecutive *virtual* ids land on the same XCD
-// (and so share its L2).  Pure speed choice -- correctness never depends on placement.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg / sonet::NUM_XCD, r = nwg % sonet::NUM_XCD;
-    const int xcd = bid % sonet::NUM_XCD, local = bid / sonet::NUM_XCD;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
-
-// ---- operand-range tracking of the fp16-split kernels (two integer max per value pair) ---------------------------
-// |x| as ordered bits over everything a lane has seen: positive floats order as signed ints (mp), negative ones --
-// sign bit set -- order by magnitude as unsigned ints (mn); a NaN of either sign lands above +-inf in one of the two.
-struct RangeAcc { int mp; unsigned mn; };
-__device__ __forceinline__ void range_track(RangeAcc &r, float x0, float x1) {
-    const int a = __float_as_int(x0), b = __float_as_int(x1);
-    r.mp = max(max(r.mp, a), b);                                           // v_max3_i32
-    r.mn = max(max(r.mn, (unsigned)a), (unsigned)b);                       // v_max3_u32
-}
-__device__ __forceinline__ unsigned range_amax_bits(const RangeAcc &r) {   // bits of max |x| (NaN > inf > finite)
-    const unsigned neg = (r.mn & 0x80000000u) ? (r.mn & 0x7FFFFFFFu) : 0u;
-    const unsigned pos = (unsigned)r.mp;
-    return pos > neg ? pos : neg;
-}
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-// one atomic per wave at most, and only while the wave's value still raises the word
-__device__ __forceinline__ void range_publish(unsigned *word, unsigned wave_max_bits, int lane) {
-    if (lane == 0 && wave_max_bits > __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMax(word, wave_max_bits);
-}
-
-// ---- P16 planes (include/sonet_hip.h): a value pair clamped to the fp16-split range, scaled by 32, as packed fp16 hi + packed fp16 residual
-// (the residual is exact in f32 before it is rounded) -- the arithmetic of split_act in pointmlp_h3p.hip, for the producers outside it
-__device__ __forceinline__ void p16_split_pair(float x0, float x1, unsigned &h, unsigned &m) {
-    typedef _Float16 sonet_h2_t __attribute__((ext_vector_type(2)));
-    typedef float sonet_f2_t __attribute__((ext_vector_type(2)));
-    const sonet_f2_t X = {32.f * __builtin_amdgcn_fmed3f(x0, -2047.f, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, -2047.f, 2047.f)};
-    const sonet_h2_t hv = __builtin_convertvector(X, sonet_h2_t);
-    const sonet_f2_t R = {X[0] - (float)hv[0], X[1] - (float)hv[1]};
-    h = __builtin_bit_cast(unsigned, hv);
-    m = __builtin_bit_cast(unsigned, __builtin_convertvector(R, sonet_h2_t));
-}
-// cluster mean of the SOM stage (models/networks.py:142): sum / (count + 1e-5), every step rounded to f32 (no reciprocal, no FMA)
-__device__ __forceinline__ float cluster_mean(float sum, float count) { return __fdiv_rn(sum, __fadd_rn(count, 1e-5f)); }
 
 // groups (nodes) per 128-column block of the K-level tensor of the flat node-level stage (node_stage.hip): as many as fit, at most 16
 static inline int knn_stage_groups(int K) { const int g = 128 / K; return g > 16 ? 16 : g; }
+
+#include "device.hpp"                   // the device-side building blocks of the kernels

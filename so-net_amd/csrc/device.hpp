@@ -1,0 +1,156 @@
+// device.hpp -- the device-side building blocks shared by the kernels of libsonet_hip.so (gfx950 only): one copy of each.
+// Included through common.hpp.  Everything here is __device__ __forceinline__ in the global namespace; a kernel file keeps only
+// what is its own (its pipeline, its tile constants, helpers whose arithmetic differs from the ones here as written).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+// ---- vector types (register shapes of the MFMA operands, packed pairs, buffer descriptors) ------------------------
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+// compile-time values handed to generic lambdas (dispatch of a runtime choice to a template instantiation)
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+
+// ---- conversions and keys -----------------------------------------------------------------------------------------
+// Two f32 -> one dword of two bf16 (lo | hi << 16), round to nearest even, NaN stays NaN: one v_cvt_pk_bf16_f32.  As an asm
+// statement so that it IS this one instruction, whatever the compiler's own f32 -> __bf16 lowering does: the split and epilogue
+// instruction counts of the layer kernels are budgeted for it.  Not volatile: it is pure and may be scheduled or removed.
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+// Two f32 -> one dword of two fp16, round to nearest even: the vector conversion is selected as one v_cvt_pk_f16_f32.
+__device__ __forceinline__ unsigned cvt_pk_f16(float lo, float hi) {
+    const f32x2_t v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
+}
+// Orderable key of a float's bits: unsigned compare == float compare (a total order), so an integer atomicMax finds a maximum
+// deterministically.  -0 counts as +0 (the reference's torch.max does not tell them apart); a NaN maps to 0, the smallest key: it
+// never wins (a NaN must not beat the reference's initial running maximum of -1000).
+__device__ __forceinline__ unsigned ord_f32(unsigned bits) {
+    if (bits == 0x80000000u) bits = 0u;
+    const unsigned o = bits ^ ((unsigned)((int)bits >> 31) | 0x80000000u);
+    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? 0u : o;
+}
+
+// ---- raw buffer descriptors ------------------------------------------------------------------------------------
+// `bytes` of memory at `ptr` as a raw buffer (stride 0, offsets in bytes): a load past `bytes` returns 0 and a store past it is
+// dropped, which is how the layer kernels handle their edges.  Word 3 is DATA_FORMAT 32 (bits 12..18) with every other field
+// zero: no swizzle, no index/offset striding, OOB_SELECT 0 (raw: the byte offset is checked against NUM_RECORDS) -- the value the
+// compiler's own raw buffer accesses use on gfx9.  raw_buffer is for the __builtin_amdgcn_raw_buffer_* builtins (the descriptor
+// type they take, so hipcc sees the accesses as memory operations and counts them); raw_buffer_sgpr is the same four words made
+// wave-uniform by hand, for the "s" operand of a buffer instruction written as inline asm.
+constexpr int RAW_BUFFER_WORD3 = 0x00020000;
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_buffer(const T *ptr, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(ptr), 0, bytes, RAW_BUFFER_WORD3);
+}
+__device__ __forceinline__ i32x4_t raw_buffer_sgpr(const void *base, unsigned bytes) {
+    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+    i32x4_t r;
+    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
+    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xFFFFu));      // stride 0: raw buffer
+    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
+    r[3] = RAW_BUFFER_WORD3;
+    return r;
+}
+
+// ---- f32 / bf16 storage by overload (uint16_t = bfloat16 bits): values widened on the load, arithmetic in f32 ----------------------
+__device__ __forceinline__ float ld_f32(const float *p, long long i) { return p[i]; }
+__device__ __forceinline__ float ld_f32(const uint16_t *p, long long i) { return __uint_as_float((unsigned)p[i] << 16); }
+// ... and ONE rounding on the store: round to nearest even
+__device__ __forceinline__ void st_rne(float *p, long long i, float v) { p[i] = v; }
+__device__ __forceinline__ void st_rne(uint16_t *p, long long i, float v) { p[i] = (uint16_t)(cvt_pk_bf16(v, v) & 0xFFFFu); }
+// four consecutive values (o 16 / 8 byte aligned)
+__device__ __forceinline__ void st4_rne(float *o, const float (&v)[4]) { *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void st4_rne(uint16_t *o, const float (&v)[4]) {
+    *reinterpret_cast<uint2 *>(o) = make_uint2(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]));
+}
+
+// ---- bf16 normalise-on-load: a packed bf16 pair through act(raw * s + h) ---------------------------------------------
+// f32 fma, one round-to-nearest-even back to bf16, ReLU -- sonet_channel_affine_act_out_bf16's arithmetic per element (there: ReLU in
+// f32 in front of the rounding; rounding is monotone and keeps the sign, so the order does not matter.  A -0.0 comes out as +0.0
+// here: as an operand of the product that is the same number).  Five vector instructions: two unpacks, v_pk_fma_f32,
+// v_cvt_pk_bf16_f32, v_pk_max_i16 against `floor2` (0 with ReLU, the most negative i16 in both halves -- the identity -- without).
+// NaN: the integer maximum after the rounding turns a NaN with the sign bit set into 0 and keeps one with the sign bit clear, where
+// the f32 `v < 0 ? 0 : v` keeps both: "bit for bit" holds for non-NaN data.
+__device__ __forceinline__ unsigned bf16_pair_affine_act(unsigned pk, f32x2_t sc, f32x2_t sh, unsigned floor2) {
+    const f32x2_t x = {__uint_as_float(pk << 16), __uint_as_float(pk & 0xFFFF0000u)};
+    f32x2_t v;
+    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(v) : "v"(x), "v"(sc), "v"(sh));
+    unsigned r = cvt_pk_bf16(v[0], v[1]);
+    asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(r), "v"(floor2));
+    return r;
+}
+
+// sum over the 32 lanes of a half wave, result in every lane (all lanes must be active): xor-1, xor-2 inside a quad, mirror inside
+// 8 and 16 lanes (DPP modifiers of the add), then the other row of 16 through ds_swizzle (no LDS memory is touched)
+__device__ __forceinline__ float row32_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));                     // lane ^ 16
+    return v;
+}
+
+// Bijective XCD-aware remap of a 1-D block id: consecutive *virtual* ids land on the same XCD
+// (and so share its L2).  Pure speed choice -- correctness never depends on placement.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg / sonet::NUM_XCD, r = nwg % sonet::NUM_XCD;
+    const int xcd = bid % sonet::NUM_XCD, local = bid / sonet::NUM_XCD;
+    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    return base + local;
+}
+
+// ---- operand-range tracking of the fp16-split kernels (two integer max per value pair) ---------------------------
+// |x| as ordered bits over everything a lane has seen: positive floats order as signed ints (mp), negative ones --
+// sign bit set -- order by magnitude as unsigned ints (mn); a NaN of either sign lands above +-inf in one of the two.
+struct RangeAcc { int mp; unsigned mn; };
+__device__ __forceinline__ void range_track(RangeAcc &r, float x0, float x1) {
+    const int a = __float_as_int(x0), b = __float_as_int(x1);
+    r.mp = max(max(r.mp, a), b);                                           // v_max3_i32
+    r.mn = max(max(r.mn, (unsigned)a), (unsigned)b);                       // v_max3_u32
+}
+__device__ __forceinline__ unsigned range_amax_bits(const RangeAcc &r) {   // bits of max |x| (NaN > inf > finite)
+    const unsigned neg = (r.mn & 0x80000000u) ? (r.mn & 0x7FFFFFFFu) : 0u;
+    const unsigned pos = (unsigned)r.mp;
+    return pos > neg ? pos : neg;
+}
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
+    return v;
+}
+// one atomic per wave at most, and only while the wave's value still raises the word
+__device__ __forceinline__ void range_publish(unsigned *word, unsigned wave_max_bits, int lane) {
+    if (lane == 0 && wave_max_bits > __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMax(word, wave_max_bits);
+}
+
+// ---- P16 planes (include/sonet_hip.h): a value pair clamped to the fp16-split range, scaled by 32, as packed fp16 hi + packed fp16 residual
+// p16_split2: (X0, X1) already scaled by 32 and inside +-65504 -> packed hi, packed residual (exact in f32 before it is rounded)
+__device__ __forceinline__ void p16_split2(float X0, float X1, unsigned &h, unsigned &m) {
+    h = cvt_pk_f16(X0, X1);
+    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
+    m = cvt_pk_f16(X0 - (float)hv[0], X1 - (float)hv[1]);
+}
+// the clamp is one v_med3_f32: a NaN leaves as the lower bound, the minimum of the three
+__device__ __forceinline__ void p16_split_pair(float x0, float x1, unsigned &h, unsigned &m) {
+    p16_split2(32.f * __builtin_amdgcn_fmed3f(x0, -2047.f, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, -2047.f, 2047.f), h, m);
+}
+// channel of element e (0..7) of half h in a 16-channel chunk of a P16 plane
+__device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
+
+// cluster mean of the SOM stage (models/networks.py:142): sum / (count + 1e-5), every step rounded to f32 (no reciprocal, no FMA)
+__device__ __forceinline__ float cluster_mean(float sum, float count) { return __fdiv_rn(sum, __fadd_rn(count, 1e-5f)); }

@@ -20,9 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m) { p16_split_pair(x0, x1, h, m); }
-__device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
-
 constexpr int KS_CPW = 4;            // 16-channel chunks per workgroup of the input kernel
 
 // Per padded column of the K-level tensor: rec = (source column of the neighbour on the flat M-level axis, the three de-centred
@@ -70,8 +67,8 @@ __global__ __launch_bounds__(256) void knn_stage_prepare_kernel(const float *__r
 #pragma unroll
         for (int c = 0; c < 3; ++c) center[((long long)b * 3 + c) * M + m] = ctr[c];
         unsigned h0, m0, h1v, m1;
-        split_pair(ctr[0], ctr[1], h0, m0);
-        split_pair(ctr[2], 0.f, h1v, m1);
+        p16_split_pair(ctr[0], ctr[1], h0, m0);
+        p16_split_pair(ctr[2], 0.f, h1v, m1);
         center_p16[(0 * 2 + 0) * Lm + n] = make_uint4(h0, h1v, 0u, 0u);
         center_p16[(0 * 2 + 1) * Lm + n] = make_uint4(0u, 0u, 0u, 0u);
         center_p16[(1 * 2 + 0) * Lm + n] = make_uint4(m0, m1, 0u, 0u);
@@ -93,8 +90,6 @@ __global__ __launch_bounds__(256) void knn_stage_prepare_kernel(const float *__r
 // power of two rides in a coefficient: the planes hold 32 z and the split wants 32 h1, so the table keeps 32 w, scale, 32 shift --
 // a = 32 z + (32 w) . d is 32 x the reference's sum bit for bit, and (32 s)(a / 32) ... no: act(a * scale + 32 shift) = 32 h1 exactly
 // (powers of two commute with the rounding of an fma below overflow, and |32 h1| <= 65504 is the range the split clamps to anyway).
-typedef float ks_f2 __attribute__((ext_vector_type(2)));
-typedef _Float16 ks_h2 __attribute__((ext_vector_type(2)));
 
 constexpr int KS_MAXG = 8;           // chunk groups one workgroup walks at most (its coefficient table: 5 x 8 x 64 floats)
 
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(256) void knn_stage_input_kernel(const int4 *__rest
         coef[4][t] = in ? 32.f * shift[c] : 0.f;
     }
     const bool valid = r.x != -2, ok = r.x >= 0;
-    const ks_f2 d0 = {__int_as_float(r.y), __int_as_float(r.y)}, d1 = {__int_as_float(r.z), __int_as_float(r.z)},
+    const f32x2_t d0 = {__int_as_float(r.y), __int_as_float(r.y)}, d1 = {__int_as_float(r.z), __int_as_float(r.z)},
                 d2 = {__int_as_float(r.w), __int_as_float(r.w)};
     RangeAcc xr = {0, 0u};
     const float lo = relu ? 0.f : -65504.f;                              // ReLU and the lower clamp of the split are one v_med3_f32
@@ -165,24 +160,20 @@ __global__ __launch_bounds__(256) void knn_stage_input_kernel(const int4 *__rest
 #pragma unroll
             for (int q = 0; q < 4; ++q) {                                // elements 2 q, 2 q + 1: two consecutive channels
                 const int slot = (j * KS_CPW + i) * 16 + hh * 8 + 2 * q;
-                const ks_f2 w0 = *reinterpret_cast<const ks_f2 *>(&coef[0][slot]), w1 = *reinterpret_cast<const ks_f2 *>(&coef[1][slot]),
-                            w2 = *reinterpret_cast<const ks_f2 *>(&coef[2][slot]), sc = *reinterpret_cast<const ks_f2 *>(&coef[3][slot]),
-                            sh = *reinterpret_cast<const ks_f2 *>(&coef[4][slot]);
-                const ks_h2 zh2 = __builtin_bit_cast(ks_h2, zh[q]), zm2 = __builtin_bit_cast(ks_h2, zm[q]);
+                const f32x2_t w0 = *reinterpret_cast<const f32x2_t *>(&coef[0][slot]), w1 = *reinterpret_cast<const f32x2_t *>(&coef[1][slot]),
+                            w2 = *reinterpret_cast<const f32x2_t *>(&coef[2][slot]), sc = *reinterpret_cast<const f32x2_t *>(&coef[3][slot]),
+                            sh = *reinterpret_cast<const f32x2_t *>(&coef[4][slot]);
+                const f16x2_t zh2 = __builtin_bit_cast(f16x2_t, zh[q]), zm2 = __builtin_bit_cast(f16x2_t, zm[q]);
                 // 32 z = hi + residual (exact: two fp16 values whose exponents are at most 11 apart)
-                ks_f2 a = __builtin_convertvector(zh2, ks_f2) + __builtin_convertvector(zm2, ks_f2);
+                f32x2_t a = __builtin_convertvector(zh2, f32x2_t) + __builtin_convertvector(zm2, f32x2_t);
                 a = __builtin_elementwise_fma(w0, d0, a);                // (the reference's order: z, then the three coordinate channels)
                 a = __builtin_elementwise_fma(w1, d1, a);
                 a = __builtin_elementwise_fma(w2, d2, a);
                 a = __builtin_elementwise_fma(a, sc, sh);                // 32 x the pre-activation
-                if (!valid) a = ks_f2{0.f, 0.f};
+                if (!valid) a = f32x2_t{0.f, 0.f};
                 range_track(xr, a[0], a[1]);
                 // (a NaN leaves v_med3_f32 as the lower bound, as in split_act; the range log has seen it)
-                const ks_f2 X = {__builtin_amdgcn_fmed3f(a[0], lo, 65504.f), __builtin_amdgcn_fmed3f(a[1], lo, 65504.f)};
-                const ks_h2 hp = __builtin_convertvector(X, ks_h2);
-                const ks_f2 R = X - __builtin_convertvector(hp, ks_f2);
-                hv[q] = __builtin_bit_cast(unsigned, hp);
-                mv[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(R, ks_h2));
+                p16_split2(__builtin_amdgcn_fmed3f(a[0], lo, 65504.f), __builtin_amdgcn_fmed3f(a[1], lo, 65504.f), hv[q], mv[q]);
             }
 #ifdef SONET_VARIANTS
             if ((abl & 1) && hv[0] != 0x12345u) { hq += 4 * Lp; continue; }    // (ablation: no stores)
@@ -235,7 +226,6 @@ __global__ __launch_bounds__(256) void p16_flat_to_bcm_kernel(const uint4 *__res
     const int kc = blockIdx.y >> 1, hh = blockIdx.y & 1;
     if (l >= BM) return;
     const uint4 hv = p[((long long)(kc * 2 + 0) * 2 + hh) * Lm + l], mv = p[((long long)(kc * 2 + 1) * 2 + hh) * Lm + l];
-    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
     const f16x8 h8 = __builtin_bit_cast(f16x8, hv), m8 = __builtin_bit_cast(f16x8, mv);
     const long long b = l / M;
     const int m = (int)(l - b * M);

@@ -10,12 +10,9 @@
 
 namespace {
 
-__device__ __forceinline__ float ld(const float *p, long long i) { return p[i]; }
-__device__ __forceinline__ float ld(const uint16_t *p, long long i) { return __uint_as_float((unsigned)p[i] << 16); }
-__device__ __forceinline__ void st(float *p, long long i, float v) { p[i] = v; }
-__device__ __forceinline__ void st(uint16_t *p, long long i, float v) {           // v is a value that came from bf16 storage (or 0): exact
-    p[i] = (uint16_t)(__float_as_uint(v) >> 16);
-}
+// store of a value that came from storage of the same type (or 0): exact, so bf16 TRUNCATES -- not the rounding store st_rne (device.hpp)
+__device__ __forceinline__ void st_exact(float *p, long long i, float v) { p[i] = v; }
+__device__ __forceinline__ void st_exact(uint16_t *p, long long i, float v) { p[i] = (uint16_t)(__float_as_uint(v) >> 16); }
 
 // one thread per row of K contiguous values: value and index of the FIRST maximum; a NaN wins (the first one), as torch.max
 template <typename T>
@@ -24,13 +21,13 @@ __global__ __launch_bounds__(256) void lastdim_argmax_kernel(const T *__restrict
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
     const long long base = r * K;
-    float m = ld(x, base);
+    float m = ld_f32(x, base);
     int mi = 0;
     for (int k = 1; k < K; ++k) {
-        const float v = ld(x, base + k);
+        const float v = ld_f32(x, base + k);
         if (v > m || (v != v && m == m)) { m = v; mi = k; }
     }
-    st(out, r, m);
+    st_exact(out, r, m);
     idx[r] = mi;
 }
 
@@ -40,10 +37,10 @@ __global__ __launch_bounds__(256) void lastdim_max_bwd_kernel(const T *__restric
 {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
-    const float gv = ld(g, r);
+    const float gv = ld_f32(g, r);
     const int mi = idx[r];
     const long long base = r * K;
-    for (int k = 0; k < K; ++k) st(gx, base + k, k == mi ? gv : 0.f);
+    for (int k = 0; k < K; ++k) st_exact(gx, base + k, k == mi ? gv : 0.f);
 }
 
 // inverse neighbour lists of one cloud: off[b][m] .. off[b][m+1] index into list[b][.] = the entries e = m' * K + k (ascending) whose
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(256) void knn_gather_bwd_kernel(const T *__restrict
     const int32_t *L = list + (long long)b * M * K;
     const long long base = bc * (long long)M * K;
     float s = 0.f;
-    for (int i = o[m]; i < o[m + 1]; ++i) s += ld(g, base + L[i]);
+    for (int i = o[m]; i < o[m + 1]; ++i) s += ld_f32(g, base + L[i]);
     gx[t] = s;
 }
 
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(256) void node_gather_bwd_kernel(const T *__restric
     const int32_t *Lst = list + (long long)b * L;
     const long long base = bc * (long long)L;
     float s = 0.f;
-    for (int i = o[m]; i < o[m + 1]; ++i) s += ld(g, base + Lst[i]);
+    for (int i = o[m]; i < o[m + 1]; ++i) s += ld_f32(g, base + Lst[i]);
     gx[t] = s;
 }
 

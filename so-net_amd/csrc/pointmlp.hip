@@ -31,7 +31,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int PM_THREADS = 256;
 constexpr int PM_WAVES = PM_THREADS / 64;
@@ -368,7 +367,6 @@ __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_wlds_kernel(
 // of this wave's cloud, so rows past the panel (the zero-padded channels of a partial K-group, padded
 // groups of the last stage) read as 0 in hardware: no clamps, no selects, one loader for every stage.
 // Requires Cout % 32 == 0 and panels < 4 GiB per cloud (all layers of the path); other shapes use v2.
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 template <int MT, int S>
 __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_lean_kernel(
@@ -395,14 +393,10 @@ __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_lean_kernel(
     const int lc = (l0 + j < L) ? l0 + j : l0;               // clamped point (never stored when invalid)
 
     const unsigned rowB = (unsigned)L * 4u;                   // bytes per channel row
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x1 + b * (long long)C1 * L), 0, (int)((unsigned)C1 * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x2 ? x2 + b * (long long)C2 * L : x1), 0, (int)((unsigned)(x2 ? C2 : 0) * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        y + b * (long long)Cout * L, 0, (int)((unsigned)Cout * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(Wp), 0, (int)((unsigned)CT * (unsigned)G * 1024u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = raw_buffer(x1 + b * (long long)C1 * L, (int)((unsigned)C1 * rowB));
+    const __amdgpu_buffer_rsrc_t r2 = raw_buffer(x2 ? x2 + b * (long long)C2 * L : x1, (int)((unsigned)(x2 ? C2 : 0) * rowB));
+    const __amdgpu_buffer_rsrc_t ry = raw_buffer(y + b * (long long)Cout * L, (int)((unsigned)Cout * rowB));
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer(Wp, (int)((unsigned)CT * (unsigned)G * 1024u));
     const unsigned vox = (unsigned)(h * L + lc) * 4u;          // lane byte offset inside a channel-pair of rows
     const unsigned voy = (unsigned)(4 * h * L + lc) * 4u;      // ... inside an output row quad (D rows r and r+4)
     const unsigned vow = (unsigned)lane * 16u;

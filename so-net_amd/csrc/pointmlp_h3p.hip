@@ -41,37 +41,17 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int P_THREADS = 256;
 constexpr int P_KPAD = 8;                                     // the pack's K range is padded with zero chunks to a multiple of this (as the h3 pack)
 constexpr unsigned OOB = 0x7FFFFF00u;                          // a lane offset no descriptor covers: loads return 0, stores are dropped
 
-__device__ __forceinline__ unsigned pk_f16(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-}
-// (X0, X1) already scaled by 32 and inside +-65504 -> packed hi, packed mid (residual exact in f32, then rounded)
-__device__ __forceinline__ void split2(float X0, float X1, unsigned &h, unsigned &m) {
-    h = pk_f16(X0, X1);
-    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
-    m = pk_f16(X0 - (float)hv[0], X1 - (float)hv[1]);
-}
 // activation side: clamp to the fp16-split range (a NaN leaves as the lower bound, as in the second generation), scale, split.
 // RELU: the lower bound is 0 -- ReLU and clamp are one v_med3_f32.
 template <bool RELU>
 __device__ __forceinline__ void split_act(float x0, float x1, unsigned &h, unsigned &m) {
     constexpr float lo = RELU ? 0.f : -2047.f;
-    split2(32.f * __builtin_amdgcn_fmed3f(x0, lo, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, lo, 2047.f), h, m);
+    p16_split2(32.f * __builtin_amdgcn_fmed3f(x0, lo, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, lo, 2047.f), h, m);
 }
-
-// channel of element e (0..7) of half h in a 16-channel chunk
-__device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
 
 // ---- weight pack: Wp[ct][kcp][form][lane] (uint4 = 8 fp16):  row ct*32 + (lane & 31), K slots 8 (lane >> 5) .. +7 of chunk kcp in P16 channel
 // order; form 0 = fp16(32 w), form 1 = fp16(32 w - form 0); zero chunks from ceil(Cin/16) to KCP; 64-byte trailer: word 0 = bits of max |w|.
@@ -94,7 +74,7 @@ __global__ __launch_bounds__(256) void h3p_pack_kernel(const float *__restrict__
         range_track(wr, w0, w1);
         w0 = 32.f * __builtin_fminf(__builtin_fmaxf(w0, -2047.f), 2047.f);
         w1 = 32.f * __builtin_fminf(__builtin_fmaxf(w1, -2047.f), 2047.f);
-        split2(w0, w1, h[p], m[p]);
+        p16_split2(w0, w1, h[p], m[p]);
     }
     uint4 *dst = Wp + (r * 2) * 64 + lane;
     dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
@@ -201,24 +181,15 @@ struct H3pArgs {
     int GK, G, ngout, Lout;                // (Lout >= ngout: column count = plane stride of yp)
 };
 
-__device__ __forceinline__ i32x4_t make_rsrc(const void *base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    i32x4_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xFFFFu));      // stride 0: raw buffer
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-__device__ __forceinline__ u32x4 bload16(i32x4_t rsrc, unsigned voff, unsigned soff) {
-    u32x4 r;
+__device__ __forceinline__ u32x4_t bload16(i32x4_t rsrc, unsigned voff, unsigned soff) {
+    u32x4_t r;
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(r) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
     return r;
 }
 // Stores go through the compiler's builtins: nothing about a store needs hiding from hipcc (it never waits for one), and an inline-asm
 // buffer_store_dwordx4 needs wait states before its data registers may be rewritten that hipcc does not add behind an asm statement
 // (the first version of the transposed epilogue lost the last two values of a quad that way).
-__device__ __forceinline__ void bstore16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, u32x4 v) {
+__device__ __forceinline__ void bstore16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, u32x4_t v) {
     __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, soff, 0);
 }
 __device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float v) {
@@ -227,11 +198,11 @@ __device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t rsrc, unsigned vo
 // "at most N vector-memory operations of this wave are outstanding", then the workgroup barrier; the registers the wait is FOR are
 // in/out operands, so that every later use depends on this statement
 template <int N>
-__device__ __forceinline__ void wait_barrier(u32x4 &a, u32x4 &b) {
+__device__ __forceinline__ void wait_barrier(u32x4_t &a, u32x4_t &b) {
     asm volatile("s_waitcnt vmcnt(%2)\n\ts_barrier" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
 template <int N>
-__device__ __forceinline__ void wait_barrier(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d) {
+__device__ __forceinline__ void wait_barrier(u32x4_t &a, u32x4_t &b, u32x4_t &c, u32x4_t &d) {
     asm volatile("s_waitcnt vmcnt(%4)\n\ts_barrier" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
 }
 
@@ -279,7 +250,7 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
     constexpr int KWAIT = (PB - 1) * (NBL + ND);
     static_assert(KWAIT < 64, "vmcnt is a 6-bit counter");
     struct Lds {
-        u32x4 wsm[NSLOT][NSL][64];                            // W ring first: LDS-DMA addresses below 64 KiB
+        u32x4_t wsm[NSLOT][NSL][64];                            // W ring first: LDS-DMA addresses below 64 KiB
         // scale / 1024 and shift of the slab's rows (EPI 1: slabs of <= 16 tiles, the addend rows need the space) as [tile][h][scale, shift][16]:
         // the 16 rows of a tile a lane's registers hold (row (r & 3) + 8 (r >> 2) + 4 h in register r), contiguous, so that a tile's 32 values
         // are eight 16-byte reads at the top of the tile instead of 32 reads inside it
@@ -325,13 +296,15 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
         if (a.abl & 1) { voy[c] = OOB; voyp[c] = OOB; pv[c] = false; }
 #endif
     }
-    const i32x4_t r1 = make_rsrc(static_cast<const char *>(a.x1) + (size_t)b * a.KC1 * 64 * L1, (unsigned)a.KC1 * 64u * (unsigned)L1);
-    const i32x4_t r2 = make_rsrc(a.x2 ? static_cast<const char *>(a.x2) + (size_t)b * a.KC2 * 64 * L : static_cast<const char *>(a.x1),
+    const i32x4_t r1 = raw_buffer_sgpr(static_cast<const char *>(a.x1) + (size_t)b * a.KC1 * 64 * L1, (unsigned)a.KC1 * 64u * (unsigned)L1);
+    const i32x4_t r2 = raw_buffer_sgpr(a.x2 ? static_cast<const char *>(a.x2) + (size_t)b * a.KC2 * 64 * L : static_cast<const char *>(a.x1),
                                  a.x2 ? (unsigned)a.KC2 * 64u * (unsigned)L : 0u);
+    // (the builtin itself, not raw_buffer(): through the helper hipcc places the scalar selects of these two optional outputs elsewhere
+    // in the prologue -- 48 lines of 73,294 in nine instantiations -- and "instruction-identical to what was measured" is worth two lines)
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        a.y ? reinterpret_cast<char *>(a.y) + (size_t)b * a.Cout * L * 4 : nullptr, 0, a.y ? (int)((unsigned)a.Cout * (unsigned)L * 4u) : 0, 0x00020000);
+        a.y ? reinterpret_cast<char *>(a.y) + (size_t)b * a.Cout * L * 4 : nullptr, 0, a.y ? (int)((unsigned)a.Cout * (unsigned)L * 4u) : 0, RAW_BUFFER_WORD3);
     const __amdgpu_buffer_rsrc_t ryp = __builtin_amdgcn_make_buffer_rsrc(
-        a.yp ? static_cast<char *>(a.yp) + (size_t)b * (a.Cout / 16) * 64 * L : nullptr, 0, a.yp ? (int)((unsigned)(a.Cout / 16) * 64u * (unsigned)L) : 0, 0x00020000);
+        a.yp ? static_cast<char *>(a.yp) + (size_t)b * (a.Cout / 16) * 64 * L : nullptr, 0, a.yp ? (int)((unsigned)(a.Cout / 16) * 64u * (unsigned)L) : 0, RAW_BUFFER_WORD3);
 
     const int ct_begin = wg_slab * a.ct_per_y;
     const int ct_end = min(a.CT, ct_begin + a.ct_per_y);
@@ -345,7 +318,7 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
     const char *wp = static_cast<const char *>(a.Wp);
 
     // X chunk kc (of this wave's columns) -> registers: [c][form]
-    auto load_b = [&](u32x4 (&bb)[NBL], int kc) {
+    auto load_b = [&](u32x4_t (&bb)[NBL], int kc) {
 #ifdef SONET_VARIANTS
         if (a.abl & 2) kc = 0;
 #endif
@@ -380,14 +353,14 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
                          : "=&s"(keep) : "v"(vow), "s"(g), "s"(d) : "memory");
         }
     };
-    auto read_a = [&](u32x4 (&A)[4], int slot, int p) {        // tile pair p of the chunk in `slot`: [tile 2p: hi, mid][tile 2p+1: hi, mid]
+    auto read_a = [&](u32x4_t (&A)[4], int slot, int p) {        // tile pair p of the chunk in `slot`: [tile 2p: hi, mid][tile 2p+1: hi, mid]
 #pragma unroll
         for (int u = 0; u < 4; ++u) A[u] = lds.wsm[slot][4 * p + u][lane];
     };
 
     f32x16 acc[MT][NC];
 
-    auto mfma_pair = [&](const u32x4 (&A)[4], const u32x4 (&bb)[NBL], int p) {
+    auto mfma_pair = [&](const u32x4_t (&A)[4], const u32x4_t (&bb)[NBL], int p) {
         f16x8 Bh[NC], Bm[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -414,7 +387,7 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
     int zm[NC];
     bool zok[NC];
     unsigned zvo[NC], zla[NC];
-    const i32x4_t rz = make_rsrc(a.zadd ? a.zadd + (size_t)b * a.Cout * a.ZM : nullptr, a.zadd ? (unsigned)a.Cout * (unsigned)a.ZM * 4u : 0u);
+    const i32x4_t rz = raw_buffer_sgpr(a.zadd ? a.zadd + (size_t)b * a.Cout * a.ZM : nullptr, a.zadd ? (unsigned)a.Cout * (unsigned)a.ZM * 4u : 0u);
     if constexpr (EPI == 1 || EPI == 3) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -470,7 +443,7 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
                             range_track(yr, m0, m1);
                             unsigned hv, mv;
                             // (OUT == 2: the affine table made the values 32 x already, like the plain P16 epilogue)
-                            split2(__builtin_amdgcn_fmed3f(m0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(m1, split_lo * 32.f, 65504.f), hv, mv);
+                            p16_split2(__builtin_amdgcn_fmed3f(m0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(m1, split_lo * 32.f, 65504.f), hv, mv);
                             unsigned *dst = reinterpret_cast<unsigned *>(static_cast<char *>(a.yp)
                                 + ((((size_t)((ct0 + mt) * 2 + qq) * 2) * 2 + h2) * (size_t)a.Lout + (size_t)n_out) * 16) + p;
                             dst[0] = hv;
@@ -575,10 +548,10 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
                                 const float x0 = v[2 * p], x1 = v[2 * p + 1];
                                 range_track(yr, x0, x1);
                                 if constexpr (OUT == 2)             // (the values are 32 x already: see the affine table)
-                                    split2(__builtin_amdgcn_fmed3f(x0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(x1, split_lo * 32.f, 65504.f),
+                                    p16_split2(__builtin_amdgcn_fmed3f(x0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(x1, split_lo * 32.f, 65504.f),
                                            hh[2 * hf + p], mm[2 * hf + p]);
                                 else
-                                    split2(32.f * __builtin_amdgcn_fmed3f(x0, split_lo, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, split_lo, 2047.f),
+                                    p16_split2(32.f * __builtin_amdgcn_fmed3f(x0, split_lo, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, split_lo, 2047.f),
                                            hh[2 * hf + p], mm[2 * hf + p]);
                             }
                         }
@@ -587,7 +560,7 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
                     if constexpr ((OUT & 2) == 0) __builtin_amdgcn_sched_barrier(0);
                     if constexpr ((OUT & 2) != 0) {
                         const unsigned so = (unsigned)(((ct0 + mt) * 2 + qq) * 2) * (unsigned)L * 32u;
-                        const u32x4 hv = {hh[0], hh[1], hh[2], hh[3]}, mv = {mm[0], mm[1], mm[2], mm[3]};
+                        const u32x4_t hv = {hh[0], hh[1], hh[2], hh[3]}, mv = {mm[0], mm[1], mm[2], mm[3]};
                         bstore16(ryp, voyp[c], so, hv);
                         bstore16(ryp, voyp[c], so + (unsigned)L * 32u, mv);
                         __builtin_amdgcn_sched_barrier(0);
@@ -639,8 +612,8 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
     };
 
     // ---- the flat loop over (pass, chunk) -------------------------------------------------------------------------------------
-    u32x4 bq[NB][NBL];
-    u32x4 Aq[2][4];
+    u32x4_t bq[NB][NBL];
+    u32x4_t Aq[2][4];
     // prologue: the issue order of the steady state (DMA of a chunk BEFORE the X loads issued in the same body), so that the wait count
     // below means the same thing at chunk 0 as everywhere else
     // (KCr is a multiple of 4 >= D + 1, so chunks 0 .. D belong to pass 0)

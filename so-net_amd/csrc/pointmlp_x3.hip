@@ -31,21 +31,9 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int X3_THREADS = 256;
 constexpr int X3_WAVES = 4;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 
 // (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
@@ -58,27 +46,17 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, uns
 
 // fp16 flavour, B side: (x0, x1) -> 32 xh = fp16(32 x), fp16(32 x - 32 xh), xh = 32 xh * 2^-5 (packed pairs; exact residual)
 constexpr unsigned F16_2_M5_PK = 0x28002800u;
-__device__ __forceinline__ unsigned cvt_pk_f16(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-}
 __device__ __forceinline__ void split16_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
     x0 = 32.f * __builtin_fminf(__builtin_fmaxf(x0, -2047.f), 2047.f);
     x1 = 32.f * __builtin_fminf(__builtin_fmaxf(x1, -2047.f), 2047.f);
-    h = cvt_pk_f16(x0, x1);
-    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
-    m = cvt_pk_f16(x0 - (float)hv[0], x1 - (float)hv[1]);
-    l = __builtin_bit_cast(unsigned, hv * __builtin_bit_cast(f16x2_t, F16_2_M5_PK));
+    p16_split2(x0, x1, h, m);
+    l = __builtin_bit_cast(unsigned, __builtin_bit_cast(f16x2_t, h) * __builtin_bit_cast(f16x2_t, F16_2_M5_PK));
 }
 // the same values with the clamp written as one v_med3_f32 (what hipcc makes of fmin(fmax()) after a canonicalising v_max x, x:
 // a NaN input still leaves as -2047, the minimum of the three)
 __device__ __forceinline__ void split16_pair_med3(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-    x0 = 32.f * __builtin_amdgcn_fmed3f(x0, -2047.f, 2047.f);
-    x1 = 32.f * __builtin_amdgcn_fmed3f(x1, -2047.f, 2047.f);
-    h = cvt_pk_f16(x0, x1);
-    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
-    m = cvt_pk_f16(x0 - (float)hv[0], x1 - (float)hv[1]);
-    l = __builtin_bit_cast(unsigned, hv * __builtin_bit_cast(f16x2_t, F16_2_M5_PK));
+    p16_split_pair(x0, x1, h, m);
+    l = __builtin_bit_cast(unsigned, __builtin_bit_cast(f16x2_t, h) * __builtin_bit_cast(f16x2_t, F16_2_M5_PK));
 }
 // A side: (w0, w1) -> fp16(w), fp16(32 * (w - fp16(w)))
 __device__ __forceinline__ void split16_w(float w0, float w1, unsigned &h, unsigned &res) {
@@ -192,7 +170,7 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const PackEntry *__rest
             const int c = c0 + 2 * p;
             const float w0 = (o < e.rows && c < e.Cin) ? e.W[(long long)o * e.rs + (long long)c * e.cs] : 0.f;
             const float w1 = (o < e.rows && c + 1 < e.Cin) ? e.W[(long long)o * e.rs + (long long)(c + 1) * e.cs] : 0.f;
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w[p]) : "v"(w0), "v"(w1));
+            w[p] = cvt_pk_bf16(w0, w1);
         }
         reinterpret_cast<uint4 *>(e.Wp)[t] = make_uint4(w[0], w[1], w[2], w[3]);
     }
@@ -283,11 +261,6 @@ struct SegPoolArgs {
     int M;
 };
 constexpr unsigned long long SP_INIT_KEY = (0x3B85FFFFull << 32) | 0xFFFFFFFFull;   // ord(-1000.0f), column 0 (index_max.hip)
-__device__ __forceinline__ unsigned sp_ord_f32(unsigned bits) {   // total order; -0 == +0; NaN -> 0 (never wins)
-    if (bits == 0x80000000u) bits = 0u;
-    const unsigned o = bits ^ ((unsigned)((int)bits >> 31) | 0x80000000u);
-    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? 0u : o;
-}
 
 // XAFF (f32-class training forward): the inputs are the RAW outputs of BatchNorm layers whose normalise + ReLU pass was never run;
 // the operand load applies it -- x = act(raw * scale[c] + shift[c]) per input channel, the arithmetic of sonet_channel_affine_act_f32 bit
@@ -360,14 +333,10 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
     const int lc = (l0 + j < L) ? l0 + j : l0;
 
     const unsigned rowB = (unsigned)L * 4u, rowB1 = (unsigned)L1 * 4u;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x1 + b * (long long)C1 * L1), 0, (int)((unsigned)C1 * rowB1), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x2 ? x2 + b * (long long)C2 * L : x1), 0, (int)((unsigned)(x2 ? C2 : 0) * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        y + b * (long long)Cout * L, 0, (int)((unsigned)Cout * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint4 *>(Wp3), 0, (int)((unsigned)CT * (unsigned)KCP * (unsigned)(NTW * 1024)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = raw_buffer(x1 + b * (long long)C1 * L1, (int)((unsigned)C1 * rowB1));
+    const __amdgpu_buffer_rsrc_t r2 = raw_buffer(x2 ? x2 + b * (long long)C2 * L : x1, (int)((unsigned)(x2 ? C2 : 0) * rowB));
+    const __amdgpu_buffer_rsrc_t ry = raw_buffer(y + b * (long long)Cout * L, (int)((unsigned)Cout * rowB));
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer(Wp3, (int)((unsigned)CT * (unsigned)KCP * (unsigned)(NTW * 1024)));
     const unsigned vox = (unsigned)(8 * h * L + lc) * 4u;      // lane byte offset inside a 16-channel chunk
     // x1 through a gather index (the neighbour gather of KNNModule, models/layers.py:313-350, done by the operand load):
     // an index outside [0, L1) reads zeros (lane offset past the panel: the descriptor's bounds check)
@@ -388,10 +357,8 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
         sp_p0rel = wave_valid ? sp.pos0[b] - l0 : -1;
     }
 
-    const __amdgpu_buffer_rsrc_t rbn = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(BNB ? bnb.raw + b * (long long)C1 * L : x1), 0, (int)((unsigned)(BNB ? C1 : 0) * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rgo = __builtin_amdgcn_make_buffer_rsrc(
-        (BNB && bnb.g_out) ? bnb.g_out + b * (long long)C1 * L : y, 0, (int)((unsigned)((BNB && bnb.g_out) ? C1 : 0) * rowB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rbn = raw_buffer(BNB ? bnb.raw + b * (long long)C1 * L : x1, (int)((unsigned)(BNB ? C1 : 0) * rowB));
+    const __amdgpu_buffer_rsrc_t rgo = raw_buffer((BNB && bnb.g_out) ? bnb.g_out + b * (long long)C1 * L : y, (int)((unsigned)((BNB && bnb.g_out) ? C1 : 0) * rowB));
     auto load_b = [&](float (&raw)[S][BW], int st) {
 #pragma unroll
         for (int i = 0; i < S; ++i) {
@@ -632,7 +599,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                     const int po = __shfl_xor(p, 32, 64);
                     if (mo > m || (mo == m && po < p)) { m = mo; p = po; }
                     if (h == 0 && m > -__builtin_inff()) {
-                        const unsigned long long key = ((unsigned long long)sp_ord_f32(__float_as_uint(m)) << 32) |
+                        const unsigned long long key = ((unsigned long long)ord_f32(__float_as_uint(m)) << 32) |
                                                        (unsigned long long)(0xFFFFFFFFu - (unsigned)(l0 + p));
                         atomicMax(sp.keys + ((size_t)b * Cout + (ct0 + mt) * 32 + j) * sp.M + node, key);
                     }
@@ -643,8 +610,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
         } else if (BNB && bnb.pstats != nullptr) {
             // the output is gy of the layer below: its BatchNorm-backward sums from here (same reduction as the forward statistics below)
             const unsigned voy_s = pv ? voy : 0x7FFFFF00u;
-            const __amdgpu_buffer_rsrc_t rpr = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float *>(bnb.praw + b * (long long)Cout * L), 0, (int)((unsigned)Cout * rowB), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rpr = raw_buffer(bnb.praw + b * (long long)Cout * L, (int)((unsigned)Cout * rowB));
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const unsigned so_tile = (unsigned)((ct0 + mt) * 32) * rowB;
@@ -735,7 +701,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
             __amdgpu_buffer_rsrc_t rya = ry;
             if constexpr (BNB) {
                 addy = bnb.yadd != nullptr;
-                if (addy) rya = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(bnb.yadd + b * (long long)Cout * L), 0, (int)((unsigned)Cout * rowB), 0x00020000);
+                if (addy) rya = raw_buffer(bnb.yadd + b * (long long)Cout * L, (int)((unsigned)Cout * rowB));
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
@@ -834,12 +800,9 @@ __global__ __launch_bounds__(X3_THREADS, NC == 1 ? 2 : 1) void pointmlp_h3r_kern
     const int lc = (l0 + NC * j < L) ? l0 + NC * j : l0;        // the lane's first column
 
     const unsigned rowB = (unsigned)L * 4u, rowB1 = (unsigned)L1 * 4u;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x1 + b * (long long)C1 * L1), 0, (int)((unsigned)C1 * rowB1), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(x2 ? x2 + b * (long long)C2 * L : x1), 0, (int)((unsigned)(x2 ? C2 : 0) * rowB), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        y + b * (long long)Cout * L, 0, (int)((unsigned)Cout * rowB), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = raw_buffer(x1 + b * (long long)C1 * L1, (int)((unsigned)C1 * rowB1));
+    const __amdgpu_buffer_rsrc_t r2 = raw_buffer(x2 ? x2 + b * (long long)C2 * L : x1, (int)((unsigned)(x2 ? C2 : 0) * rowB));
+    const __amdgpu_buffer_rsrc_t ry = raw_buffer(y + b * (long long)Cout * L, (int)((unsigned)Cout * rowB));
     const unsigned vox = (unsigned)(8 * h * L + lc) * 4u;
     unsigned vox1 = vox;
     if constexpr (NC == 1) {

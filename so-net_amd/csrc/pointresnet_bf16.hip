@@ -29,9 +29,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int FB_THREADS = 256, FB_WAVES = 4;
 constexpr int G0_SL = 20, L3G_SL = 32, L4G_SL = 60;            // slices per group
@@ -42,17 +39,9 @@ constexpr int BUF_SL = 60;
 constexpr int CH_TOTAL_BF = 64 + 128 + 256 + 384;
 constexpr int AFF_L1 = 0, AFF_L2 = 64, AFF_L3 = 192, AFF_L4 = 448;
 
-template <int N> struct IC { static constexpr int value = N; };
-typedef short i16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned fb_relu_pk(unsigned pk) {
     const i16x2 v = __builtin_bit_cast(i16x2, pk), z = {0, 0};
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, z));
-}
-
-__device__ __forceinline__ unsigned fb_cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
 }
 
 // slice s of the stream -> (layer, cout tile, K chunk); one thread per (slice, lane).  "chained" layers take their input
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(256) void pointresnet_bf16_pack_kernel(const float 
                 const int c = chained ? kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * h : kc * 16 + 8 * h + e;
                 v[z] = c < Cin ? W[(long long)(ct * 32 + i) * Cin + c] : 0.f;
             }
-            w[p] = fb_cvt_pk_bf16(v[0], v[1]);
+            w[p] = cvt_pk_bf16(v[0], v[1]);
         }
     }
     out[(long long)s * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -98,7 +87,7 @@ __global__ __launch_bounds__(256) void pointresnet_bf16_pack_kernel(const float 
 // ---- one pass: MTn cout tiles x KCn K chunks out of an LDS buffer, optionally staging the next group -----------------
 // lds_cur: &buffer[first slice of the pass][lane]; slice (kc, mt) at (kc * MTn + mt) * 64.
 // Staging (STAGE): this wave moves NSTG_W slices of the next group (stream slices idx * 4 + wave), PER per K chunk:
-// buffer_load at chunk kc, ds_write at chunk kc + 2.  bfrag(IC<kc>, Ba, Bb) supplies the two B fragments of chunk kc.
+// buffer_load at chunk kc, ds_write at chunk kc + 2.  bfrag(int_c<kc>, Ba, Bb) supplies the two B fragments of chunk kc.
 // SWAP: X as the A operand and W as B (the per-lane register contents of both are the same either way): the accumulator
 // tile comes out transposed, rows = points, columns = channels -- what the per-node max-pool epilogue wants.
 template <int KCn, int MTn, int PER, int NSTG_W, bool STAGE, bool SWAP = false, typename BF>
@@ -132,26 +121,26 @@ __device__ __forceinline__ void mfma_pass(f32x16 (&acc)[MTn][2], const uint4 *ld
         }
         __builtin_amdgcn_sched_barrier(0);
         bf16x8 Ba, Bb;
-        if (kc == 0) bfrag(IC<0>{}, Ba, Bb);
-        else if (kc == 1) bfrag(IC<(KCn > 1 ? 1 : 0)>{}, Ba, Bb);
-        else if (kc == 2) bfrag(IC<(KCn > 2 ? 2 : 0)>{}, Ba, Bb);
-        else if (kc == 3) bfrag(IC<(KCn > 3 ? 3 : 0)>{}, Ba, Bb);
-        else if (kc == 4) bfrag(IC<(KCn > 4 ? 4 : 0)>{}, Ba, Bb);
-        else if (kc == 5) bfrag(IC<(KCn > 5 ? 5 : 0)>{}, Ba, Bb);
-        else if (kc == 6) bfrag(IC<(KCn > 6 ? 6 : 0)>{}, Ba, Bb);
-        else if (kc == 7) bfrag(IC<(KCn > 7 ? 7 : 0)>{}, Ba, Bb);
-        else if (kc == 8) bfrag(IC<(KCn > 8 ? 8 : 0)>{}, Ba, Bb);
-        else if (kc == 9) bfrag(IC<(KCn > 9 ? 9 : 0)>{}, Ba, Bb);
-        else if (kc == 10) bfrag(IC<(KCn > 10 ? 10 : 0)>{}, Ba, Bb);
-        else if (kc == 11) bfrag(IC<(KCn > 11 ? 11 : 0)>{}, Ba, Bb);
-        else if (kc == 12) bfrag(IC<(KCn > 12 ? 12 : 0)>{}, Ba, Bb);
-        else if (kc == 13) bfrag(IC<(KCn > 13 ? 13 : 0)>{}, Ba, Bb);
-        else if (kc == 14) bfrag(IC<(KCn > 14 ? 14 : 0)>{}, Ba, Bb);
-        else if (kc == 15) bfrag(IC<(KCn > 15 ? 15 : 0)>{}, Ba, Bb);
-        else if (kc == 16) bfrag(IC<(KCn > 16 ? 16 : 0)>{}, Ba, Bb);
-        else if (kc == 17) bfrag(IC<(KCn > 17 ? 17 : 0)>{}, Ba, Bb);
-        else if (kc == 18) bfrag(IC<(KCn > 18 ? 18 : 0)>{}, Ba, Bb);
-        else bfrag(IC<(KCn > 19 ? 19 : 0)>{}, Ba, Bb);
+        if (kc == 0) bfrag(int_c<0>{}, Ba, Bb);
+        else if (kc == 1) bfrag(int_c<(KCn > 1 ? 1 : 0)>{}, Ba, Bb);
+        else if (kc == 2) bfrag(int_c<(KCn > 2 ? 2 : 0)>{}, Ba, Bb);
+        else if (kc == 3) bfrag(int_c<(KCn > 3 ? 3 : 0)>{}, Ba, Bb);
+        else if (kc == 4) bfrag(int_c<(KCn > 4 ? 4 : 0)>{}, Ba, Bb);
+        else if (kc == 5) bfrag(int_c<(KCn > 5 ? 5 : 0)>{}, Ba, Bb);
+        else if (kc == 6) bfrag(int_c<(KCn > 6 ? 6 : 0)>{}, Ba, Bb);
+        else if (kc == 7) bfrag(int_c<(KCn > 7 ? 7 : 0)>{}, Ba, Bb);
+        else if (kc == 8) bfrag(int_c<(KCn > 8 ? 8 : 0)>{}, Ba, Bb);
+        else if (kc == 9) bfrag(int_c<(KCn > 9 ? 9 : 0)>{}, Ba, Bb);
+        else if (kc == 10) bfrag(int_c<(KCn > 10 ? 10 : 0)>{}, Ba, Bb);
+        else if (kc == 11) bfrag(int_c<(KCn > 11 ? 11 : 0)>{}, Ba, Bb);
+        else if (kc == 12) bfrag(int_c<(KCn > 12 ? 12 : 0)>{}, Ba, Bb);
+        else if (kc == 13) bfrag(int_c<(KCn > 13 ? 13 : 0)>{}, Ba, Bb);
+        else if (kc == 14) bfrag(int_c<(KCn > 14 ? 14 : 0)>{}, Ba, Bb);
+        else if (kc == 15) bfrag(int_c<(KCn > 15 ? 15 : 0)>{}, Ba, Bb);
+        else if (kc == 16) bfrag(int_c<(KCn > 16 ? 16 : 0)>{}, Ba, Bb);
+        else if (kc == 17) bfrag(int_c<(KCn > 17 ? 17 : 0)>{}, Ba, Bb);
+        else if (kc == 18) bfrag(int_c<(KCn > 18 ? 18 : 0)>{}, Ba, Bb);
+        else bfrag(int_c<(KCn > 19 ? 19 : 0)>{}, Ba, Bb);
         static_assert(KCn <= 20, "extend the chunk dispatch");
 #pragma unroll
         for (int mt = 0; mt < MTn; ++mt) {
@@ -204,8 +193,8 @@ __device__ __forceinline__ void pack_tiles(const f32x16 (&acc)[T][2], const floa
                 // ReLU on the packed pair: a bf16 with the sign bit set is a negative 16-bit integer, so max(., 0) as signed
                 // halves clears exactly the negative values (-0 -> +0; a positive-sign NaN stays a NaN) -- one v_pk_max_i16
                 // per two values where compare + select on the f32 values would take four instructions
-                P[2 * t + q][0][p] = fb_relu_pk(fb_cvt_pk_bf16(va[2 * p], va[2 * p + 1]));
-                P[2 * t + q][1][p] = fb_relu_pk(fb_cvt_pk_bf16(vb[2 * p], vb[2 * p + 1]));
+                P[2 * t + q][0][p] = fb_relu_pk(cvt_pk_bf16(va[2 * p], va[2 * p + 1]));
+                P[2 * t + q][1][p] = fb_relu_pk(cvt_pk_bf16(vb[2 * p], vb[2 * p + 1]));
             }
         }
     }
@@ -224,13 +213,8 @@ __device__ __forceinline__ void frag_of(const unsigned (&p)[2][4], bf16x8 &Ba, b
 constexpr int FB_SLOTS = 8;                                    // nodes of a tile pre-reduced in LDS (the rest: global atomics)
 constexpr unsigned FB_INIT = 0x3B85FFFFu;                     // orderable(-1000.0f): the reference's initial running max
 
-__device__ __forceinline__ unsigned fb_ord(unsigned bits) {    // total order; -0 == +0; NaN -> 0 (never wins)
-    if (bits == 0x80000000u) bits = 0u;
-    const unsigned o = bits ^ ((unsigned)((int)bits >> 31) | 0x80000000u);
-    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? 0u : o;
-}
 __device__ __forceinline__ float fb_round_bf16(float v) {      // the f32 value of bf16(v), round to nearest even
-    return __uint_as_float(fb_cvt_pk_bf16(v, v) << 16);
+    return __uint_as_float(cvt_pk_bf16(v, v) << 16);
 }
 
 template <bool POOL>
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
     const int j = lane & 31, h = lane >> 5;
     const unsigned vow = (unsigned)lane * 16u;
     const unsigned rowX = (unsigned)L * 4u, rowY = (unsigned)L * 2u;
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(Wst), 0, NSLICE_BF * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer(Wst, NSLICE_BF * 1024);
     for (int c = threadIdx.x; c < CH_TOTAL_BF; c += FB_THREADS) aff[c] = affine_g[c];
     for (int sl = wave; sl < G0_SL; sl += FB_WAVES)             // group 0 of the first tile
         wbuf[0][sl][lane] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rw, vow, (unsigned)sl * 1024u, 0));
@@ -268,8 +252,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
         const int l0 = (int)(t - b * tpc) * 256 + wave * 64;
         const int ca = l0 + 2 * j, cb = ca + 1;
         const int cca = ca < L ? ca : (l0 < L ? l0 : 0), ccb = cb < L ? cb : cca;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(x + b * (long long)Cin0 * L), 0, (int)((unsigned)Cin0 * rowX), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = raw_buffer(x + b * (long long)Cin0 * L, (int)((unsigned)Cin0 * rowX));
 #pragma unroll
         for (int e = 0; e < 8; ++e) {                           // rows 8h + e; rows >= Cin0 read zeros (descriptor bounds)
             xin[e][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(8 * h * L + cca) * 4u, (unsigned)e * rowX, 0));
@@ -303,8 +286,8 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
             unsigned X0[2][4];
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                X0[0][p] = fb_cvt_pk_bf16(xin[2 * p][0], xin[2 * p + 1][0]);
-                X0[1][p] = fb_cvt_pk_bf16(xin[2 * p][1], xin[2 * p + 1][1]);
+                X0[0][p] = cvt_pk_bf16(xin[2 * p][0], xin[2 * p + 1][0]);
+                X0[1][p] = cvt_pk_bf16(xin[2 * p][1], xin[2 * p + 1][1]);
             }
             const uint4 *cur = &wbuf[nb & 1][0][lane];
             uint4 *nxt = &wbuf[(nb & 1) ^ 1][wave][lane];
@@ -342,7 +325,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
         // the next tile's input: requested here, consumed after four layer-4 groups
         if (has_next) load_x(tile + gridDim.x);
         // ---- groups 3..6: layer 4, three output tiles each; K chunks 0-3 = act1 (the skip), 4-19 = act3 ------------------
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + b * (long long)384 * L, 0, (int)(384u * rowY), 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = raw_buffer(y + b * (long long)384 * L, (int)(384u * rowY));
         const unsigned voya = (unsigned)(4 * h * L + cca) * 2u, voyb = (unsigned)(4 * h * L + ccb) * 2u;
         for (int g = 0; g < 4; ++g) {
             const uint4 *cur = &wbuf[nb & 1][0][lane];
@@ -434,7 +417,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
                             float m = mx[mt];
                             const float o = __shfl_xor(m, 32, 64);                                          // the other half-wave's 16 rows
                             asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(o));
-                            const unsigned key = fb_ord(__float_as_uint(fb_round_bf16(m + bias4[mt])));
+                            const unsigned key = ord_f32(__float_as_uint(fb_round_bf16(m + bias4[mt])));
                             if (h == 0 && !(abl & 4)) {
                                 if (slot < FB_SLOTS) atomicMax(&bins[slot][(g * 3 + mt) * 32 + j], key);
                                 else atomicMax(pooled + ((long long)b * M + node) * 384 + (g * 3 + mt) * 32 + j, key);
@@ -467,7 +450,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
                         for (int r = 0; r < 16; ++r) {
                             const int orow = (r & 3) + 8 * (r >> 2);
                             const float2 ss = ap[orow];
-                            const unsigned pk = fb_cvt_pk_bf16(__fmaf_rn(a4[mt][0][r], ss.x, ss.y), __fmaf_rn(a4[mt][1][r], ss.x, ss.y));
+                            const unsigned pk = cvt_pk_bf16(__fmaf_rn(a4[mt][0][r], ss.x, ss.y), __fmaf_rn(a4[mt][1][r], ss.x, ss.y));
                             const unsigned so = so_tile + (unsigned)orow * rowY;
                             if constexpr (decltype(paired_c)::value != 0) {
                                 __builtin_amdgcn_raw_buffer_store_b32((int)pk, ry, voya, so, 0);
@@ -478,7 +461,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
                         }
                     }
                 };
-                if (paired) store_tiles(IC<1>{}); else store_tiles(IC<0>{});
+                if (paired) store_tiles(int_c<1>{}); else store_tiles(int_c<0>{});
             }
             if (g < 3 || has_next) {
                 __syncthreads();
@@ -501,7 +484,7 @@ __global__ __launch_bounds__(FB_THREADS, 1) void pointresnet_bf16_kernel(
 // Price: every A fragment read from LDS feeds one MFMA instead of two, and the weight stream is pulled once per 128 points
 // instead of once per 256.  Same stream, arithmetic and roundings as the kernels above: bit-identical results.
 template <int N, typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(IC<I>{}), ...); }
+__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(int_c<I>{}), ...); }
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
@@ -559,7 +542,7 @@ __device__ __forceinline__ void mfma_pass1(f32x16 (&acc)[MTn], const uint4 *lds_
         }
         __builtin_amdgcn_sched_barrier(0);
         bf16x8 Bx;
-        bfrag(IC<KC0 + kc>{}, Bx);
+        bfrag(int_c<KC0 + kc>{}, Bx);
 #pragma unroll
         for (int mt = 0; mt < MTn; ++mt) {
             const bf16x8 A = __builtin_bit_cast(bf16x8, Af[kc & 1][mt]);
@@ -586,7 +569,7 @@ __device__ __forceinline__ void pack_tiles1(const f32x16 (&acc)[T], const float2
 #pragma unroll
             for (int e = 0; e < 8; ++e) va[e] = __fmaf_rn(acc[t][8 * q + e], sc[e], sh[e]);
 #pragma unroll
-            for (int p = 0; p < 4; ++p) P[2 * t + q][p] = fb_relu_pk(fb_cvt_pk_bf16(va[2 * p], va[2 * p + 1]));
+            for (int p = 0; p < 4; ++p) P[2 * t + q][p] = fb_relu_pk(cvt_pk_bf16(va[2 * p], va[2 * p + 1]));
         }
     }
 }
@@ -612,7 +595,7 @@ __global__ __launch_bounds__(P2_THREADS, 2) void pointresnet_bf16_pool2_kernel(
     const int j = lane & 31, h = lane >> 5;
     const unsigned vow = (unsigned)lane * 16u;
     const unsigned rowX = (unsigned)L * 4u;
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(Wst), 0, NSLICE_BF * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer(Wst, NSLICE_BF * 1024);
     const char *wst = reinterpret_cast<const char *>(Wst);
     const unsigned wbuf_lds = (unsigned)reinterpret_cast<size_t>(&wbuf[0][0][0]);      // LDS byte address of the W buffers (LDS-DMA target)
     bool unit_lane = true;
@@ -634,8 +617,7 @@ __global__ __launch_bounds__(P2_THREADS, 2) void pointresnet_bf16_pool2_kernel(
         const int t0 = (int)(t - b * tpc) * 128, l0 = t0 + wave * 32;
         const int ca = l0 + j;
         const int cc = ca < L ? ca : (l0 < L ? l0 : 0);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(x + b * (long long)Cin0 * L), 0, (int)((unsigned)Cin0 * rowX), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx = raw_buffer(x + b * (long long)Cin0 * L, (int)((unsigned)Cin0 * rowX));
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             xin[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (unsigned)(8 * h * L + cc) * 4u, (unsigned)e * rowX, 0));
@@ -657,7 +639,7 @@ __global__ __launch_bounds__(P2_THREADS, 2) void pointresnet_bf16_pool2_kernel(
         {   // group 0: layer 1 + layer 2, staging layer 3's first group (32 slices: 8 consecutive per wave over the 4 chunks of layer 2)
             unsigned X0[4];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) X0[p] = fb_cvt_pk_bf16(xin[2 * p], xin[2 * p + 1]);
+            for (int p = 0; p < 4; ++p) X0[p] = cvt_pk_bf16(xin[2 * p], xin[2 * p + 1]);
             const uint4 *cur = &wbuf[nb & 1][0][lane];
             const unsigned nxt = wbuf_lds + (unsigned)(((nb & 1) ^ 1) * P2_BUF) * 1024u;
             f32x16 a1[2];
@@ -772,7 +754,7 @@ __global__ __launch_bounds__(P2_THREADS, 2) void pointresnet_bf16_pool2_kernel(
                         float m = mx[mt];
                         const float o = __shfl_xor(m, 32, 64);
                         asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(o));
-                        const unsigned key = fb_ord(__float_as_uint(fb_round_bf16(m + bias4[mt])));
+                        const unsigned key = ord_f32(__float_as_uint(fb_round_bf16(m + bias4[mt])));
                         if (h == 0) {
                             if (slot < P2_SLOTS) atomicMax(&bins[slot][(g * 3 + mt) * 32 + j], key);
                             else atomicMax(pooled + ((long long)b * M + node) * 384 + (g * 3 + mt) * 32 + j, key);

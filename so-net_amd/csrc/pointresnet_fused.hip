@@ -50,11 +50,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int PF_THREADS = 256, PF_WAVES = 4;
 constexpr int WPTS = 64, TPTS = PF_WAVES * WPTS;              // points per wave / per workgroup tile
@@ -93,12 +88,6 @@ constexpr float F16_MAX = 2047.0f;                             // 32 * 2047 = 65
 constexpr float F16_MAX32 = 65504.0f;
 constexpr float ACC_UNSCALE = 0.0009765625f;                   // accumulators hold 1024 * (W . x)
 constexpr float ACC_TO_X32 = 0.03125f;                         // ... and 32 x = acc * (scale / 32) + 32 shift
-__device__ __forceinline__ unsigned cvt_pk_f16(float lo, float hi) {        // one v_cvt_pk_f16_f32 (round to nearest even)
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
-}
-__device__ __forceinline__ float f16_lo(unsigned pk) { return (float)__builtin_bit_cast(f16x2_t, pk)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned pk) { return (float)__builtin_bit_cast(f16x2_t, pk)[1]; }
 __device__ __forceinline__ float clamp_f16(float x) { return __builtin_fminf(__builtin_fmaxf(x, -F16_MAX), F16_MAX); }
 __device__ __forceinline__ f16x8 as_f16x8(u32x4_t v) { return __builtin_bit_cast(f16x8, v); }
 // the network input (clamped, no affine): 8 channel values of one point -> (h, m)
@@ -106,9 +95,10 @@ __device__ __forceinline__ void split_input(const float (&v)[8], u32x4_t &h, u32
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const float x0 = clamp_f16(v[2 * p]), x1 = clamp_f16(v[2 * p + 1]);
-        const unsigned hh = cvt_pk_f16(32.f * x0, 32.f * x1);                         // 32 xh
+        unsigned hh, mm;
+        p16_split2(32.f * x0, 32.f * x1, hh, mm);                                     // 32 xh, 32 (x - xh)
         h[p] = hh;
-        m[p] = cvt_pk_f16(32.f * x0 - f16_lo(hh), 32.f * x1 - f16_hi(hh));            // 32 (x - xh), exact before the rounding
+        m[p] = mm;
     }
 }
 
@@ -235,8 +225,8 @@ __global__ __launch_bounds__(256) void pointresnet_pack_kernel(const float *__re
             // clamped (a finite, wrong product instead of inf - inf = NaN in the residual); the range log above has the true value
             const float w0 = v[0] != v[0] ? v[0] : __builtin_fminf(__builtin_fmaxf(32.f * v[0], -F16_MAX32), F16_MAX32);     // (NaN stays NaN)
             const float w1 = v[1] != v[1] ? v[1] : __builtin_fminf(__builtin_fmaxf(32.f * v[1], -F16_MAX32), F16_MAX32);
-            const unsigned hh = cvt_pk_f16(w0, w1);
-            const unsigned ll = cvt_pk_f16(w0 - f16_lo(hh), w1 - f16_hi(hh));
+            unsigned hh, ll;
+            p16_split2(w0, w1, hh, ll);
             w[p] = term == 0 ? hh : ll;
         }
     }
@@ -259,11 +249,6 @@ constexpr int SEG_SLOTS = 16;                                 // nodes of a 256-
 constexpr int PCH = 32 * MT4;                                 // channels per layer-4 pass
 constexpr unsigned SEG_INIT = 0x3B85FFFFu;                    // orderable(-1000.0f): the reference's initial running max
 
-__device__ __forceinline__ unsigned ord_f32(unsigned bits) {   // total order; -0 == +0; NaN -> 0 (never wins)
-    if (bits == 0x80000000u) bits = 0u;
-    const unsigned o = bits ^ ((unsigned)((int)bits >> 31) | 0x80000000u);
-    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? 0u : o;
-}
 #ifdef SONET_PROF
 // Profiling build only (make prof; tools/fused_phases.py): per-wave shader-clock cycles spent in each phase.
 constexpr int PROF_N = 32;
@@ -520,8 +505,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void pointresnet_fused_kernel(
         t = t < ntiles ? t : ntiles - 1;                        // unconditional: the registers are dead between layer 1 and here
         const long long bb = t / tpc;
         const int t0 = (int)(t - bb * tpc) * TPTS;
-        const __amdgpu_buffer_rsrc_t rxx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float *>(x + bb * (long long)Cin0 * L), 0, (int)((unsigned)Cin0 * rowB), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rxx = raw_buffer(x + bb * (long long)Cin0 * L, (int)((unsigned)Cin0 * rowB));
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int ll0 = t0 + wave * WPTS + 32 * c;
@@ -661,8 +645,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void pointresnet_fused_kernel(
                 pbh[1] = PF_PARK(k + 1, 1, 0); pbm[1] = PF_PARK(k + 1, 1, 1);
             }
             if constexpr (k + 1 == KC3) {                       // the tile's input again (from L2), for the second run of layer 1
-                const __amdgpu_buffer_rsrc_t rxx = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<float *>(x + b * (long long)Cin0 * L), 0, (int)((unsigned)Cin0 * rowB), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rxx = raw_buffer(x + b * (long long)Cin0 * L, (int)((unsigned)Cin0 * rowB));
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -709,10 +692,8 @@ __global__ __launch_bounds__(PF_THREADS, 1) void pointresnet_fused_kernel(
         // Pass 0 carries the in-place jobs of layer 3's second tile group (one per step, steps 0-15: tile 4 + s/4, half (s/2)&1,
         // column tile s&1 -- tile 4 is complete when step 12 needs it); passes 1-3 run the same steps without jobs.
         // (y == nullptr -- the P16-only store variant: a descriptor of zero bytes, every f32 store falls outside it and writes nothing)
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-            y ? y + b * (long long)(32 * T3) * L : const_cast<float *>(x), 0, y ? (int)((unsigned)(32 * T3) * rowB) : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t ryp = __builtin_amdgcn_make_buffer_rsrc(
-            P16OUT ? static_cast<char *>(yp) + b * (long long)(2 * T3) * 64 * L : nullptr, 0, P16OUT ? (int)((unsigned)(2 * T3) * 64u * (unsigned)L) : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ry = raw_buffer(y ? y + b * (long long)(32 * T3) * L : x, y ? (int)((unsigned)(32 * T3) * rowB) : 0);
+        const __amdgpu_buffer_rsrc_t ryp = raw_buffer(P16OUT ? static_cast<char *>(yp) + b * (long long)(2 * T3) * 64 * L : nullptr, P16OUT ? (int)((unsigned)(2 * T3) * 64u * (unsigned)L) : 0);
 #define ACC4(u, c) acc[u][c]
 #define PF_L4_BODY(JOBS)                                                                                 \
             SFOR(kc, KC4)                                                                                \
@@ -881,9 +862,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void pointresnet_fused_kernel(
                                 for (int p = 0; p < 4; ++p) {
                                     const float x0 = vv[8 * q + 2 * p], x1 = vv[8 * q + 2 * p + 1];
                                     range_track(yr4, x0, x1);
-                                    const float X0 = 32.f * __builtin_amdgcn_fmed3f(x0, -2047.f, 2047.f), X1 = 32.f * __builtin_amdgcn_fmed3f(x1, -2047.f, 2047.f);
-                                    hh[p] = cvt_pk_f16(X0, X1);
-                                    mm[p] = cvt_pk_f16(X0 - f16_lo(hh[p]), X1 - f16_hi(hh[p]));
+                                    p16_split_pair(x0, x1, hh[p], mm[p]);
                                 }
                                 const unsigned so = (unsigned)((ct * 2 + q) * 2) * (unsigned)L * 32u;
                                 const u32x4_t hv = {hh[0], hh[1], hh[2], hh[3]}, mv = {mm[0], mm[1], mm[2], mm[3]};
@@ -1002,14 +981,7 @@ __global__ __launch_bounds__(256) void pooled_decode_kernel(const unsigned *__re
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 range_track(xr, v[2 * q], v[2 * q + 1]);
-                const float X0 = 32.f * __builtin_amdgcn_fmed3f(v[2 * q], -2047.f, 2047.f), X1 = 32.f * __builtin_amdgcn_fmed3f(v[2 * q + 1], -2047.f, 2047.f);
-                typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-                typedef float f2_t __attribute__((ext_vector_type(2)));
-                const f2_t xv = {X0, X1};
-                const h2_t hp = __builtin_convertvector(xv, h2_t);
-                const f2_t rv = {X0 - (float)hp[0], X1 - (float)hp[1]};
-                hv[q] = __builtin_bit_cast(unsigned, hp);
-                mv[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(rv, h2_t));
+                p16_split_pair(v[2 * q], v[2 * q + 1], hv[q], mv[q]);
             }
             const int kc = c0 / 16 + qq;
             out_p16[((long long)(kc * 2 + 0) * 2 + hh) * BM + l] = make_uint4(hv[0], hv[1], hv[2], hv[3]);

@@ -124,21 +124,6 @@ __global__ __launch_bounds__(256) void node_add_affine_act_kernel(float *__restr
 // K * M: one ninth of the MFMAs at K = 9) and gathered here; the NL <= 4 lead channels are exact f32 fmas in channel order.
 // One workgroup per (cloud, 8 channels): gidx / lead are read once per 8 output rows, the 8 node rows sit in LDS.
 constexpr int NGL_CH = 8, NGL_THREADS = 128;
-__device__ __forceinline__ float ngl_ld(const float *p, size_t i) { return p[i]; }
-__device__ __forceinline__ float ngl_ld(const uint16_t *p, size_t i) { return __uint_as_float((unsigned)p[i] << 16); }
-__device__ __forceinline__ void ngl_st4(float *o, const float (&v)[4]) { *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void ngl_st4(uint16_t *o, const float (&v)[4]) {                 // bfloat16, round to nearest even
-    unsigned a, b;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(a) : "v"(v[0]), "v"(v[1]));
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(b) : "v"(v[2]), "v"(v[3]));
-    *reinterpret_cast<uint2 *>(o) = make_uint2(a, b);
-}
-__device__ __forceinline__ void ngl_st1(float *o, float v) { *o = v; }
-__device__ __forceinline__ void ngl_st1(uint16_t *o, float v) {
-    unsigned a;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(a) : "v"(v), "v"(v));
-    *o = (uint16_t)(a & 0xFFFFu);
-}
 // T: storage type of z and out (float, or uint16_t = bfloat16 bits: values widened, arithmetic in f32, one rounding on the store)
 template <typename T>
 __global__ __launch_bounds__(NGL_THREADS) void node_gather_lead_kernel(const T *__restrict__ z, const int32_t *__restrict__ gidx,
@@ -151,7 +136,7 @@ __global__ __launch_bounds__(NGL_THREADS) void node_gather_lead_kernel(const T *
     const int cb = blockIdx.x * NGL_CH;
     const long long b = blockIdx.y;
     const int nch = min(NGL_CH, C - cb);
-    for (int i = threadIdx.x; i < nch * M; i += NGL_THREADS) zs[i] = ngl_ld(z, (size_t)((long long)b * C + cb) * M + i);
+    for (int i = threadIdx.x; i < nch * M; i += NGL_THREADS) zs[i] = ld_f32(z, ((long long)b * C + cb) * M + i);
     if (threadIdx.x < nch) {
         const int c = cb + threadIdx.x;
         for (int i = 0; i < 4; ++i) coef[threadIdx.x * 6 + i] = i < NL ? wl[c * NL + i] : 0.f;
@@ -198,10 +183,10 @@ __global__ __launch_bounds__(NGL_THREADS) void node_gather_lead_kernel(const T *
                 v[e] = (relu && a < 0.f) ? 0.f : a;
             }
             T *o = ob + (long long)c * L + l;
-            if (vec) ngl_st4(o, v);
+            if (vec) st4_rne(o, v);
             else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) if (l + e < L) ngl_st1(o + e, v[e]);
+                for (int e = 0; e < 4; ++e) if (l + e < L) st_rne(o, e, v[e]);
             }
         }
     }
@@ -257,12 +242,6 @@ __global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(const double *__rest
 // widened from bf16, results rounded to nearest-even bf16.  Two elements (one dword) per lane when the rows are dword aligned.
 __device__ __forceinline__ float bf_lo(unsigned d) { return __uint_as_float(d << 16); }
 __device__ __forceinline__ float bf_hi(unsigned d) { return __uint_as_float(d & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned bf_pack(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ float bf_at(const uint16_t *p, long long i) { return __uint_as_float((unsigned)p[i] << 16); }
 
 // grid (chunks, C) as bwd_stats_kernel / channel_stats_kernel; raw == nullptr: plain statistics of gy (sum, sum of squares)
 template <bool PAIR>
@@ -287,8 +266,8 @@ __global__ __launch_bounds__(BW_THREADS) void bwd_stats_bf16_kernel(const uint16
             g[0] = bf_lo(dg); g[1] = bf_hi(dg);
             if (raw) { const unsigned dr = *reinterpret_cast<const unsigned *>(raw + o); r[0] = bf_lo(dr); r[1] = bf_hi(dr); }
         } else {
-            g[0] = bf_at(gy, o);
-            if (raw) r[0] = bf_at(raw, o);
+            g[0] = ld_f32(gy, o);
+            if (raw) r[0] = ld_f32(raw, o);
         }
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -348,11 +327,11 @@ __global__ __launch_bounds__(256) void rowwise_bf16_kernel(const uint16_t *__res
         for (int t = blockIdx.y * 256 + threadIdx.x; t < Lv; t += gridDim.y * 256) {
             const unsigned dr = reinterpret_cast<const unsigned *>(r)[t];
             const unsigned dg = MODE == 1 ? reinterpret_cast<const unsigned *>(g)[t] : 0u;
-            reinterpret_cast<unsigned *>(o)[t] = bf_pack(f(bf_lo(dr), bf_lo(dg)), f(bf_hi(dr), bf_hi(dg)));
+            reinterpret_cast<unsigned *>(o)[t] = cvt_pk_bf16(f(bf_lo(dr), bf_lo(dg)), f(bf_hi(dr), bf_hi(dg)));
         }
     } else {
         for (int t = blockIdx.y * 256 + threadIdx.x; t < L; t += gridDim.y * 256)
-            o[t] = (uint16_t)(bf_pack(f(bf_at(r, t), MODE == 1 ? bf_at(g, t) : 0.f), 0.f) & 0xFFFFu);
+            o[t] = (uint16_t)(cvt_pk_bf16(f(ld_f32(r, t), MODE == 1 ? ld_f32(g, t) : 0.f), 0.f) & 0xFFFFu);
     }
 }
 
@@ -390,9 +369,8 @@ namespace {
 // pure streams over [B][C][L] tensors; with 4-byte accesses per lane they ran at 3.0-4.3 TB/s (and the statistics pass paid a 64-bit
 // division per element for its flat index).  Same arithmetic per element, 16 bytes per lane and access (4 f32 / 8 bf16), one (b, c) row
 // segment per workgroup: used whenever the rows are 16-byte aligned (L % 4 == 0 resp. L % 8 == 0); the scalar kernels above remain for the rest.
-typedef unsigned vu4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
-    const vu4 v = __builtin_nontemporal_load(reinterpret_cast<const vu4 *>(p));
+    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 template <bool BF> struct VecIO;
@@ -412,7 +390,7 @@ template <> struct VecIO<true> {                               // bf16: 8 elemen
         v[4] = bf_lo(d.z); v[5] = bf_hi(d.z); v[6] = bf_lo(d.w); v[7] = bf_hi(d.w);
     }
     static __device__ __forceinline__ uint4 pack(const float (&v)[8]) {
-        return make_uint4(bf_pack(v[0], v[1]), bf_pack(v[2], v[3]), bf_pack(v[4], v[5]), bf_pack(v[6], v[7]));
+        return make_uint4(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]), cvt_pk_bf16(v[4], v[5]), cvt_pk_bf16(v[6], v[7]));
     }
 };
 
@@ -925,12 +903,6 @@ __global__ __launch_bounds__(64) void pooled_sort_kernel(const int32_t *__restri
     }
 }
 
-__device__ __forceinline__ void pd_store(float *p, size_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void pd_store(uint16_t *p, size_t i, float v) {     // bfloat16, round to nearest even
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(v));
-    p[i] = (uint16_t)(r & 0xFFFFu);
-}
 template <typename TO>
 __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32_t *__restrict__ tile_off, const uint32_t *__restrict__ ent_key,
                                                            const float *__restrict__ ent_val, const float *__restrict__ g_pooled /*[B][E]: the entries' values by id*/,
@@ -1016,8 +988,7 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32
         for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
             const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
             if (l0 + col >= L) continue;                        // (L even: col + 1 is inside too)
-            unsigned pk;
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(acc[col * ld + r]), "v"(acc[(col + 1) * ld + r]));
+            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
             const int ch = ch0 + r;
             TO *dst = ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L + l0 + col : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col;
             *reinterpret_cast<unsigned *>(dst) = pk;
@@ -1029,8 +1000,8 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32
         if (l0 + col >= L) continue;
         const float v = acc[col * ld + r];
         const int ch = ch0 + r;
-        if (ch < C1) pd_store(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
-        else pd_store(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
+        if (ch < C1) st_rne(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
+        else st_rne(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
     }
 }
 
@@ -1123,8 +1094,7 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad4_kernel(const int3
         for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
             const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
             if (l0 + col >= L) continue;
-            unsigned pk;
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(acc[col * ld + r]), "v"(acc[(col + 1) * ld + r]));
+            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
             const int ch = ch0 + r;
             TO *dst = ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L + l0 + col : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col;
             *reinterpret_cast<unsigned *>(dst) = pk;
@@ -1136,8 +1106,8 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad4_kernel(const int3
         if (l0 + col >= L) continue;
         const float v = acc[col * ld + r];
         const int ch = ch0 + r;
-        if (ch < C1) pd_store(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
-        else pd_store(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
+        if (ch < C1) st_rne(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
+        else st_rne(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
     }
 }
 #endif  // SONET_VARIANTS
@@ -1346,8 +1316,7 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad5_kernel(const int3
         for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
             const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
             if (l0 + col >= L) continue;
-            unsigned pk;
-            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(acc[col * ld + r]), "v"(acc[(col + 1) * ld + r]));
+            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
             const int ch = ch0 + r;
             TO *dst = ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L + l0 + col : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col;
             *reinterpret_cast<unsigned *>(dst) = pk;
@@ -1359,8 +1328,8 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad5_kernel(const int3
         if (l0 + col >= L) continue;
         const float v = acc[col * ld + r];
         const int ch = ch0 + r;
-        if (ch < C1) pd_store(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
-        else pd_store(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
+        if (ch < C1) st_rne(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
+        else st_rne(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
     }
 }
 
@@ -1376,20 +1345,12 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad5_kernel(const int3
 constexpr int PM_TL = 64;                      // columns per workgroup (two 32-column buckets)
 constexpr int PM_PITCH = 784;                  // bytes per G^T row: 384 channels x 2 + 16 (196 words = 4 mod 64 banks: 16-byte reads of 16 rows tile the banks)
 
-__device__ __forceinline__ unsigned pm_cvt_pk(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 template <int NMT, int CH /*64-column halves per workgroup: 1 or 2*/>
 __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32_t *__restrict__ tile_off, const uint32_t *__restrict__ ent_key,
                                                                 const float *__restrict__ ent_val, const uint4 *__restrict__ Wtp,
                                                                 int E, int M, int C, int KC, int C1, int C2, int L, int nbucket,
                                                                 uint16_t *__restrict__ gx1, uint16_t *__restrict__ gx2)
 {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     constexpr int NR = 32 * CH;                  // G^T rows (column pairs) per parity
     extern __shared__ uint4 pm_lds[];            // Ge[NR][PM_PITCH] | Go[NR][PM_PITCH]: G^T of the even / odd columns, channels contiguous
     unsigned char *Ge = reinterpret_cast<unsigned char *>(pm_lds), *Go = Ge + NR * PM_PITCH;
@@ -1427,7 +1388,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
         do {
             assumed = old;
             const float cur = __uint_as_float(((assumed >> sh) & 0xFFFFu) << 16);
-            const unsigned nb = pm_cvt_pk(cur + g, 0.f) & 0xFFFFu;
+            const unsigned nb = cvt_pk_bf16(cur + g, 0.f) & 0xFFFFu;
             old = atomicCAS(wd, assumed, (assumed & ~(0xFFFFu << sh)) | (nb << sh));
         } while (old != assumed);
     }
@@ -1470,7 +1431,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ci = (mhalf * NMT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                *reinterpret_cast<unsigned *>(ot + ci * OP + (64 * chalf + 2 * n) * 2) = pm_cvt_pk(acc[mt][0][r], acc[mt][1][r]);
+                *reinterpret_cast<unsigned *>(ot + ci * OP + (64 * chalf + 2 * n) * 2) = cvt_pk_bf16(acc[mt][0][r], acc[mt][1][r]);
             }
         __syncthreads();
         const int l0 = tile * (PM_TL * CH);
@@ -1499,7 +1460,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
             for (int r = 0; r < 16; ++r) {
                 const int ci = (mhalf * NMT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (ci >= C1 + C2) continue;
-                const unsigned pk = pm_cvt_pk(acc[mt][0][r], acc[mt][1][r]);
+                const unsigned pk = cvt_pk_bf16(acc[mt][0][r], acc[mt][1][r]);
                 uint16_t *dst = ci < C1 ? gx1 + ((size_t)b * C1 + ci) * L + col : gx2 + ((size_t)b * C2 + (ci - C1)) * L + col;
                 *reinterpret_cast<unsigned *>(dst) = pk;
             }
@@ -1591,14 +1552,14 @@ __global__ __launch_bounds__(PW_T) void pooled_wgrad_kernel(const float *__restr
             // bf16 rows (PW_R == 2: channels ci0, ci0 + 1) sit INTERLEAVED in LDS, one dword per column = (row ci0 | row ci0 + 1 << 16): an entry
             // costs ONE LDS read for both rows (round 6; two 2-byte reads before -- the multiply is bound by its LDS reads).  The values and
             // the order of the fmas are unchanged: bit-identical sums.  With xs / xh the rows are normalised on the way in: act(raw * xs + xh)
-            // in f32, ReLU, one round-to-nearest-even back to bf16 -- sonet_channel_affine_act_bf16's arithmetic.
+            // in f32, ReLU, one round-to-nearest-even back to bf16 -- sonet_channel_affine_act_out_bf16's arithmetic.
             const float s0 = xs ? xs[ci0] : 1.f, h0 = xs ? xh[ci0] : 0.f;
             const float s1 = (xs && nr > 1) ? xs[ci0 + 1] : 1.f, h1 = (xs && nr > 1) ? xh[ci0 + 1] : 0.f;
             auto act16 = [&](unsigned v, bool second) -> unsigned {
                 if (xs == nullptr) return v;
                 float f = __fmaf_rn(__uint_as_float(v << 16), second ? s1 : s0, second ? h1 : h0);
                 if (xrelu && f < 0.f) f = 0.f;
-                return bf_pack(f, 0.f) & 0xFFFFu;
+                return cvt_pk_bf16(f, 0.f) & 0xFFFFu;
             };
             unsigned *pairs = reinterpret_cast<unsigned *>(rows_raw);
             const uint16_t *x0 = reinterpret_cast<const uint16_t *>(xb), *x1r = x0 + L;
@@ -1830,13 +1791,8 @@ extern "C" int sonet_pooled_dgrad_mfma_bf16(const float *g_pooled, const int32_t
     if (ch == 2 && (size_t)CT * 32 * 272 > lds) lds = (size_t)CT * 32 * 272;          // (the output tile reuses the image)
     const uint4 *wtp = reinterpret_cast<const uint4 *>(wt_pack);
     uint16_t *g2 = gx2 ? gx2 : gx1;
-#define PM_LAUNCH1(NN, CC) do { static bool attr_set = false;                                                                        \
-        if (!attr_set) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(&pooled_dgrad_mfma_kernel<NN, CC>),                   \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)                \
-                             return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: cannot reserve the LDS", what);                           \
-                         attr_set = true; }                                                                                           \
-        hipLaunchKernelGGL((pooled_dgrad_mfma_kernel<NN, CC>), dim3(ntile_l, B), dim3(128 * CC), lds, st, tile_off, ent_key, ent_val, wtp, E, M, C, C / 16, \
-                           C1, C2, L, nbucket, gx1, g2); } while (0)
+#define PM_LAUNCH1(NN, CC) do { if (const int rc_ = sonet::launch_lds_once<&pooled_dgrad_mfma_kernel<NN, CC>, 128 * 1024>(what, dim3(ntile_l, B), dim3(128 * CC), lds, st, \
+                tile_off, ent_key, ent_val, wtp, E, M, C, C / 16, C1, C2, L, nbucket, gx1, g2)) return rc_; } while (0)
 #define PM_LAUNCH(NN) do { if (ch == 2) PM_LAUNCH1(NN, 2); else PM_LAUNCH1(NN, 1); } while (0)
     switch (CT / 2) {
         case 1: PM_LAUNCH(1); break;

@@ -886,7 +886,6 @@ __global__ __launch_bounds__(SP_THREADS) void som_sort_fill2_kernel(
 
 // Host dispatch of the selection kernels: f(k, id bits) with both as compile-time constants (std::integral_constant) -- k = 1..4
 // (checked by the callers) and the id bits of the packed keys, 6 for M <= 64 nodes, else 10 (M <= 1024).
-template <int V> using int_c = std::integral_constant<int, V>;
 template <class F>
 int som_dispatch(int k, int M, F f)
 {

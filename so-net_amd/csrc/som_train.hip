@@ -27,7 +27,6 @@ constexpr int ST_MAX_POINTS = SONET_SOM_TRAIN_MAX_POINTS;
 constexpr size_t ST_LDS_MAX = 160 * 1024;
 
 
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 __host__ __device__ inline size_t st_node_bytes(int M) {         // nodes | means | sums | counts | max word, padded to 16 B
     return ((size_t)M * (2 * sizeof(float4) + 3 * sizeof(unsigned long long) + sizeof(unsigned)) + 16 + 15) & ~(size_t)15;
@@ -36,16 +35,16 @@ __host__ __device__ inline size_t st_point_bytes(int N) { return (size_t)((N + 3
 
 // the nearest node of four points (two packed pairs, one LDS broadcast read per node), ties to the lowest id
 __device__ __forceinline__ void nearest4(const float4 *__restrict__ nodes, int M, const float4 X, const float4 Y, const float4 Z, int id[4]) {
-    const f2 xa{X.x, X.y}, ya{Y.x, Y.y}, za{Z.x, Z.y}, xb{X.z, X.w}, yb{Y.z, Y.w}, zb{Z.z, Z.w};
+    const f32x2_t xa{X.x, X.y}, ya{Y.x, Y.y}, za{Z.x, Z.y}, xb{X.z, X.w}, yb{Y.z, Y.w}, zb{Z.z, Z.w};
     float b0 = __builtin_inff(), b1 = b0, b2 = b0, b3 = b0;
     int j0 = 0, j1 = 0, j2 = 0, j3 = 0;
 #pragma unroll 2
     for (int m = 0; m < M; ++m) {
         const float4 nd = nodes[m];
-        const f2 dxa = xa - nd.x, dya = ya - nd.y, dza = za - nd.z;
-        const f2 dxb = xb - nd.x, dyb = yb - nd.y, dzb = zb - nd.z;
-        const f2 da = (dxa * dxa + dya * dya) + dza * dza;     // -ffp-contract=off: no FMA, each lane rounded like sqdist (som.hip)
-        const f2 db = (dxb * dxb + dyb * dyb) + dzb * dzb;
+        const f32x2_t dxa = xa - nd.x, dya = ya - nd.y, dza = za - nd.z;
+        const f32x2_t dxb = xb - nd.x, dyb = yb - nd.y, dzb = zb - nd.z;
+        const f32x2_t da = (dxa * dxa + dya * dya) + dza * dza;     // -ffp-contract=off: no FMA, each lane rounded like sqdist (som.hip)
+        const f32x2_t db = (dxb * dxb + dyb * dyb) + dzb * dzb;
         if (da.x < b0) { b0 = da.x; j0 = m; }
         if (da.y < b1) { b1 = da.y; j1 = m; }
         if (db.x < b2) { b2 = db.x; j2 = m; }

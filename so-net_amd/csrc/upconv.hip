@@ -29,8 +29,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int UP_THREADS = 256;
 constexpr int UP_TP = SONET_UPCONV_TILE_PIXELS;            // columns (low-resolution pixels) per workgroup

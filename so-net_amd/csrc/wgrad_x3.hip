@@ -22,25 +22,18 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int WG_THREADS = 256;                                 // 4 waves
 constexpr int WG_BLK = 128;                                     // output block edge: 4 tiles of 32
 constexpr int WG_UNIT = 32;                                     // columns per loop iteration = two MFMA steps
 
-__device__ __forceinline__ unsigned wg_cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 // (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
 __device__ __forceinline__ void wg_split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-    h = wg_cvt_pk_bf16(x0, x1);
+    h = cvt_pk_bf16(x0, x1);
     const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xFFFF0000u);
-    m = wg_cvt_pk_bf16(r0, r1);
+    m = cvt_pk_bf16(r0, r1);
     const float q0 = r0 - __uint_as_float(m << 16), q1 = r1 - __uint_as_float(m & 0xFFFF0000u);
-    l = wg_cvt_pk_bf16(q0, q1);
+    l = cvt_pk_bf16(q0, q1);
 }
 
 // 16 floats of one row: columns [l, l + 16) of `row` (zeros past L or when the row does not exist)
@@ -333,30 +326,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_bf16_kernel(
 // have, and everyone has finished the previous unit, whose slot the next request then overwrites.  f32 partial blocks per slice,
 // summed by wgrad_reduce_kernel in a fixed order.
 // XAFF (bf16 training with normalise-on-load): x holds the RAW output of a BatchNorm layer; a wave applies act(raw * xs[c] + xh[c]) -- f32 fma,
-// round to nearest even, ReLU: what sonet_channel_affine_act_bf16 would have stored -- to the x fragment it has just read from LDS (a lane's
+// round to nearest even, ReLU: what sonet_channel_affine_act_out_bf16 would have stored -- to the x fragment it has just read from LDS (a lane's
 // eight values are one channel row: one coefficient pair per lane and x tile, held in registers for the whole launch).  Columns past L and
 // rows past Cin come from the zeroed 16 bytes and would turn into act(xh): their g partners are zero as well (same zeroed source), the
 // product is unchanged.
 constexpr int WS_UNIT = 64;
-typedef float ws_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned ws_cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 __device__ __forceinline__ uint4 ws_xaff(uint4 v, float sc, float sh, unsigned floor2) {
-    unsigned d[4] = {v.x, v.y, v.z, v.w};
-    const ws_f2 s2 = {sc, sc}, h2 = {sh, sh};
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const ws_f2 xx = {__uint_as_float(d[p] << 16), __uint_as_float(d[p] & 0xFFFF0000u)};
-        ws_f2 r;
-        asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(xx), "v"(s2), "v"(h2));
-        unsigned o = ws_cvt_pk_bf16(r[0], r[1]);
-        asm("v_pk_max_i16 %0, %1, %2" : "=v"(o) : "v"(o), "v"(floor2));
-        d[p] = o;
-    }
-    return make_uint4(d[0], d[1], d[2], d[3]);
+    const f32x2_t s2 = {sc, sc}, h2 = {sh, sh};
+    return make_uint4(bf16_pair_affine_act(v.x, s2, h2, floor2), bf16_pair_affine_act(v.y, s2, h2, floor2),
+                      bf16_pair_affine_act(v.z, s2, h2, floor2), bf16_pair_affine_act(v.w, s2, h2, floor2));
 }
 template <int GT, bool XAFF = false>
 __global__ __launch_bounds__(256, 1) void wgrad_bf16s_kernel(const uint16_t *__restrict__ g, const uint16_t *__restrict__ x,
@@ -600,22 +578,11 @@ static int wgrad_bf16_impl(const char *what, const uint16_t *g, const uint16_t *
             float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + 256);
             const size_t lds = (size_t)3 * (q.gt * 128 + 128) * 128;
             const dim3 grid((unsigned)(q.oblocks * q.cblocks * q.nsplit)), block(256);
-#define WS_LAUNCH(GG) do { static bool attr_set = false;                                                                              \
-                if (!attr_set) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_bf16s_kernel<GG>),                    \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)       \
-                                     return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: cannot reserve the LDS", what);                   \
-                                 attr_set = true; }                                                                                   \
-                hipLaunchKernelGGL(wgrad_bf16s_kernel<GG>, grid, block, lds, st, g, x, zero16, part, Cout, Cin, L, q.nL, q.units, q.nsplit, q.oblocks, q.cblocks); } while (0)
-#define WS_LAUNCH_X(GG) do { static bool attr_set = false;                                                                            \
-                if (!attr_set) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_bf16s_kernel<GG, true>),              \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)       \
-                                     return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: cannot reserve the LDS", what);                   \
-                                 attr_set = true; }                                                                                   \
-                hipLaunchKernelGGL((wgrad_bf16s_kernel<GG, true>), grid, block, lds, st, g, x, zero16, part, Cout, Cin, L, q.nL, q.units, q.nsplit, q.oblocks, q.cblocks, \
-                                   xs, xh, xrelu); } while (0)
-            if (xs) { if (q.gt == 2) WS_LAUNCH_X(2); else WS_LAUNCH_X(1); }
-            else if (q.gt == 2) WS_LAUNCH(2); else WS_LAUNCH(1);
-#undef WS_LAUNCH_X
+            // (without normalise-on-load xs, xh are NULL and xrelu is 0: what the kernel's defaults were)
+#define WS_LAUNCH(GG, XX) do { if (const int rc_ = sonet::launch_lds_once<&wgrad_bf16s_kernel<GG, XX>, 160 * 1024>(what, grid, block, lds, st, g, x, zero16, part, \
+                        Cout, Cin, L, q.nL, q.units, q.nsplit, q.oblocks, q.cblocks, xs, xh, xrelu)) return rc_; } while (0)
+            if (xs) { if (q.gt == 2) WS_LAUNCH(2, true); else WS_LAUNCH(1, true); }
+            else if (q.gt == 2) WS_LAUNCH(2, false); else WS_LAUNCH(1, false);
 #undef WS_LAUNCH
             const long long n = (long long)Cout * Cin;
             hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)sonet::ceil_div64(n, 64)), dim3(256), 0, st, part, dw,
@@ -645,7 +612,7 @@ extern "C" int sonet_wgrad_bf16(const uint16_t *g, const uint16_t *x, float *dw,
 }
 
 /* sonet_wgrad_bf16 when x is the RAW (bf16) output of a BatchNorm layer whose normalise pass was never run (bf16 training with
- * normalise-on-load): x = act(raw * xs[c] + xh[c]) rounded to bf16 is applied to the fragments, bit for bit what sonet_channel_affine_act_bf16
+ * normalise-on-load): x = act(raw * xs[c] + xh[c]) rounded to bf16 is applied to the fragments, bit for bit what sonet_channel_affine_act_out_bf16
  * would have stored; xs, xh [Cin].  Streaming-kernel shapes only (L % 8 == 0, B * ceil(L / 64) >= 2048): SONET_ERR_UNSUPPORTED otherwise. */
 extern "C" int sonet_wgrad_bf16_xaff(const uint16_t *g, const uint16_t *x, float *dw, void *ws, int B, int Cout, int Cin, int L,
                                      const float *xs, const float *xh, int xrelu, sonet_stream_t stream)
