@@ -305,7 +305,15 @@ int sonet_pointmlp_x3_bnb_acc_f32(const float *gy, const float *raw, int C, cons
 /* The same layer on bf16 MFMA with a 3-way bf16 split of both operands (6 MFMAs per product term set):
  * f32-class accuracy (classifier forward within 3e-6 * max(|ref|, rms) of the reference; tolerance 1e-5) at
  * 6/16 of the f32-MFMA cost.  Requires Cout % 32 == 0 and, with a second input, C1 % 16 == 0.
- * Wp3 = sonet_pointmlp_x3_pack_size(Cin, Cout) BYTES produced by sonet_pointmlp_x3_pack. */
+ * Wp3 = sonet_pointmlp_x3_pack_size(Cin, Cout) BYTES produced by sonet_pointmlp_x3_pack.
+ * Operand range: f32's exponent range less the width of the split -- the arithmetic stays within 0.5e-5 of float64 for operand
+ * magnitudes (x's rms; W's in units of sqrt(2 / Cin)) in [2^-102, 2^122] with sum |w||x| of an output in [2^-102, 2^127) (derived in
+ * tests/x3_model.py; docs/findings.md "x3 envelope").  The same holds for every launch in this arithmetic: sonet_pointmlp_x3_stats_f32,
+ * sonet_pointmlp_x3_bnb[_acc]_f32, sonet_wgrad_x3[_xaff]_f32.
+ * Non-finite operands: a NaN makes its output column (x) or row (W) NaN, as in f32.  An x3 launch turns a +-inf or |x| >= 3.3895e38
+ * (0x7F7F8000: bf16 rounding gives inf) INPUT into NaN for its whole output column, where f32 would hold +-inf or a finite value; the
+ * per-node arg-max pools skip NaN columns.  Such a WEIGHT is packed without the NaN: its output row is +-inf / NaN / finite as in f32.
+ * sonet_wgrad_x3[_xaff]_f32 splits both operands in its loop: such an element of g makes its row of dW NaN, one of x its column. */
 size_t sonet_pointmlp_x3_pack_size(int Cin, int Cout);
 int sonet_pointmlp_x3_pack(const float *W, void *Wp3, int Cin, int Cout, sonet_stream_t stream);
 int sonet_pointmlp_x3_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3,

@@ -9,6 +9,16 @@
 // i.e. f32-class accuracy at 6/16 of the f32-MFMA cost.  Against the reference's fixtures the whole
 // classifier forward stays within 3e-6 * max(|ref|, rms) (tolerance 1e-5); a 2-way split does not (4e-5).
 //
+// Operand range (derived by tests/x3_model.py ``derived_interval``, held by tests/test_x3_envelope_cpu.py and tests/test_gpu_x3_envelope.py;
+// docs/findings.md "x3 envelope"): the arithmetic stays within 0.5e-5 of float64 -- the other half of the 1e-5 is the f32 accumulation's --
+// for operands whose magnitude (x's rms; W's in units of its He scaling) lies in [2^-102, 2^122], with sum |w||x| of an output in
+// [2^-102, 2^127), whether the matrix cores keep or flush subnormal bf16 operands.  Below, the low pieces fall under 2^-126 (at 2^-104
+// the flushed model is at 6.8e-6, at 2^-106 at 1.5e-5); above, partial sums overflow.
+// Non-finite operands: NaN propagates to its output column (x) / row (W) as in f32.  A +-inf or finite |x| >= 0x7F7F8000 (3.3895e38, where
+// bf16 rounding gives inf) on the X side leaves split3_pair as h = inf, m = l = NaN: its whole output COLUMN is NaN where f32 holds +-inf
+// or a finite value (the hot loop is left alone; the per-node arg-max pools skip NaN columns).  On the W side the pack splits such values
+// without the NaN (split3_fix_w): the row comes out as in f32.
+//
 // Same data flow as the lean f32 kernel: W (pre-split, pre-packed in A-fragment order) goes through LDS in
 // stages shared by the 4 waves; X rows are raw-buffer loads (scalar row offsets, hardware zero fill past
 // the panel) prefetched one stage ahead as f32 and split in registers right before use:
@@ -42,6 +52,29 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, uns
     m = cvt_pk_bf16(r0, r1);
     const float q0 = r0 - __uint_as_float(m << 16), q1 = r1 - __uint_as_float(m & 0xFFFF0000u);
     l = cvt_pk_bf16(q0, q1);
+}
+
+// The WEIGHT side of the split (the pack kernels: not on a hot path).  split3_pair turns a value whose bf16 rounding is inf -- +-inf, and
+// the finite |w| >= 0x7F7F8000 (3.3895e38) -- into h = inf, m = l = NaN (inf - inf), and a NaN piece makes the whole output row NaN where
+// the f32 product holds +-inf or even a finite value.  Here instead:
+//   finite:  h = the largest finite bf16 of that sign (round towards zero); the residual then fits m and l exactly;
+//   +-inf:   h = m = 0, l = +-inf.  The l piece meets ONLY xh (the product Wl.xh), which has x's sign and is zero only where x is: the row
+//            comes out as inf * x does in f32 -- +-inf, NaN against a zero -- and no 0 * inf arises from the x pieces that happen to be zero.
+// Every other value goes through split3_pair unchanged (bit-identical packs).
+__device__ __forceinline__ void split3_fix_w(float w, unsigned &h, unsigned &m, unsigned &l) {       // one value's pieces in the low 16 bits
+    if ((h & 0x7FFFu) != 0x7F80u) return;
+    if (__builtin_isinf(w)) { l = h; h = 0u; m = 0u; return; }
+    h -= 1u;                                                                 // 0x7F80 -> 0x7F7F, sign kept
+    const float r = w - __uint_as_float(h << 16);
+    m = cvt_pk_bf16(r, 0.f) & 0xFFFFu;
+    l = cvt_pk_bf16(r - __uint_as_float(m << 16), 0.f) & 0xFFFFu;
+}
+__device__ __forceinline__ void split3_pair_w(float w0, float w1, unsigned &h, unsigned &m, unsigned &l) {
+    split3_pair(w0, w1, h, m, l);
+    unsigned h0 = h & 0xFFFFu, m0 = m & 0xFFFFu, l0 = l & 0xFFFFu, h1 = h >> 16, m1 = m >> 16, l1 = l >> 16;
+    split3_fix_w(w0, h0, m0, l0);
+    split3_fix_w(w1, h1, m1, l1);
+    h = h0 | (h1 << 16); m = m0 | (m1 << 16); l = l0 | (l1 << 16);
 }
 
 // fp16 flavour, B side: (x0, x1) -> 32 xh = fp16(32 x), fp16(32 x - 32 xh), xh = 32 xh * 2^-5 (packed pairs; exact residual)
@@ -94,7 +127,7 @@ __device__ __forceinline__ void x3_pack_body(const float *__restrict__ W, uint4 
             split16_w(w0, w1, hh, res);
             h[p] = hh; m[p] = 0u; l[p] = res;
         } else {
-            split3_pair(w0, w1, h[p], m[p], l[p]);
+            split3_pair_w(w0, w1, h[p], m[p], l[p]);
         }
     }
     if constexpr (F16) {

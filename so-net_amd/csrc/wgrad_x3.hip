@@ -28,6 +28,8 @@ constexpr int WG_BLK = 128;                                     // output block 
 constexpr int WG_UNIT = 32;                                     // columns per loop iteration = two MFMA steps
 
 // (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
+// (+-inf and finite |v| >= 0x7F7F8000 leave as h = inf, m = l = NaN: such an element of g makes its row of dW NaN, one of x its column --
+// include/sonet_hip.h, pinned by tests/test_gpu_x3_envelope.py)
 __device__ __forceinline__ void wg_split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
     h = cvt_pk_bf16(x0, x1);
     const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xFFFF0000u);
