@@ -32,6 +32,19 @@ int zero_words(void *p, size_t bytes, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+int cu_count(int least) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v >= least) return v;
+    return 256;
+}
+
+int check_layer_shape(const char *what, bool has_x2, int B, int C1, int C2, int Cout, int L, int also, int chunk) {
+    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0 && also > 0, "%s: non-positive size", what);
+    SONET_REQUIRE((C2 == 0) == !has_x2, "%s: x2 and C2 disagree", what);
+    SONET_REQUIRE(C2 == 0 || C1 % chunk == 0, "%s: with a second input C1=%d must be a multiple of %d", what, C1, chunk);
+    return SONET_OK;
+}
+
 static thread_local uint32_t *g_range_log = nullptr;
 uint32_t *range_log() { return g_range_log; }
 

@@ -44,6 +44,24 @@ static inline const char *knob(const char *name) { return getenv(name); }
 static inline const char *knob(const char *) { return nullptr; }
 #endif
 
+// integer knob: *out = atoi of the variable and true when it is set; never in the product build, where the caller's branch folds away
+static inline bool knob_int(const char *name, int *out) {
+    const char *e = knob(name);
+    if (e) *out = atoi(e);
+    return e != nullptr;
+}
+
+// Compute units of the current device, for the launchers that size a persistent grid or count rounds of workgroups: the attribute,
+// or 256 (an MI355X) when the query fails or reports fewer than `least`.  The launchers of the streaming bf16 kernels spread
+// cus / 8 column streams over the XCDs (least = 8); the others take any positive count (least = 1).  Asked per call, not cached.
+// Defined in api.hip.
+int cu_count(int least = 8);
+
+// What the layer launchers check first about their shapes, in this order (the first failing check is the message): positive sizes
+// (`also` = one more size that must be positive), x2 given exactly when C2 > 0, and C1 a multiple of the K chunk (`chunk` channels)
+// when a second panel follows it.  SONET_OK or the error.  Defined in api.hip.
+int check_layer_shape(const char *what, bool has_x2, int B, int C1, int C2, int Cout, int L, int also = 1, int chunk = 16);
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div64(long long a, long long b) { return (a + b - 1) / b; }
 
@@ -87,3 +105,12 @@ static inline int launch_lds_once(const char *what, dim3 grid, dim3 block, size_
 static inline int knn_stage_groups(int K) { const int g = 128 / K; return g > 16 ? 16 : g; }
 
 #include "device.hpp"                   // the device-side building blocks of the kernels
+
+// A runtime tile count as a compile-time constant: f(int_c<V>{}) for the V of the list that equals v, for the last one otherwise --
+// the `switch (MT)` of a launcher over its kernel instantiations, which are exactly the counts of the list.
+template <int V, int... Vs, typename F>
+static inline void with_int_c(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) f(int_c<V>{});
+    else if (v == V) f(int_c<V>{});
+    else with_int_c<Vs...>(v, f);
+}

@@ -604,9 +604,7 @@ extern "C" int sonet_pointmlp_f32(const float *x1, int C1, const float *x2, int 
 {
     const char *what = "sonet_pointmlp_f32";
     SONET_REQUIRE(x1 && Wp && scale && shift && y, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (x2 == nullptr), "%s: x2 and C2 disagree", what);
-    SONET_REQUIRE(C2 == 0 || C1 % 8 == 0, "%s: with a second input C1=%d must be a multiple of 8", what, C1);
+    if (const int rc = sonet::check_layer_shape(what, x2 != nullptr, B, C1, C2, Cout, L, 1, 8)) return rc;   // (K groups of 8 channels)
     const int Cin = C1 + C2;
     const int CT = sonet::ceil_div(Cout, 32), G = sonet::ceil_div(Cin, 8);
     const int gpc = sonet::ceil_div(L, 32);
@@ -623,10 +621,8 @@ extern "C" int sonet_pointmlp_f32(const float *x1, int C1, const float *x2, int 
     else if (CT % 2 == 0) MT = 2;
     if (MT == 2 || (MT == 4 && CT <= 8)) S = 2;
     if (G == 1) S = 1;
-    if (const char *e = sonet::knob("SONET_POINTMLP_MT")) {      // tuning knob (bench experiments only)
-        const int want = atoi(e);
-        if ((want == 8 || want == 6 || want == 4 || want == 2) && CT % want == 0) MT = want;
-    }
+    int want = 0;
+    if (sonet::knob_int("SONET_POINTMLP_MT", &want) && (want == 8 || want == 6 || want == 4 || want == 2) && CT % want == 0) MT = want;   // tuning knob (bench experiments only)
     if (nwg_x > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many points", what);
     // split the cout passes over gridDim.y when the point axis alone cannot fill the chip
     int ysplit = 1;
@@ -635,12 +631,9 @@ extern "C" int sonet_pointmlp_f32(const float *x1, int C1, const float *x2, int 
     const int ct_per_y = CT / ysplit;
     if (ct_per_y > 32) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d too large for one pass table", what, Cout);
     dim3 grid((unsigned)nwg_x, (unsigned)ysplit), block(PM_THREADS);
-    if (const char *e = sonet::knob("SONET_POINTMLP_S")) {       // tuning knob (bench experiments only)
-        const int want = atoi(e);
-        if (want == 1 || want == 2 || want == 4) S = want;
-    }
+    if (sonet::knob_int("SONET_POINTMLP_S", &want) && (want == 1 || want == 2 || want == 4)) S = want;   // tuning knob (bench experiments only)
     int abl = 0;
-    if (const char *e = sonet::knob("SONET_POINTMLP_ABLATE")) abl = atoi(e);   // bench-only: no stores / no X loads
+    sonet::knob_int("SONET_POINTMLP_ABLATE", &abl);              // bench-only: no stores / no X loads
 #define PM_ARGS grid, block, 0, st, x1, C1, x2, C2, Wp, scale, shift, relu, y, Cout, L, gpc, ngroups, CT, G, ct_per_y
 #ifdef SONET_VARIANTS
 #define PM_LAUNCH_V2(MM)                                                                              \

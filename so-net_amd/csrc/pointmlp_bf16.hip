@@ -944,18 +944,51 @@ extern "C" int sonet_pointmlp_bf16_pack_strided(const float *W, long long row_st
     return bf16_pack_impl("sonet_pointmlp_bf16_pack_strided", W, Wp, Cin, Cout, rows, row_stride, col_stride, stream);
 }
 
-static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uint16_t *x2, int C2, const void *Wp,
-                         const float *scale, const float *shift, int relu, uint16_t *y,
-                         int B, int Cout, int L, sonet_stream_t stream, const int32_t *gidx = nullptr, int L1 = 0,
-                         double *stats_ws = nullptr, float *mean = nullptr, float *var = nullptr, const BfrXaff *xaff = nullptr,
-                         const uint16_t *yadd = nullptr, const BfBnb *bnb = nullptr)
+// What both launches of pointmlp_bf16r_kernel -- the storing one of bf16_run_impl and the pooled one -- fill the same way: operands, shape,
+// slab split and the normalise-on-load table at byte xco_off of the dynamic LDS.  Everything else is zero; the caller adds its outputs,
+// nstream / ngroups and sync.
+static BfrArgs bfr_args(const uint16_t *x1, int C1, const uint16_t *x2, int C2, const void *Wp, const float *scale, const float *shift, int relu,
+                        int Cout, int L, int gpc, int KC, int tps, int nslab, const BfrXaff *xaff, size_t xco_off)
 {
-    if (!gidx) L1 = L;
+    BfrArgs a = {};
+    a.x1 = x1; a.x2 = x2; a.Wp = reinterpret_cast<const uint4 *>(Wp); a.scale = scale; a.shift = shift;
+    a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.L = L; a.gpc = gpc; a.relu = relu & 1; a.KC = KC; a.KC1 = C2 > 0 ? (C1 >> 4) : KC;
+    a.tps = tps; a.nslab = nslab;
+    if (xaff) {
+        a.xs1 = xaff->xs1; a.xh1 = xaff->xh1; a.xs2 = xaff->xs2; a.xh2 = xaff->xh2; a.xrelu = xaff->xrelu;
+        a.xco_off = (unsigned)xco_off;
+    }
+    return a;
+}
+
+/* One launch of the bf16 layer.  The first block is what every entry point passes; each line below it is an optional feature that stays
+ * off unless the entry point sets its fields. */
+struct BfRun {
+    const char *what;
+    const uint16_t *x1; int C1; const uint16_t *x2; int C2; const void *Wp; const float *scale, *shift; int relu; uint16_t *y;
+    int B, Cout, L; sonet_stream_t stream;
+    const int32_t *gidx = nullptr; int L1 = 0;                               // x1 [B][C1][L1] read through a per-column gather index
+    double *stats_ws = nullptr; float *mean = nullptr, *var = nullptr;       // batch statistics of the stored output from the epilogue
+    const BfrXaff *xaff = nullptr;                                           // normalise-on-load
+    const uint16_t *yadd = nullptr;                                          // accumulating store
+    const BfBnb *bnb = nullptr;                                              // BatchNorm-backward operand
+};
+
+static int bf16_run_impl(const BfRun &r)
+{
+    const char *what = r.what;
+    const uint16_t *x1 = r.x1, *x2 = r.x2, *yadd = r.yadd;
+    uint16_t *y = r.y;
+    const float *scale = r.scale, *shift = r.shift;
+    const int C1 = r.C1, C2 = r.C2, B = r.B, Cout = r.Cout, L = r.L, L1 = r.gidx ? r.L1 : r.L;
+    int relu = r.relu;
+    const int32_t *gidx = r.gidx;
+    double *stats_ws = r.stats_ws;
+    const BfrXaff *xaff = r.xaff;
+    const BfBnb *bnb = r.bnb;
     SONET_REQUIRE(L1 > 0, "%s: non-positive size", what);
-    SONET_REQUIRE(x1 && Wp && scale && shift && y, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (x2 == nullptr), "%s: x2 and C2 disagree", what);
-    SONET_REQUIRE(C2 == 0 || C1 % 16 == 0, "%s: with a second input C1=%d must be a multiple of 16", what, C1);
+    SONET_REQUIRE(x1 && r.Wp && scale && shift && y, "%s: NULL pointer", what);
+    if (const int rc = sonet::check_layer_shape(what, x2 != nullptr, B, C1, C2, Cout, L)) return rc;
     if (Cout % 32 != 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d must be a multiple of 32", what, Cout);
     const int Cin = C1 + C2;
     const int CT = Cout / 32, KC = sonet::ceil_div(Cin, 16);
@@ -975,17 +1008,11 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
     // three groups each on 256 CUs; two tiles per group doubles the workgroups that can run side by side
     if (MT == 4 && nwg_x * (CT / 4) < 256 && CT % 2 == 0) MT = 2;
     if (bnb && MT != 4 && MT != 2 && CT % 2 == 0) MT = 2;     // (the BatchNorm-backward load is instantiated for 4 and 2 tiles)
-    if (const char *e = sonet::knob("SONET_BF16_MT")) {            // tuning knob (bench experiments only)
-        const int want = atoi(e);
-        if ((want == 12 || want == 6 || want == 4 || want == 2 || want == 1) && CT % want == 0) MT = want;
-    }
-#ifdef SONET_VARIANTS
-    if (const char *e = sonet::knob("SONET_BF16_ABL")) relu = (relu & 1) | (atoi(e) << 1);
-#endif
-    if (const char *e = sonet::knob("SONET_BF16_S")) {
-        const int want = atoi(e);
-        if (want == 1 || want == 2) S = want;
-    }
+    int kv = 0;                                              // (a knob's value)
+    const bool mt_knob = sonet::knob_int("SONET_BF16_MT", &kv);   // tuning knob (bench experiments only)
+    if (mt_knob && (kv == 12 || kv == 6 || kv == 4 || kv == 2 || kv == 1) && CT % kv == 0) MT = kv;
+    if (sonet::knob_int("SONET_BF16_ABL", &kv)) relu = (relu & 1) | (kv << 1);
+    if (sonet::knob_int("SONET_BF16_S", &kv) && (kv == 1 || kv == 2)) S = kv;
     if (KC == 1) S = 1;
     // output-channel slabs: small launches spread the channels over workgroups too -- the smallest divisor d of the CT / MT groups
     // that gives >= 512 workgroups (and <= 32 tiles per slab), else the largest (round 2a: powers of two only, which left 768
@@ -993,16 +1020,16 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
     int ysplit = CT / MT;
     for (int d = CT / MT; d >= 1; --d)
         if ((CT / MT) % d == 0 && nwg_x * d >= 512 && CT / d <= 32) ysplit = d;
-    if (const char *e = sonet::knob("SONET_BF16_YSPLIT")) {
-        const int want = atoi(e);
-        if (want >= 1 && (CT / MT) % want == 0 && CT / want <= 32) ysplit = want;
-    }
+    if (sonet::knob_int("SONET_BF16_YSPLIT", &kv) && kv >= 1 && (CT / MT) % kv == 0 && CT / kv <= 32) ysplit = kv;
     const int ct_per_y = CT / ysplit;
     if (ct_per_y > 32) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d too large", what, Cout);
     const bool paired = (L % 2 == 0) && (L1 % 2 == 0) && gidx == nullptr &&
                         ((reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(y)) & 3) == 0;
-    hipStream_t st = sonet::as_stream(stream);
-    const uint4 *wp = reinterpret_cast<const uint4 *>(Wp);
+    hipStream_t st = sonet::as_stream(r.stream);
+    const uint4 *wp = reinterpret_cast<const uint4 *>(r.Wp);
+    const auto stats_finalize = [&](int nwg) {
+        if (stats_ws) sonet::launch_stats_finalize(stats_ws, nwg, Cout, 1.0 / ((double)B * L), r.mean, r.var, st);
+    };
 #ifdef SONET_VARIANTS   // (the X-in-registers kernel: bit-identical, measured slower; variants build only)
     // big launches with dword-aligned rows: X tile in registers, W by groups (above).  (KC, MT) pairs that are instantiated:
     // K chunks 1 / 4 / 8 / 16 / 20 / 24 with the tile count that keeps two W buffers inside the LDS
@@ -1013,14 +1040,11 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
         // measured SLOWER on every first-PointNet shape (0.54 vs 0.46 ms on 320 -> 384 at B = 64): one wave per SIMD, and the
         // 160 prefetch loads of the next tile pile up behind the 6-bit vmcnt during the last group.  Kept as the record of
         // the experiment and as the skeleton of the fused bf16 kernel (pointresnet_bf16.hip), where X never comes from HBM.
-        const char *e = sonet::knob("SONET_BF16_XREG");
-        const bool want = e && atoi(e) >= 1, force = e && atoi(e) == 2;
-        if (want && !stats_ws && paired && xmt > 0 && CT % xmt == 0 && Cout <= 1024 && (nwg_x >= 512 || force) && (sonet::knob("SONET_BF16_MT") == nullptr || force)) {
-            int dev = 0, cus = 256;
-            if (hipGetDevice(&dev) == hipSuccess) {
-                int v = 0;
-                if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-            }
+        int xreg = 0;
+        sonet::knob_int("SONET_BF16_XREG", &xreg);
+        const bool force = xreg == 2;
+        if (xreg >= 1 && !stats_ws && paired && xmt > 0 && CT % xmt == 0 && Cout <= 1024 && (nwg_x >= 512 || force) && (!mt_knob || force)) {
+            const int cus = sonet::cu_count(1);
             const int KC1x = C2 > 0 ? (C1 >> 4) : KC;
             const int Gx = CT / xmt;
             dim3 gridx((unsigned)(nwg_x < cus ? nwg_x : cus)), blockx(BF_THREADS);
@@ -1043,7 +1067,9 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
     {
         // (an accumulating store -- yadd -- runs on the staged kernel below: its epilogue loads would sit in the streaming kernel's hand-counted queue)
         bool want = paired && KC % 4 == 0 && CT % 2 == 0 && ngroups >= 8192 && ngroups < 0x7FFFFFFFll && yadd == nullptr && bnb == nullptr;
-        if (const char *e = sonet::knob("SONET_BF16_STREAM")) want = want && atoi(e) != 0;
+        int stream_knob = 1;
+        sonet::knob_int("SONET_BF16_STREAM", &stream_knob);
+        want = want && stream_knob != 0;
         int best_ns = 0, best_cost = 1 << 30;
         for (int ns = 1; want && ns <= CT / 2; ++ns) {
             if (CT % ns) continue;
@@ -1052,26 +1078,15 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
             const int cost = ns * (tps / (tps % 4 == 0 ? 4 : 2));            // times X goes through the vector memory path
             if (cost < best_cost) { best_cost = cost; best_ns = ns; }
         }
-        int cus = 256;
-        {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v >= 8) cus = v;
-        }
-        const int spx = best_ns > 0 ? (cus / 8) / best_ns : 0;            // column streams per XCD
+        const int spx = best_ns > 0 ? (sonet::cu_count() / 8) / best_ns : 0;            // column streams per XCD
         if (want && best_ns > 0 && spx > 0) {
-            BfrArgs a;
-            a.x1 = x1; a.x2 = x2; a.Wp = wp; a.scale = scale; a.shift = shift; a.y = y; a.stats_partial = stats_ws; a.abl = 0;
-            a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.L = L; a.gpc = gpc; a.relu = relu & 1; a.KC = KC; a.KC1 = C2 > 0 ? (C1 >> 4) : KC;
-            a.tps = CT / best_ns; a.nslab = best_ns; a.nstream = 8 * spx; a.ngroups = (int)ngroups;
+            const int tps = CT / best_ns;
+            const size_t lds_x = (size_t)tps * KC * 1024 + (size_t)tps * 32 * 8 + (stats_ws ? (size_t)8 * tps * 32 * 8 : 0);   // (the table of xaff follows)
+            const size_t lds = lds_x + (xaff ? (size_t)KC * 128 : 0);
+            BfrArgs a = bfr_args(x1, C1, x2, C2, r.Wp, scale, shift, relu, Cout, L, gpc, KC, tps, best_ns, xaff, lds_x);
+            a.y = y; a.stats_partial = stats_ws; a.nstream = 8 * spx; a.ngroups = (int)ngroups;
             a.sync = ((unsigned)L * 2u) % 128u != 0 ? 2 : 0;
-            if (const char *e = sonet::knob("SONET_BF16_SYNC")) a.sync = atoi(e);
-            size_t lds = (size_t)a.tps * KC * 1024 + (size_t)a.tps * 32 * 8 + (stats_ws ? (size_t)8 * a.tps * 32 * 8 : 0);
-            a.xs1 = a.xh1 = a.xs2 = a.xh2 = nullptr; a.xrelu = 0; a.xco_off = 0;
-            if (xaff) {
-                a.xs1 = xaff->xs1; a.xh1 = xaff->xh1; a.xs2 = xaff->xs2; a.xh2 = xaff->xh2; a.xrelu = xaff->xrelu;
-                a.xco_off = (unsigned)lds;
-                lds += (size_t)KC * 128;
-            }
+            sonet::knob_int("SONET_BF16_SYNC", &a.sync);
             const dim3 gridr((unsigned)(8 * spx * best_ns)), blockr(512);
 #define BFR_LAUNCH(MM, SS) do { if (const int rc_ = sonet::launch_lds_once<&pointmlp_bf16r_kernel<MM, SS>, 160 * 1024>(what, gridr, blockr, lds, st, a)) return rc_; } while (0)
 #define BFR_LAUNCH_X(MM) do { if (const int rc_ = sonet::launch_lds_once<&pointmlp_bf16r_kernel<MM, true, false, true>, 160 * 1024>(what, gridr, blockr, lds, st, a)) return rc_; } while (0)
@@ -1083,7 +1098,7 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
             else                     { if (stats_ws) BFR_LAUNCH(2, true); else BFR_LAUNCH(2, false); }
 #undef BFR_LAUNCH_X
 #undef BFR_LAUNCH
-            if (stats_ws) sonet::launch_stats_finalize(stats_ws, a.nstream, Cout, 1.0 / ((double)B * L), mean, var, st);
+            stats_finalize(a.nstream);
             return sonet::launched(what);
         }
     }
@@ -1100,34 +1115,26 @@ static int bf16_run_impl(const char *what, const uint16_t *x1, int C1, const uin
         else         hipLaunchKernelGGL((pointmlp_bf16_kernel<2, 2, true, 2, true>), BF_ARGS, *bnb);
         return sonet::launched(what);
     }
-#define BF_LAUNCH(MM) do { if (paired) { if (S == 2) hipLaunchKernelGGL((pointmlp_bf16_kernel<MM, 2, true>), BF_ARGS); \
-                                         else        hipLaunchKernelGGL((pointmlp_bf16_kernel<MM, 1, true>), BF_ARGS); } \
-                           else        { if (S == 2) hipLaunchKernelGGL((pointmlp_bf16_kernel<MM, 2, false>), BF_ARGS); \
-                                         else        hipLaunchKernelGGL((pointmlp_bf16_kernel<MM, 1, false>), BF_ARGS); } } while (0)
     if (MT == 12) S = 1;                                      // (12 slices per chunk already: one chunk per stage)
 #ifdef SONET_VARIANTS
     // X and W two stages ahead (NXB = 3): measured 1-5 % SLOWER than one stage ahead on every shape (profiles/r04s_bf16_layers_ablation.log
     // and docs/findings.md R4.8: the staged kernel is bound by the serialisation of a pass, not by its look-ahead) -- kept as the record
     // of the experiment, selectable in the variants build only
-    if (const char *e = sonet::knob("SONET_BF16_NXB")) {
-        if (atoi(e) == 3 && paired && S == 2 && (MT == 4 || MT == 2)) {
-            if (MT == 4) hipLaunchKernelGGL((pointmlp_bf16_kernel<4, 2, true, 3>), BF_ARGS);
-            else         hipLaunchKernelGGL((pointmlp_bf16_kernel<2, 2, true, 3>), BF_ARGS);
-            if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x, Cout, 1.0 / ((double)B * L), mean, var, st);
-            return sonet::launched(what);
-        }
+    if (sonet::knob_int("SONET_BF16_NXB", &kv) && kv == 3 && paired && S == 2 && (MT == 4 || MT == 2)) {
+        if (MT == 4) hipLaunchKernelGGL((pointmlp_bf16_kernel<4, 2, true, 3>), BF_ARGS);
+        else         hipLaunchKernelGGL((pointmlp_bf16_kernel<2, 2, true, 3>), BF_ARGS);
+        stats_finalize((int)nwg_x);
+        return sonet::launched(what);
     }
 #endif
-    switch (MT) {
-        case 12: BF_LAUNCH(12); break;
-        case 6: BF_LAUNCH(6); break;
-        case 4: BF_LAUNCH(4); break;
-        case 2: BF_LAUNCH(2); break;
-        default: BF_LAUNCH(1);
-    }
-#undef BF_LAUNCH
+    with_int_c<12, 6, 4, 2, 1>(MT, [&](auto m) {           // (MT as a compile-time constant; a count outside the list takes the last)
+        constexpr int M = decltype(m)::value;
+        if (paired) { if (S == 2) hipLaunchKernelGGL((pointmlp_bf16_kernel<M, 2, true>), BF_ARGS);
+                      else        hipLaunchKernelGGL((pointmlp_bf16_kernel<M, 1, true>), BF_ARGS); }
+        else        { if (S == 2) hipLaunchKernelGGL((pointmlp_bf16_kernel<M, 2, false>), BF_ARGS);
+                      else        hipLaunchKernelGGL((pointmlp_bf16_kernel<M, 1, false>), BF_ARGS); } });
 #undef BF_ARGS
-    if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x, Cout, 1.0 / ((double)B * L), mean, var, st);
+    stats_finalize((int)nwg_x);
     return sonet::launched(what);
 }
 
@@ -1144,8 +1151,9 @@ extern "C" int sonet_pointmlp_bf16_stats(const uint16_t *x1, int C1, const uint1
                                          int B, int Cout, int L, void *stats_ws, float *mean, float *var, sonet_stream_t stream)
 {
     SONET_REQUIRE(stats_ws && mean && var, "sonet_pointmlp_bf16_stats: NULL pointer");
-    return bf16_run_impl("sonet_pointmlp_bf16_stats", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                         reinterpret_cast<double *>(stats_ws), mean, var);
+    BfRun r{"sonet_pointmlp_bf16_stats", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream};
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
+    return bf16_run_impl(r);
 }
 
 /* sonet_pointmlp_bf16_stats with NORMALISE-ON-LOAD (bf16 training forward, hidden layers of the first PointNet): x1 / x2 hold the RAW outputs
@@ -1162,8 +1170,10 @@ extern "C" int sonet_pointmlp_bf16_stats_xaff(const uint16_t *x1, int C1, const 
     const char *what = "sonet_pointmlp_bf16_stats_xaff";
     SONET_REQUIRE(stats_ws && mean && var && xs1 && xh1 && (C2 == 0 || (xs2 && xh2)), "%s: NULL pointer", what);
     const BfrXaff xa = {xs1, xh1, xs2, xh2, xrelu};
-    return bf16_run_impl(what, x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                         reinterpret_cast<double *>(stats_ws), mean, var, &xa);
+    BfRun r{what, x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream};
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
+    r.xaff = &xa;
+    return bf16_run_impl(r);
 }
 
 /* The layer and the per-node arg-max pool of its output in ONE launch; the output itself is never written (the last layer of the first
@@ -1178,9 +1188,7 @@ static int bf16_pool_impl(const char *what, const uint16_t *x1, int C1, const ui
                           int32_t *out_idx, float *out_val, int B, int Cout, int L, int M, sonet_stream_t stream, const BfrXaff *xaff)
 {
     SONET_REQUIRE(x1 && Wp && scale && shift && ids && out_idx && out_val, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0 && M > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (x2 == nullptr), "%s: x2 and C2 disagree", what);
-    SONET_REQUIRE(C2 == 0 || C1 % 16 == 0, "%s: with a second input C1=%d must be a multiple of 16", what, C1);
+    if (const int rc = sonet::check_layer_shape(what, x2 != nullptr, B, C1, C2, Cout, L, M)) return rc;
     const int Cin = C1 + C2;
     if (Cout % 32 != 0 || Cin % 64 != 0 || L % 2 != 0 || L > 65534 || M > 255 || B > 65535 ||
         ((reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2)) & 3) != 0)
@@ -1188,56 +1196,39 @@ static int bf16_pool_impl(const char *what, const uint16_t *x1, int C1, const ui
     const int CT = Cout / 32, KC = Cin / 16, gpc = sonet::ceil_div(L, 64);
     if ((double)C1 * L * 2.0 >= 2.0e9 || (double)C2 * L * 2.0 >= 2.0e9 || (long long)B * gpc >= 0x7FFFFFFFll)
         return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: a per-cloud panel is too large", what);
-    int cus = 256;
-    {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v >= 8) cus = v;
-    }
-    // output slabs: one workgroup per (cloud, slab) and CU -- the slab count whose B x nslab workgroups need the fewest rounds of tile passes
-    int best_ns = 0, best_mt = 0;
-    long long best_cost = 0;
-    size_t best_lds = 0;
-    for (int ns = 1; ns <= CT; ++ns) {
-        if (CT % ns) continue;
+    const int cus = sonet::cu_count();
+    // a slab count's tile shape and LDS budget (W slab, affine, bins, first values, the cloud's node ids, then the normalise-on-load table);
+    // false when it does not divide the tiles, leaves no tile count or does not fit
+    const auto slab_fits = [&](int ns, int *mt, size_t *lds) {
+        if (ns < 1 || CT % ns) return false;
         const int tps = CT / ns;
-        const int mt = tps % 4 == 0 ? 4 : tps % 3 == 0 ? 3 : tps % 2 == 0 ? 2 : 0;
-        if (mt == 0) continue;
-        const size_t lds = (size_t)tps * KC * 1024 + (size_t)tps * 32 * 8 + (size_t)tps * 32 * M * 8 + (size_t)tps * 32 * 4 + (size_t)((L + 15) & ~15)
-                           + (xaff ? (size_t)KC * 128 : 0);
-        if (lds > 158 * 1024) continue;
-        const long long cost = sonet::ceil_div64((long long)B * ns, cus) * tps;
+        *mt = tps % 4 == 0 ? 4 : tps % 3 == 0 ? 3 : tps % 2 == 0 ? 2 : 0;
+        *lds = (size_t)tps * KC * 1024 + (size_t)tps * 32 * 8 + (size_t)tps * 32 * M * 8 + (size_t)tps * 32 * 4 + (size_t)((L + 15) & ~15)
+               + (xaff ? (size_t)KC * 128 : 0);
+        return *mt != 0 && *lds <= 158 * 1024;
+    };
+    // output slabs: one workgroup per (cloud, slab) and CU -- the slab count whose B x nslab workgroups need the fewest rounds of tile passes
+    int best_ns = 0, best_mt = 0, mt = 0;
+    long long best_cost = 0;
+    size_t best_lds = 0, lds = 0;
+    for (int ns = 1; ns <= CT; ++ns) {
+        if (!slab_fits(ns, &mt, &lds)) continue;
+        const long long cost = sonet::ceil_div64((long long)B * ns, cus) * (CT / ns);
         if (best_ns == 0 || cost < best_cost) { best_ns = ns; best_mt = mt; best_cost = cost; best_lds = lds; }
     }
-#ifdef SONET_VARIANTS
-    if (const char *e = sonet::knob("SONET_BF16_POOL_NS")) {       // (tools/bench_pool_epilogue.py: a slab count by hand)
-        const int ns = atoi(e);
-        if (ns >= 1 && CT % ns == 0) {
-            const int tps = CT / ns, mt = tps % 4 == 0 ? 4 : tps % 3 == 0 ? 3 : tps % 2 == 0 ? 2 : 0;
-            const size_t lds = (size_t)tps * KC * 1024 + (size_t)tps * 32 * 8 + (size_t)tps * 32 * M * 8 + (size_t)tps * 32 * 4 + (size_t)((L + 15) & ~15)
-                               + (xaff ? (size_t)KC * 128 : 0);
-            if (mt && lds <= 158 * 1024) { best_ns = ns; best_mt = mt; best_lds = lds; }
-        }
-    }
-#endif
+    int ns_knob = 0;                                              // (tools/bench_pool_epilogue.py: a slab count by hand)
+    if (sonet::knob_int("SONET_BF16_POOL_NS", &ns_knob) && slab_fits(ns_knob, &mt, &lds)) { best_ns = ns_knob; best_mt = mt; best_lds = lds; }
     if (best_ns == 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: no slab shape fits the LDS (Cin=%d Cout=%d M=%d L=%d)", what, Cin, Cout, M, L);
-    BfrArgs a;
-    a.x1 = x1; a.x2 = x2; a.Wp = reinterpret_cast<const uint4 *>(Wp); a.scale = scale; a.shift = shift; a.y = nullptr; a.stats_partial = nullptr;
-    a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.L = L; a.gpc = gpc; a.relu = relu & 1; a.KC = KC; a.KC1 = C2 > 0 ? (C1 >> 4) : KC;
-    a.tps = CT / best_ns; a.nslab = best_ns; a.nstream = (B + 7) / 8 * 8; a.ngroups = B * gpc;
+    // (the table is the last item of the slab's LDS budget)
+    BfrArgs a = bfr_args(x1, C1, x2, C2, Wp, scale, shift, relu, Cout, L, gpc, KC, CT / best_ns, best_ns, xaff, best_lds - (size_t)KC * 128);
+    a.nstream = (B + 7) / 8 * 8; a.ngroups = B * gpc;
     // (no workgroup barriers here: the eight waves of a workgroup walk adjacent column groups of ONE cloud and its four slab workgroups share
     //  an XCD's L2 -- the shared cache lines of unaligned rows come from L2 either way, and free-running waves let one wave's epilogue sit
     //  under another's MFMAs: 559 -> 478 us at 64 x 15000 columns, tools/bench_pool_epilogue.py)
     a.sync = 0;
-    a.ids = ids; a.row_max = row_max; a.out_idx = out_idx; a.out_val = out_val; a.M = M; a.abl = 0;
-    a.xs1 = a.xh1 = a.xs2 = a.xh2 = nullptr; a.xrelu = 0; a.xco_off = 0;
-    if (xaff) {
-        a.xs1 = xaff->xs1; a.xh1 = xaff->xh1; a.xs2 = xaff->xs2; a.xh2 = xaff->xh2; a.xrelu = xaff->xrelu;
-        a.xco_off = (unsigned)(best_lds - (size_t)KC * 128);             // (the table is the last item of the slab's LDS budget)
-    }
-#ifdef SONET_VARIANTS
-    if (const char *e = sonet::knob("SONET_BF16_POOL_ABL")) a.abl = atoi(e);
-    if (const char *e = sonet::knob("SONET_BF16_SYNC")) a.sync = atoi(e);
-#endif
+    a.ids = ids; a.row_max = row_max; a.out_idx = out_idx; a.out_val = out_val; a.M = M;
+    sonet::knob_int("SONET_BF16_POOL_ABL", &a.abl);
+    sonet::knob_int("SONET_BF16_SYNC", &a.sync);
     hipStream_t st = sonet::as_stream(stream);
     // (workgroup -> (slab, stream) as in the storing launch: the slabs of a cloud on one XCD; streams >= B leave at once)
     const dim3 gridr((unsigned)(a.nstream * best_ns)), blockr(512);
@@ -1276,7 +1267,7 @@ extern "C" int sonet_pointmlp_bf16(const uint16_t *x1, int C1, const uint16_t *x
                                    const float *scale, const float *shift, int relu, uint16_t *y,
                                    int B, int Cout, int L, sonet_stream_t stream)
 {
-    return bf16_run_impl("sonet_pointmlp_bf16", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream);
+    return bf16_run_impl(BfRun{"sonet_pointmlp_bf16", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream});
 }
 
 /* sonet_pointmlp_bf16 with an ACCUMULATING store: y = bf16(float(bf16(result)) + float(yadd)), yadd [B][Cout][L] bf16 -- another gradient of the
@@ -1289,8 +1280,9 @@ extern "C" int sonet_pointmlp_bf16_acc(const uint16_t *x1, int C1, const uint16_
 {
     SONET_REQUIRE(yadd, "sonet_pointmlp_bf16_acc: NULL pointer");
     if ((reinterpret_cast<uintptr_t>(yadd) & 3) != 0) return sonet::fail(SONET_ERR_INVALID_ARG, "sonet_pointmlp_bf16_acc: yadd must be 4-byte aligned");
-    return bf16_run_impl("sonet_pointmlp_bf16_acc", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0, nullptr, nullptr, nullptr,
-                         nullptr, yadd);
+    BfRun r{"sonet_pointmlp_bf16_acc", x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream};
+    r.yadd = yadd;
+    return bf16_run_impl(r);
 }
 
 /* The input gradient of a bf16 layer behind a training-mode BatchNorm (+ ReLU) with the BatchNorm / ReLU backward applied by the operand load
@@ -1309,7 +1301,9 @@ extern "C" int sonet_pointmlp_bf16_bnb(const uint16_t *gy, const uint16_t *raw, 
     if (yadd && (reinterpret_cast<uintptr_t>(yadd) & 3) != 0) return sonet::fail(SONET_ERR_INVALID_ARG, "%s: yadd must be 4-byte aligned", what);
     if (C < 32) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: C=%d < 32", what, C);
     const BfBnb bn = {raw, a, b, c0, sc, sh, g_raw_out, relu};
-    return bf16_run_impl(what, gy, C, nullptr, 0, Wp, scale, shift, 0, y, B, Cout, L, stream, nullptr, 0, nullptr, nullptr, nullptr, nullptr, yadd, &bn);
+    BfRun r{what, gy, C, /* x2, C2 */ nullptr, 0, Wp, scale, shift, /* relu */ 0, y, B, Cout, L, stream};
+    r.yadd = yadd; r.bnb = &bn;
+    return bf16_run_impl(r);
 }
 
 extern "C" int sonet_pointmlp_bf16_gather(const uint16_t *x1, int C1, int L1, const int32_t *gidx, const uint16_t *x2, int C2, const void *Wp,
@@ -1318,5 +1312,7 @@ extern "C" int sonet_pointmlp_bf16_gather(const uint16_t *x1, int C1, int L1, co
 {
     const char *what = "sonet_pointmlp_bf16_gather";
     SONET_REQUIRE(gidx, "%s: NULL pointer", what);
-    return bf16_run_impl(what, x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream, gidx, L1);
+    BfRun r{what, x1, C1, x2, C2, Wp, scale, shift, relu, y, B, Cout, L, stream};
+    r.gidx = gidx; r.L1 = L1;
+    return bf16_run_impl(r);
 }

@@ -833,9 +833,7 @@ static int h3p_launch(const char *what, const void *x1p, int C1, int L1, const i
 {
     if (!gidx) L1 = L;
     SONET_REQUIRE(x1p && Wp && scale && shift && (y || yp), "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0 && L1 > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (x2p == nullptr), "%s: x2 and C2 disagree", what);
-    SONET_REQUIRE(C2 == 0 || C1 % 16 == 0, "%s: with a second input C1=%d must be a multiple of 16", what, C1);
+    if (const int rc = sonet::check_layer_shape(what, x2p != nullptr, B, C1, C2, Cout, L, L1)) return rc;
     SONET_REQUIRE((zadd == nullptr) == (zidx == nullptr) && (!zadd || ZM > 0), "%s: zadd, zidx and ZM come together", what);
     SONET_REQUIRE(!stats_ws || (y && !yp && mean && var && !zadd), "%s: the statistics epilogue needs y (only), mean, var and no addend", what);
     if (Cout % 32 != 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d must be a multiple of 32", what, Cout);
@@ -867,10 +865,8 @@ static int h3p_launch(const char *what, const void *x1p, int C1, int L1, const i
     for (int d = 1; d <= groups; ++d)
         if (groups % d == 0 && (d <= 4 || cols < 131072 || CT / nslab > (zadd ? 16 : 32))) nslab = d;
 #ifdef SONET_VARIANTS
-    if (const char *e = sonet::knob("SONET_H3P_NSLAB")) {
-        const int want = atoi(e);
-        if (want >= 1 && groups % want == 0 && CT / want <= 32) nslab = want;
-    }
+    int want = 0;
+    if (sonet::knob_int("SONET_H3P_NSLAB", &want) && want >= 1 && groups % want == 0 && CT / want <= 32) nslab = want;
 #endif
     const long long nwg = sonet::ceil_div64(ncol, 8) * 8 * nslab;
     if (nwg > 0x7FFFFFFFll || ncol > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many points", what);
@@ -881,7 +877,7 @@ static int h3p_launch(const char *what, const void *x1p, int C1, int L1, const i
     a.rlog = sonet::range_log(); a.stats_partial = reinterpret_cast<double *>(stats_ws); a.ngroups = ngroups;
     a.prof = nullptr; a.abl = 0;
 #ifdef SONET_VARIANTS
-    if (const char *e = sonet::knob("SONET_H3P_ABL")) a.abl = atoi(e);
+    sonet::knob_int("SONET_H3P_ABL", &a.abl);
     if (const char *e = sonet::knob("SONET_H3P_PROF")) a.prof = reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0));   // device address of 5 u64 counters
 #endif
     a.KC1 = KC1; a.KC2 = KC2; a.L1 = L1; a.L = L; a.Cout = Cout; a.CT = CT; a.KC = KC; a.KCr = KCr; a.KCP = KCP; a.ct_per_y = CT / nslab;

@@ -1200,16 +1200,36 @@ extern "C" int sonet_pack_multi_kc(int flavour, int Cin)
     return flavour == 2 ? sonet::ceil_div(Cin, 16 * H3_KPAD) * H3_KPAD : sonet::ceil_div(Cin, 16);
 }
 
-static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, const float *x2, int C2, const void *Wp3,
-                       const float *scale, const float *shift, int relu, float *y,
-                       int B, int Cout, int L, sonet_stream_t stream, const int32_t *gidx = nullptr, int L1 = 0,
-                       double *stats_ws = nullptr, float *mean = nullptr, float *var = nullptr,
-                       const float *zadd = nullptr, const int32_t *zidx = nullptr, int ZM = 0, unsigned *kmax = nullptr, int KM = 0,
-                       const SegPoolArgs *segpool = nullptr, const XAffArgs *xaff = nullptr, const BnbArgs *bnbp = nullptr, double *bnb_psums = nullptr)
+/* One launch of the bf16-split (f16 = false) or fp16-split layer.  The first block is what every entry point passes; each line below it
+ * is an optional feature that stays off unless the entry point sets its fields. */
+struct X3Run {
+    const char *what; bool f16;
+    const float *x1; int C1; const float *x2; int C2; const void *Wp3; const float *scale, *shift; int relu; float *y;
+    int B, Cout, L; sonet_stream_t stream;
+    const int32_t *gidx = nullptr; int L1 = 0;                               // x1 [B][C1][L1] read through a per-column gather index
+    double *stats_ws = nullptr; float *mean = nullptr, *var = nullptr;       // batch statistics of y from the epilogue
+    const float *zadd = nullptr; const int32_t *zidx = nullptr; int ZM = 0;  // per-node addend gathered in the epilogue
+    unsigned *kmax = nullptr; int KM = 0;                                    // max-reduced keys instead of y (variants build)
+    const SegPoolArgs *segpool = nullptr;                                    // per-node arg-max pool instead of y
+    const XAffArgs *xaff = nullptr;                                          // normalise-on-load
+    const BnbArgs *bnb = nullptr; double *psums = nullptr;                   // BatchNorm-backward operand (+ the sums of the layer below)
+};
+
+static int x3_run_impl(const X3Run &r)
 {
-    if (!gidx) L1 = L;
+    const char *what = r.what;
+    const bool f16 = r.f16;
+    const float *x1 = r.x1, *x2 = r.x2, *scale = r.scale, *shift = r.shift, *zadd = r.zadd;
+    float *y = r.y;
+    const int C1 = r.C1, C2 = r.C2, relu = r.relu, B = r.B, Cout = r.Cout, L = r.L, ZM = r.ZM, KM = r.KM, L1 = r.gidx ? r.L1 : r.L;
+    const int32_t *gidx = r.gidx, *zidx = r.zidx;
+    double *stats_ws = r.stats_ws;
+    unsigned *kmax = r.kmax;
+    const SegPoolArgs *segpool = r.segpool;
+    const XAffArgs *xaff = r.xaff;
+    const BnbArgs *bnbp = r.bnb;
     SONET_REQUIRE(L1 > 0, "%s: non-positive size", what);
-    SONET_REQUIRE(x1 && Wp3 && scale && shift && (y || kmax || segpool), "%s: NULL pointer", what);
+    SONET_REQUIRE(x1 && r.Wp3 && scale && shift && (y || kmax || segpool), "%s: NULL pointer", what);
     SONET_REQUIRE(!segpool || (f16 && !gidx && !stats_ws && !zadd && !kmax), "%s: the pooled form takes the plain fp16-split layer only", what);
     const SegPoolArgs sp = segpool ? *segpool : SegPoolArgs{nullptr, nullptr, nullptr, nullptr, 0};
     SONET_REQUIRE(!xaff || (f16 && !gidx && !zadd && !kmax && xaff->s1 && xaff->h1 && ((C2 == 0) || (xaff->s2 && xaff->h2))),
@@ -1219,13 +1239,11 @@ static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, cons
     SONET_REQUIRE(!bnbp || (!f16 && !gidx && !zadd && !kmax && !segpool && !xaff && !stats_ws && C2 == 0 && bnbp->raw && bnbp->a && bnbp->b && bnbp->c0
                             && bnbp->sc && bnbp->sh), "%s: the BatchNorm-backward operand takes the plain bf16-split layer with one input panel", what);
     if (bnbp && C1 > 512) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: the BatchNorm-backward operand needs <= 512 input channels", what);
-    SONET_REQUIRE(!bnbp || ((bnbp->praw == nullptr) == (bnbp->pstats == nullptr) && (bnbp->pstats == nullptr) == (bnb_psums == nullptr) &&
+    SONET_REQUIRE(!bnbp || ((bnbp->praw == nullptr) == (bnbp->pstats == nullptr) && (bnbp->pstats == nullptr) == (r.psums == nullptr) &&
                             (!bnbp->praw || (bnbp->psc && bnbp->psh))), "%s: the sums of the layer below need praw, psc, psh, a workspace and the output", what);
     SONET_REQUIRE(!bnbp || !bnbp->yadd || !bnbp->pstats, "%s: an accumulated output and the sums of the layer below do not combine", what);
     const BnbArgs bnb = bnbp ? *bnbp : BnbArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-    SONET_REQUIRE(B > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && L > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (x2 == nullptr), "%s: x2 and C2 disagree", what);
-    SONET_REQUIRE(C2 == 0 || C1 % 16 == 0, "%s: with a second input C1=%d must be a multiple of 16", what, C1);
+    if (const int rc = sonet::check_layer_shape(what, x2 != nullptr, B, C1, C2, Cout, L)) return rc;
     if (Cout % 32 != 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d must be a multiple of 32", what, Cout);
     const int Cin = C1 + C2;
     const int CT = Cout / 32, KC = sonet::ceil_div(Cin, 16);
@@ -1236,10 +1254,12 @@ static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, cons
         return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: a per-cloud panel exceeds 4 GiB", what);
     const long long nwg_x = sonet::ceil_div64(ngroups, (long long)X3_WAVES);
     if (nwg_x > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many points", what);
-    hipStream_t st = sonet::as_stream(stream);
-    const uint4 *wp = reinterpret_cast<const uint4 *>(Wp3);
+    hipStream_t st = sonet::as_stream(r.stream);
+    const uint4 *wp = reinterpret_cast<const uint4 *>(r.Wp3);
     unsigned *rlog = f16 ? sonet::range_log() : nullptr;
-    const char *eg = sonet::knob("SONET_POINTMLP_H3R");          // bench-only: 0 = the first-generation pipeline
+    const auto stats_finalize = [&](long long nwg) {
+        if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg, Cout, 1.0 / ((double)B * L), r.mean, r.var, st);
+    };
     // second-generation pipeline where it measures faster (profiles/r02y_pointmlp_h3r.log, r02zd): inputs that stay in the 256 MB
     // MALL across the CT / 4 passes over X, and point-level inputs whenever the first generation would also run 4-tile groups (CT
     // not a multiple of 6: 1024 -> 512 at 64 x 3072 columns 0.62 vs 0.78 ms).  With 6-tile groups (two passes for 384 channels
@@ -1249,71 +1269,44 @@ static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, cons
     const bool h3r_pick = h3r_fits || (CT % 6 != 0 && Cin >= 512 && (long long)B * L >= 256);
     // (the per-node addend form measured better on the first generation: 0.86 vs 0.98 ms for 393 -> 1024 at 64 x 3072 columns)
     if (kmax && !(f16 && CT % H3R_MT == 0)) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: the max-reduced form needs Cout %% 128 == 0", what);
+    int NC = 0;                                                  // column tiles per wave of the second-generation launch; 0: the staged kernels below
 #ifdef SONET_VARIANTS
     // Two column tiles per wave (NC = 2), variants build only (SONET_POINTMLP_NC=2; tools/bench_h3w.py): bit-identical, and measured
     // 2 % faster on the two K >= 512 segmenter layers but 3-18 % SLOWER everywhere else (profiles/r03b_pointmlp_two_tiles.log) -- the
     // per-layer kernel is bound by its X stream, where two waves per SIMD hide more than the halved weight stream saves.
-    const char *enc = sonet::knob("SONET_POINTMLP_NC");
-    const bool wide = enc && atoi(enc) == 2 && f16 && CT % H3R_MT == 0 && !gidx && !kmax && (L % 2 == 0);
-    if (wide) {
-        const int gpc2 = sonet::ceil_div(L, 64);
-        const long long ngroups2 = (long long)B * gpc2, nwg_x2 = sonet::ceil_div64(ngroups2, (long long)X3_WAVES);
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-        // output-channel slabs: as below, with one workgroup per CU
-        const int groups = CT / H3R_MT;
-        int best = 0;
-        long long best_cost = 0;
-        for (int d = 1; d <= groups; ++d) {
-            if (groups % d != 0 || CT / d > 32) continue;
-            const long long cost = sonet::ceil_div64(nwg_x2 * d, (long long)cus) * (groups / d);
-            if (best == 0 || cost <= best_cost) { best = d; best_cost = cost; }
-        }
-        if (const char *e = sonet::knob("SONET_POINTMLP_YSPLIT")) {
-            const int want = atoi(e);
-            if (want >= 1 && groups % want == 0 && CT / want <= 32) best = want;
-        }
-        if (best == 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d too large", what, Cout);
-        const long long nwg = sonet::ceil_div64(nwg_x2, 8) * 8 * best;
-        if (nwg > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many points", what);
-        hipLaunchKernelGGL(pointmlp_h3r_kernel<2>, dim3((unsigned)nwg), dim3(X3_THREADS), 0, st,
-                           x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc2, ngroups2, CT, KC, CT / best, gidx, L1, rlog, KCP, best, (int)nwg_x2,
-                           zadd, zidx, ZM, kmax, KM, stats_ws);
-        if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x2, Cout, 1.0 / ((double)B * L), mean, var, st);
-        return sonet::launched(what);
-    }
+    int want_nc = 0;
+    if (sonet::knob_int("SONET_POINTMLP_NC", &want_nc) && want_nc == 2 && f16 && CT % H3R_MT == 0 && !gidx && !kmax && (L % 2 == 0)) NC = 2;
 #endif
-    if (!segpool && !xaff && f16 && CT % H3R_MT == 0 && (kmax || (eg ? atoi(eg) != 0 : (h3r_pick && !zadd)))) {
-        // output-channel slabs: the divisor d of the CT / 4 tile groups that needs the fewest rounds of (2 workgroups per CU)
-        // x (groups per workgroup); ties go to the larger d (shorter workgroups)
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
+    int h3r = h3r_pick && !zadd;
+    sonet::knob_int("SONET_POINTMLP_H3R", &h3r);                 // bench-only: 0 = the first-generation pipeline
+    if (NC == 0 && !segpool && !xaff && f16 && CT % H3R_MT == 0 && (kmax || h3r != 0)) NC = 1;
+    if (NC != 0) {
+        const int gpc_n = sonet::ceil_div(L, 32 * NC);
+        const long long ngroups_n = (long long)B * gpc_n, nwg_n = sonet::ceil_div64(ngroups_n, (long long)X3_WAVES);
+        // output-channel slabs: the divisor d of the CT / 4 tile groups that needs the fewest rounds of (2 workgroups per CU; one with
+        // two column tiles per wave) x (groups per workgroup); ties go to the larger d (shorter workgroups)
         const int groups = CT / H3R_MT;
-        const long long slots = 2ll * cus;
+        const long long slots = (long long)(NC == 1 ? 2 : 1) * sonet::cu_count(1);
         int best = 0;
         long long best_cost = 0;
         for (int d = 1; d <= groups; ++d) {
             if (groups % d != 0 || CT / d > 32) continue;
-            const long long cost = sonet::ceil_div64(nwg_x * d, slots) * (groups / d);
+            const long long cost = sonet::ceil_div64(nwg_n * d, slots) * (groups / d);
             if (best == 0 || cost <= best_cost) { best = d; best_cost = cost; }
         }
-        if (const char *e = sonet::knob("SONET_POINTMLP_YSPLIT")) {
-            const int want = atoi(e);
-            if (want >= 1 && groups % want == 0 && CT / want <= 32) best = want;
-        }
+        int want = 0;
+        if (sonet::knob_int("SONET_POINTMLP_YSPLIT", &want) && want >= 1 && groups % want == 0 && CT / want <= 32) best = want;
         if (best == 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d too large", what, Cout);
-        const long long nwg = sonet::ceil_div64(nwg_x, 8) * 8 * best;
+        const long long nwg = sonet::ceil_div64(nwg_n, 8) * 8 * best;
         if (nwg > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many points", what);
-        hipLaunchKernelGGL(pointmlp_h3r_kernel<1>, dim3((unsigned)nwg), dim3(X3_THREADS), 0, st,
-                           x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc, ngroups, CT, KC, CT / best, gidx, L1, rlog, KCP, best, (int)nwg_x,
-                           zadd, zidx, ZM, kmax, KM, stats_ws);
-        if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x, Cout, 1.0 / ((double)B * L), mean, var, st);
+#define H3R_ARGS dim3((unsigned)nwg), dim3(X3_THREADS), 0, st, x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc_n, ngroups_n, CT, KC, CT / best, \
+                 gidx, L1, rlog, KCP, best, (int)nwg_n, zadd, zidx, ZM, kmax, KM, stats_ws
+#ifdef SONET_VARIANTS
+        if (NC == 2) hipLaunchKernelGGL(pointmlp_h3r_kernel<2>, H3R_ARGS); else
+#endif
+        hipLaunchKernelGGL(pointmlp_h3r_kernel<1>, H3R_ARGS);
+#undef H3R_ARGS
+        stats_finalize(nwg_n);
         return sonet::launched(what);
     }
     int MT = 1, S = 1;
@@ -1323,14 +1316,10 @@ static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, cons
     if (CT % 6 == 0) MT = 6;
     else if (CT % 4 == 0 && !(nwg_x < 64)) MT = 4;
     else if (CT % 2 == 0) MT = 2;
-    if (const char *e = sonet::knob("SONET_POINTMLP_MT")) {      // tuning knob (bench experiments only)
-        const int want = atoi(e);
-        if ((want == 6 || want == 4 || want == 2 || want == 1) && CT % want == 0) MT = want;
-    }
-    if (const char *e = sonet::knob("SONET_POINTMLP_S")) {
-        const int want = atoi(e);
-        if (want == 1 || want == 2) S = want;
-    }
+    int want = 0;
+    const bool mt_knob = sonet::knob_int("SONET_POINTMLP_MT", &want);      // tuning knob (bench experiments only)
+    if (mt_knob && (want == 6 || want == 4 || want == 2 || want == 1) && CT % want == 0) MT = want;
+    if (sonet::knob_int("SONET_POINTMLP_S", &want) && (want == 1 || want == 2)) S = want;
     if (KC == 1) S = 1;
     if (xaff && MT != 6) MT = 4;
     // output-channel slabs per column group: the smallest divisor of the CT / MT tile groups that fills the chip (>= 1024 workgroups) --
@@ -1347,68 +1336,46 @@ static int x3_run_impl(const char *what, bool f16, const float *x1, int C1, cons
         }
         if (best > 0) ysplit = best;
     }
-    if (const char *e = sonet::knob("SONET_POINTMLP_YSPLIT")) {  // tuning knob (bench experiments only): output-channel slabs per column group.
-        const int want = atoi(e);                           // 1152 workgroups on 768 resident slots run 1.5 rounds; 2 slabs of half the work
-        if (want >= 1 && (CT / MT) % want == 0 && CT / want <= 32) ysplit = want;   // each would run 3 rounds of half the length (X re-read twice)
-    }
+    // tuning knob (bench experiments only): output-channel slabs per column group.  1152 workgroups on 768 resident slots run 1.5 rounds;
+    // 2 slabs of half the work each would run 3 rounds of half the length (X re-read twice)
+    if (sonet::knob_int("SONET_POINTMLP_YSPLIT", &want) && want >= 1 && (CT / MT) % want == 0 && CT / want <= 32) ysplit = want;
     const int ct_per_y = CT / ysplit;
     if (ct_per_y > 32) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d too large", what, Cout);
     dim3 grid((unsigned)nwg_x, (unsigned)ysplit), block(X3_THREADS);
-#define X3_ARGS grid, block, 0, st, x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc, ngroups, CT, KC, ct_per_y, gidx, L1, rlog, KCP, stats_ws, zadd, zidx, ZM, sp, xa, bnb
-#define X3_LAUNCH(MM) do { if (f16) { if (S == 2) hipLaunchKernelGGL((pointmlp_x3_kernel<MM, 2, true>), X3_ARGS); \
-                                      else        hipLaunchKernelGGL((pointmlp_x3_kernel<MM, 1, true>), X3_ARGS); } \
-                           else     { if (S == 2) hipLaunchKernelGGL((pointmlp_x3_kernel<MM, 2, false>), X3_ARGS); \
-                                      else        hipLaunchKernelGGL((pointmlp_x3_kernel<MM, 1, false>), X3_ARGS); } } while (0)
-    if (zadd && f16 && CT % 4 == 0 && !stats_ws && nwg_x >= 512 && !sonet::knob("SONET_POINTMLP_MT")) {      // (small launches: more slabs instead)
+#define X3_ARGS(GRID, CPY) GRID, block, 0, st, x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc, ngroups, CT, KC, CPY, gidx, L1, rlog, KCP, stats_ws, zadd, zidx, ZM, sp, xa, bnb
+    if (zadd && f16 && CT % 4 == 0 && !stats_ws && nwg_x >= 512 && !mt_knob) {      // (small launches: more slabs instead)
         // per-node addend: 4-tile groups with the gathers in flight during the K loop
         dim3 gz((unsigned)nwg_x, (unsigned)sonet::ceil_div(CT, 32));      // (slabs of <= 32 tiles: the affine table; a workgroup walks its groups)
         const int cpy = CT / (int)gz.y;
         if (CT % (int)gz.y == 0 && cpy % 4 == 0 && cpy <= 32) {
-            hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, true, true>), gz, block, 0, st, x1, C1, x2, C2, wp, scale, shift, relu, y, Cout, L, gpc, ngroups,
-                               CT, KC, cpy, gidx, L1, rlog, KCP, stats_ws, zadd, zidx, ZM, sp, xa, bnb);
+            hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, true, true>), X3_ARGS(gz, cpy));
             return sonet::launched(what);
         }
     }
+    // the tile count MT as a compile-time constant M; each form instantiates the counts of its list, and MT outside it takes the last
     if (bnbp) {
-        switch (MT) {
-            case 6: hipLaunchKernelGGL((pointmlp_x3_kernel<6, 1, false, false, false, false, true>), X3_ARGS); break;
-            case 4: hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, false, false, false, false, true>), X3_ARGS); break;
-            case 2: hipLaunchKernelGGL((pointmlp_x3_kernel<2, 1, false, false, false, false, true>), X3_ARGS); break;
-            default: hipLaunchKernelGGL((pointmlp_x3_kernel<1, 1, false, false, false, false, true>), X3_ARGS);
-        }
-        if (bnb.pstats) hipLaunchKernelGGL(bwd_sums_finalize_kernel, dim3((unsigned)Cout), dim3(256), 0, st, bnb.pstats, (int)nwg_x, Cout, bnb_psums);
-        return sonet::launched(what);
+        with_int_c<6, 4, 2, 1>(MT, [&](auto m) {
+            hipLaunchKernelGGL((pointmlp_x3_kernel<decltype(m)::value, 1, false, false, false, false, true>), X3_ARGS(grid, ct_per_y)); });
+        if (bnb.pstats) hipLaunchKernelGGL(bwd_sums_finalize_kernel, dim3((unsigned)Cout), dim3(256), 0, st, bnb.pstats, (int)nwg_x, Cout, r.psums);
+    } else if (xaff) {                                           // (MT is 6 or 4 here: Cout % 128 == 0)
+        if (segpool) with_int_c<6, 4>(MT, [&](auto m) {
+            hipLaunchKernelGGL((pointmlp_x3_kernel<decltype(m)::value, 1, true, false, true, true>), X3_ARGS(grid, ct_per_y)); });
+        else         with_int_c<6, 4>(MT, [&](auto m) {
+            hipLaunchKernelGGL((pointmlp_x3_kernel<decltype(m)::value, 1, true, false, false, true>), X3_ARGS(grid, ct_per_y)); });
+        if (!segpool) stats_finalize(nwg_x);
+    } else if (segpool) {                                        // (one K chunk per stage, as the storing launch of the same shape)
+        with_int_c<6, 4, 2, 1>(MT, [&](auto m) {
+            hipLaunchKernelGGL((pointmlp_x3_kernel<decltype(m)::value, 1, true, false, true>), X3_ARGS(grid, ct_per_y)); });
+    } else {
+        with_int_c<6, 4, 2, 1>(MT, [&](auto m) {
+            constexpr int M = decltype(m)::value;
+            if (f16) { if (S == 2) hipLaunchKernelGGL((pointmlp_x3_kernel<M, 2, true>), X3_ARGS(grid, ct_per_y));
+                       else        hipLaunchKernelGGL((pointmlp_x3_kernel<M, 1, true>), X3_ARGS(grid, ct_per_y)); }
+            else     { if (S == 2) hipLaunchKernelGGL((pointmlp_x3_kernel<M, 2, false>), X3_ARGS(grid, ct_per_y));
+                       else        hipLaunchKernelGGL((pointmlp_x3_kernel<M, 1, false>), X3_ARGS(grid, ct_per_y)); } });
+        stats_finalize(nwg_x);
     }
-    if (xaff) {                                                  // (MT is 6 or 4 here: Cout % 128 == 0)
-        if (segpool) {
-            if (MT == 6) hipLaunchKernelGGL((pointmlp_x3_kernel<6, 1, true, false, true, true>), X3_ARGS);
-            else         hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, true, false, true, true>), X3_ARGS);
-            return sonet::launched(what);
-        }
-        if (MT == 6) hipLaunchKernelGGL((pointmlp_x3_kernel<6, 1, true, false, false, true>), X3_ARGS);
-        else         hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, true, false, false, true>), X3_ARGS);
-        if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x, Cout, 1.0 / ((double)B * L), mean, var, st);
-        return sonet::launched(what);
-    }
-    if (segpool) {
-        // (one K chunk per stage, as the storing launch of the same shape)
-        switch (MT) {
-            case 6: hipLaunchKernelGGL((pointmlp_x3_kernel<6, 1, true, false, true>), X3_ARGS); break;
-            case 4: hipLaunchKernelGGL((pointmlp_x3_kernel<4, 1, true, false, true>), X3_ARGS); break;
-            case 2: hipLaunchKernelGGL((pointmlp_x3_kernel<2, 1, true, false, true>), X3_ARGS); break;
-            default: hipLaunchKernelGGL((pointmlp_x3_kernel<1, 1, true, false, true>), X3_ARGS);
-        }
-        return sonet::launched(what);
-    }
-    switch (MT) {
-        case 6: X3_LAUNCH(6); break;
-        case 4: X3_LAUNCH(4); break;
-        case 2: X3_LAUNCH(2); break;
-        default: X3_LAUNCH(1);
-    }
-#undef X3_LAUNCH
 #undef X3_ARGS
-    if (stats_ws) sonet::launch_stats_finalize(stats_ws, (int)nwg_x, Cout, 1.0 / ((double)B * L), mean, var, st);
     return sonet::launched(what);
 }
 
@@ -1419,8 +1386,9 @@ extern "C" int sonet_pointmlp_h3_nodeadd_f32(const float *x1, int C1, const floa
                                              const float *zadd, const int32_t *zidx, int ZM, sonet_stream_t stream)
 {
     SONET_REQUIRE(zadd && zidx && ZM > 0, "sonet_pointmlp_h3_nodeadd_f32: NULL pointer or ZM <= 0");
-    return x3_run_impl("sonet_pointmlp_h3_nodeadd_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                       nullptr, nullptr, nullptr, zadd, zidx, ZM);
+    X3Run r{"sonet_pointmlp_h3_nodeadd_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.zadd = zadd; r.zidx = zidx; r.ZM = ZM;
+    return x3_run_impl(r);
 }
 
 namespace {
@@ -1476,8 +1444,10 @@ extern "C" int sonet_pointmlp_h3_segpool_f32(const float *x1, int C1, const floa
     hipLaunchKernelGGL(segpool_init_kernel, dim3((unsigned)sonet::ceil_div64(n, 256)), dim3(256), 0, st, keys, n);
     const SegPoolArgs sp = {ids_sorted, pos0, keys, v0, M};
     const XAffArgs xa = {xs1, xh1, xs2, xh2, xrelu};
-    const int rc = x3_run_impl(what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, nullptr, B, Cout, L, stream, nullptr, 0,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, &sp, xs1 ? &xa : nullptr);
+    X3Run r{what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, /* y */ nullptr, B, Cout, L, stream};
+    r.segpool = &sp;
+    if (xs1) r.xaff = &xa;
+    const int rc = x3_run_impl(r);
     if (rc != SONET_OK) return rc;
     hipLaunchKernelGGL(segpool_decode_kernel, dim3((unsigned)sonet::ceil_div64(n, 256)), dim3(256), 0, st, keys, v0, pos0, row_max, out_idx, out_val, Cout, M, n);
     return sonet::launched(what);
@@ -1505,8 +1475,9 @@ extern "C" int sonet_pointmlp_h3_kmax_f32(const float *x1, int C1, const float *
     SONET_REQUIRE(out && keys_ws && M > 0 && L % M == 0, "%s: NULL pointer or L %% M != 0", what);
     const size_t n = (size_t)B * Cout * M;
     if (hipMemsetAsync(keys_ws, 0, n * 4, sonet::as_stream(stream)) != hipSuccess) return sonet::fail(SONET_ERR_LAUNCH, "%s: memset failed", what);
-    const int rc = x3_run_impl(what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, nullptr, B, Cout, L, stream, nullptr, 0,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, reinterpret_cast<unsigned *>(keys_ws), M);
+    X3Run r{what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, /* y */ nullptr, B, Cout, L, stream};
+    r.kmax = reinterpret_cast<unsigned *>(keys_ws); r.KM = M;
+    const int rc = x3_run_impl(r);
     if (rc != SONET_OK) return rc;
     hipLaunchKernelGGL(kmax_decode_kernel, dim3((unsigned)sonet::ceil_div64((long long)n, 256)), dim3(256), 0, sonet::as_stream(stream),
                        reinterpret_cast<const unsigned *>(keys_ws), out, (long long)n);
@@ -1527,8 +1498,9 @@ extern "C" int sonet_pointmlp_h3_stats_f32(const float *x1, int C1, const float 
                                            float *mean, float *var, sonet_stream_t stream)
 {
     SONET_REQUIRE(stats_ws && mean && var, "sonet_pointmlp_h3_stats_f32: NULL pointer");
-    return x3_run_impl("sonet_pointmlp_h3_stats_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                       reinterpret_cast<double *>(stats_ws), mean, var);
+    X3Run r{"sonet_pointmlp_h3_stats_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
+    return x3_run_impl(r);
 }
 
 /* sonet_pointmlp_h3_stats_f32 on inputs that are the RAW outputs of BatchNorm layers: x = act(raw * xs[c] + xh[c]) is applied by the operand
@@ -1541,8 +1513,10 @@ extern "C" int sonet_pointmlp_h3_stats_xaff_f32(const float *x1, int C1, const f
 {
     SONET_REQUIRE(stats_ws && mean && var && xs1 && xh1, "sonet_pointmlp_h3_stats_xaff_f32: NULL pointer");
     const XAffArgs xa = {xs1, xh1, xs2, xh2, xrelu};
-    return x3_run_impl("sonet_pointmlp_h3_stats_xaff_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                       reinterpret_cast<double *>(stats_ws), mean, var, nullptr, nullptr, 0, nullptr, 0, nullptr, &xa);
+    X3Run r{"sonet_pointmlp_h3_stats_xaff_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
+    r.xaff = &xa;
+    return x3_run_impl(r);
 }
 
 extern "C" int sonet_pointmlp_x3_stats_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3, const float *scale,
@@ -1550,8 +1524,9 @@ extern "C" int sonet_pointmlp_x3_stats_f32(const float *x1, int C1, const float 
                                            float *mean, float *var, sonet_stream_t stream)
 {
     SONET_REQUIRE(stats_ws && mean && var, "sonet_pointmlp_x3_stats_f32: NULL pointer");
-    return x3_run_impl("sonet_pointmlp_x3_stats_f32", false, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream, nullptr, 0,
-                       reinterpret_cast<double *>(stats_ws), mean, var);
+    X3Run r{"sonet_pointmlp_x3_stats_f32", false, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
+    return x3_run_impl(r);
 }
 
 /* The input gradient of a layer behind a training-mode BatchNorm (+ ReLU) with the BatchNorm / ReLU backward applied by the operand load:
@@ -1574,8 +1549,9 @@ extern "C" int sonet_pointmlp_x3_bnb_f32(const float *gy, const float *raw, int 
         return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: the sums of the layer below (praw / psums) are a variants-build record, pass NULL", what);
 #endif
     const BnbArgs bn = {raw, a, b, c0, sc, sh, g_raw_out, relu, praw, psc, psh, prelu, reinterpret_cast<double *>(pstats_ws), nullptr};
-    return x3_run_impl(what, false, gy, C, nullptr, 0, Wp3, scale, shift, 0, y, B, Cout, L, stream, nullptr, 0, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, &bn, psums);
+    X3Run r{what, false, gy, C, /* x2, C2 */ nullptr, 0, Wp3, scale, shift, /* relu */ 0, y, B, Cout, L, stream};
+    r.bnb = &bn; r.psums = psums;
+    return x3_run_impl(r);
 }
 
 /* sonet_pointmlp_x3_bnb_f32 with the store accumulating: y = (W . g_raw) * scale + shift + yadd  (yadd [B][Cout][L]: another gradient of the
@@ -1588,22 +1564,23 @@ extern "C" int sonet_pointmlp_x3_bnb_acc_f32(const float *gy, const float *raw, 
     const char *what = "sonet_pointmlp_x3_bnb_acc_f32";
     SONET_REQUIRE(gy && raw && a && b && c0 && sc && sh && y && yadd, "%s: NULL pointer", what);
     const BnbArgs bn = {raw, a, b, c0, sc, sh, g_raw_out, relu, nullptr, nullptr, nullptr, 0, nullptr, yadd};
-    return x3_run_impl(what, false, gy, C, nullptr, 0, Wp3, scale, shift, 0, y, B, Cout, L, stream, nullptr, 0, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, &bn, nullptr);
+    X3Run r{what, false, gy, C, /* x2, C2 */ nullptr, 0, Wp3, scale, shift, /* relu */ 0, y, B, Cout, L, stream};
+    r.bnb = &bn;
+    return x3_run_impl(r);
 }
 
 extern "C" int sonet_pointmlp_x3_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3,
                                      const float *scale, const float *shift, int relu, float *y,
                                      int B, int Cout, int L, sonet_stream_t stream)
 {
-    return x3_run_impl("sonet_pointmlp_x3_f32", false, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream);
+    return x3_run_impl(X3Run{"sonet_pointmlp_x3_f32", false, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream});
 }
 
 extern "C" int sonet_pointmlp_h3_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3,
                                      const float *scale, const float *shift, int relu, float *y,
                                      int B, int Cout, int L, sonet_stream_t stream)
 {
-    return x3_run_impl("sonet_pointmlp_h3_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream);
+    return x3_run_impl(X3Run{"sonet_pointmlp_h3_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream});
 }
 
 
@@ -1615,5 +1592,7 @@ extern "C" int sonet_pointmlp_h3_gather_f32(const float *x1, int C1, int L1, con
 {
     const char *what = "sonet_pointmlp_h3_gather_f32";
     SONET_REQUIRE(gidx, "%s: NULL pointer", what);
-    return x3_run_impl(what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream, gidx, L1);
+    X3Run r{what, true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.gidx = gidx; r.L1 = L1;
+    return x3_run_impl(r);
 }

@@ -992,21 +992,12 @@ __global__ __launch_bounds__(256) void pooled_decode_kernel(const unsigned *__re
     }
 }
 
-int cu_count() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    return cus;
-}
-
 // Persistent grid: one workgroup per CU.  A workgroup owns a whole CU (512 registers per lane), so nothing of another stream runs beside it.
 // Leaving CUs out for the other graphs' small launches was measured and is slower (docs/findings.md R6.1: 3776 tiles walk in 15 rounds on
 // 252 workgroups as on 256, and the headline still lost 1.5-2 %; 8 / 12 / 20 CUs out: -1 to -3 %), so the knob stays an experiment of the VARIANTS build:
 // SONET_FUSED_FREE_CUS = k leaves at least k CUs out, -1 = the smallest grid with the same number of rounds.
 long long persistent_grid(long long ntiles, int cus) {
-    static const int free_cus = [] { const char *e = sonet::knob("SONET_FUSED_FREE_CUS"); return e ? atoi(e) : 0; }();   // (variants build only)
+    static const int free_cus = [] { int v = 0; sonet::knob_int("SONET_FUSED_FREE_CUS", &v); return v; }();   // (variants build only)
     if (ntiles <= cus) return ntiles;
     if (free_cus == 0) return cus;
     const long long rounds = (ntiles + cus - 1) / cus;
@@ -1041,8 +1032,7 @@ extern "C" int sonet_pointresnet_fused_f32(const float *x, int Cin0, const void 
     if ((double)(32 * T3) * L * 4.0 >= 4.0e9) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: a per-cloud panel exceeds 4 GiB", what);
     const int tpc = sonet::ceil_div(L, TPTS);
     const long long ntiles = (long long)B * tpc;
-    const int cus = cu_count();
-    const long long grid = persistent_grid(ntiles, cus);
+    const long long grid = persistent_grid(ntiles, sonet::cu_count(1));
     hipLaunchKernelGGL((pointresnet_fused_kernel<false>), dim3((unsigned)grid), dim3(PF_THREADS), 0, sonet::as_stream(stream),
                        x, Cin0, reinterpret_cast<const uint4 *>(wstream), reinterpret_cast<const float2 *>(affine), y, L, tpc, ntiles,
                        (const int32_t *)nullptr, (const int32_t *)nullptr, (unsigned *)nullptr, (float *)nullptr, 0, (unsigned *)nullptr, sonet::range_log());
@@ -1060,8 +1050,7 @@ extern "C" int sonet_pointresnet_fused_p16_f32(const float *x, int Cin0, const v
     if ((double)(32 * T3) * L * 4.0 >= 2.0e9) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: a per-cloud panel exceeds 2 GiB", what);
     const int tpc = sonet::ceil_div(L, TPTS);
     const long long ntiles = (long long)B * tpc;
-    const int cus = cu_count();
-    const long long grid = persistent_grid(ntiles, cus);
+    const long long grid = persistent_grid(ntiles, sonet::cu_count(1));
     hipLaunchKernelGGL((pointresnet_fused_kernel<false, true>), dim3((unsigned)grid), dim3(PF_THREADS), 0, sonet::as_stream(stream),
                        x, Cin0, reinterpret_cast<const uint4 *>(wstream), reinterpret_cast<const float2 *>(affine), y, L, tpc, ntiles,
                        (const int32_t *)nullptr, (const int32_t *)nullptr, (unsigned *)nullptr, (float *)nullptr, 0, (unsigned *)nullptr, sonet::range_log(), yp);
@@ -1090,8 +1079,7 @@ static int fused_pool_impl(const char *what, const float *x_sorted, int Cin0, co
     unsigned *partial_ws = pooled_ws + npool;
     float *v0_ws = reinterpret_cast<float *>(partial_ws + ntiles * NPASS * SEG_SLOTS * PCH);
     hipLaunchKernelGGL(pooled_init_kernel, dim3((unsigned)sonet::ceil_div64(npool, 256)), dim3(256), 0, st, pooled_ws, npool);
-    const int cus = cu_count();
-    const long long grid = persistent_grid(ntiles, cus);
+    const long long grid = persistent_grid(ntiles, sonet::cu_count(1));
     hipLaunchKernelGGL((pointresnet_fused_kernel<true>), dim3((unsigned)grid), dim3(PF_THREADS), 0, st,
                        x_sorted, Cin0, reinterpret_cast<const uint4 *>(wstream), reinterpret_cast<const float2 *>(affine), (float *)nullptr,
                        L, tpc, ntiles, ids_sorted, pos0, pooled_ws, v0_ws, M, partial_ws, sonet::range_log());

@@ -572,7 +572,9 @@ static int wgrad_bf16_impl(const char *what, const uint16_t *g, const uint16_t *
     {
         // long reductions with 16-byte aligned 8-column groups: the streaming generation (both operands through the LDS-DMA ring)
         bool want = (L & 7) == 0 && (long long)B * sonet::ceil_div(L, WS_UNIT) >= 2048;
-        if (const char *e = sonet::knob("SONET_WGRAD_BF16_STREAM")) want = want && atoi(e) != 0;
+        int stream_knob = 1;
+        sonet::knob_int("SONET_WGRAD_BF16_STREAM", &stream_knob);
+        want = want && stream_knob != 0;
         if (want) {
             const WsPlan q = ws_plan(B, Cout, Cin, L);
             if (hipMemsetAsync(ws, 0, 256, st) != hipSuccess) return sonet::fail(SONET_ERR_LAUNCH, "%s: memset failed", what);
