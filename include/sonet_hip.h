@@ -662,7 +662,8 @@ int sonet_wgrad_bf16_xaff(const uint16_t *g, const uint16_t *x, float *dw, void 
  * layer applied to the M node features once (sonet_pointmlp_h3_f32 with unit scale), gidx [B][L] i32 (out of range: 0),
  * lead [B][NL][L] the per-column channels (NL <= 4: the 3 de-centred coordinates), wl [C][NL] their weight columns, exact f32
  * fmas in channel order.  KNNModule layer 1 (models/layers.py:313-350: cat(de-centred coordinates, gathered features) -> 1x1
- * conv) without the K-fold redundant MFMAs over gathered columns. */
+ * conv) without the K-fold redundant MFMAs over gathered columns.  When L % 4 == 0 the kernel moves four columns per access: gidx and
+ * lead (NL > 0) must then be 16-byte aligned and out 16-byte (f32) / 8-byte (bf16) aligned, SONET_ERR_INVALID_ARG otherwise. */
 int sonet_node_gather_lead_affine_act_f32(const float *z, const int32_t *gidx, const float *lead, const float *wl,
                                           const float *scale, const float *shift, int relu, float *out,
                                           int B, int C, int L, int M, int NL, sonet_stream_t stream);
@@ -673,7 +674,9 @@ int sonet_node_gather_lead_affine_act_bf16(const uint16_t *z, const int32_t *gid
 
 /* Small-batch fully connected layer: y[b][o] = act((sum_k x[b][k] W[o][k]) * scale[o] + shift[o]); x [B][Cin], W [Cout][Cin]
  * (nn.Linear layout), exact f32 fma chain.  MyLinear = Linear + BatchNorm1d(eval) + ReLU (models/layers.py:123-166) with the
- * bias and the running statistics folded into (scale, shift): the classifier head of models/networks.py:202-227. */
+ * bias and the running statistics folded into (scale, shift): the classifier head of models/networks.py:202-227.  Cin <= 4096
+ * (SONET_ERR_UNSUPPORTED beyond); when Cin % 4 == 0 x and W are read 16 bytes at a time and must be 16-byte aligned
+ * (SONET_ERR_INVALID_ARG otherwise). */
 int sonet_linear_act_f32(const float *x, const float *W, const float *scale, const float *shift, int relu, float *y,
                          int B, int Cin, int Cout, sonet_stream_t stream);
 

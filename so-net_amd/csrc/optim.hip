@@ -35,7 +35,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTensor *__res
         const float d = __fsub_rn(g, m);
         m = w1 < 0.5f ? __fadd_rn(m, __fmul_rn(w1, d)) : __fsub_rn(g, __fmul_rn(d, __fsub_rn(1.f, w1)));
         v = __fadd_rn(__fmul_rn(v, beta2), __fmul_rn(__fmul_rn(w2, g), g));          // mul_(beta2).addcmul_(g, g, value = 1 - beta2)
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bs), eps);
+        // (sqrtf: the correctly rounded sequence at the library's flags, as torch's sqrt; __fsqrt_rn is the bare v_sqrt_f32 here, 1 ulp)
+        const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bs), eps);
         T.p[e] = __fadd_rn(T.p[e], __fmul_rn(-ss, __fdiv_rn(m, denom)));            // addcdiv_(m, denom, value = -step_size)
         T.m[e] = m;
         T.v[e] = v;

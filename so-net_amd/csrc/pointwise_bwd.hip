@@ -686,6 +686,14 @@ extern "C" int sonet_node_add_affine_act_f32(float *t, const float *z, const int
     return sonet::launched(what);
 }
 
+// node_gather_lead_kernel takes its quad path on L % 4 == 0 alone: 16-byte loads of gidx and lead, a 16-byte (f32) / 8-byte (bf16) store
+static bool ngl_aligned(int L, int NL, const void *gidx, const void *lead, const void *out, unsigned out_align)
+{
+    if ((L & 3) != 0) return true;
+    return (reinterpret_cast<uintptr_t>(gidx) & 15) == 0 && (NL == 0 || (reinterpret_cast<uintptr_t>(lead) & 15) == 0) &&
+           (reinterpret_cast<uintptr_t>(out) & (out_align - 1)) == 0;
+}
+
 extern "C" int sonet_node_gather_lead_affine_act_f32(const float *z, const int32_t *gidx, const float *lead, const float *wl,
                                                      const float *scale, const float *shift, int relu, float *out,
                                                      int B, int C, int L, int M, int NL, sonet_stream_t stream)
@@ -693,6 +701,7 @@ extern "C" int sonet_node_gather_lead_affine_act_f32(const float *z, const int32
     const char *what = "sonet_node_gather_lead_affine_act_f32";
     SONET_REQUIRE(z && gidx && scale && shift && out && (NL == 0 || (lead && wl)), "%s: NULL pointer", what);
     SONET_REQUIRE(B > 0 && B <= 65535 && C > 0 && L > 0 && M > 0 && M <= 1024 && NL >= 0 && NL <= 4, "%s: bad size B=%d C=%d L=%d M=%d NL=%d", what, B, C, L, M, NL);
+    SONET_REQUIRE(ngl_aligned(L, NL, gidx, lead, out, 16), "%s: gidx, lead and out must be 16-byte aligned when L %% 4 == 0 (misaligned)", what);
     hipLaunchKernelGGL(node_gather_lead_kernel<float>, dim3((unsigned)sonet::ceil_div(C, NGL_CH), (unsigned)B), dim3(NGL_THREADS), (size_t)NGL_CH * (M + 6) * sizeof(float),
                        sonet::as_stream(stream), z, gidx, lead, wl, scale, shift, relu, out, C, L, M, NL);
     return sonet::launched(what);
@@ -706,6 +715,7 @@ extern "C" int sonet_node_gather_lead_affine_act_bf16(const uint16_t *z, const i
     const char *what = "sonet_node_gather_lead_affine_act_bf16";
     SONET_REQUIRE(z && gidx && scale && shift && out && (NL == 0 || (lead && wl)), "%s: NULL pointer", what);
     SONET_REQUIRE(B > 0 && B <= 65535 && C > 0 && L > 0 && M > 0 && M <= 1024 && NL >= 0 && NL <= 4, "%s: bad size B=%d C=%d L=%d M=%d NL=%d", what, B, C, L, M, NL);
+    SONET_REQUIRE(ngl_aligned(L, NL, gidx, lead, out, 8), "%s: gidx and lead must be 16-byte, out 8-byte aligned when L %% 4 == 0 (misaligned)", what);
     hipLaunchKernelGGL(node_gather_lead_kernel<uint16_t>, dim3((unsigned)sonet::ceil_div(C, NGL_CH), (unsigned)B), dim3(NGL_THREADS), (size_t)NGL_CH * (M + 6) * sizeof(float),
                        sonet::as_stream(stream), z, gidx, lead, wl, scale, shift, relu, out, C, L, M, NL);
     return sonet::launched(what);
@@ -1929,6 +1939,9 @@ extern "C" int sonet_linear_act_f32(const float *x, const float *W, const float 
     const char *what = "sonet_linear_act_f32";
     SONET_REQUIRE(x && W && scale && shift && y, "%s: NULL pointer", what);
     SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0, "%s: non-positive size", what);
+    // (the kernel reads x and W with 16-byte loads whenever Cin % 4 == 0: the rows then start on a 16-byte boundary iff the bases do)
+    SONET_REQUIRE((Cin & 3) != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) & 15) == 0,
+                  "%s: x and W must be 16-byte aligned when Cin %% 4 == 0 (misaligned)", what);
     const int rows = sonet::ceil_div(B, FC_ROWS);
     if (rows > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B=%d too large", what, B);
     const int nj = sonet::ceil_div(Cin, 4 * FC_KS);

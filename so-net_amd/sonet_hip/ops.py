@@ -99,6 +99,14 @@ def _chk_cvec(C, **vecs):
             raise SonetHipError("%s must hold C = %d elements, got %d" % (name, C, t.numel()))
 
 
+def _aligned16(t):
+    """``t`` itself when its first element sits on a 16-byte boundary, else a fresh copy (allocations are aligned far beyond 16 bytes).  For
+    the operands a kernel reads with 16-byte loads on the strength of a LENGTH test alone (linear_act: x and W when Cin % 4 == 0;
+    node_gather_lead: gidx and lead when L % 4 == 0): a contiguous view such as ``buf[1:1 + n]`` passes every contiguity check at a 4-byte
+    offset."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _chk_f32_or_bf16(t, name):
     if t.dtype not in (torch.float32, torch.bfloat16):
         raise SonetHipError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
@@ -525,6 +533,7 @@ def node_add_affine_act_(t, z, min_idx_i32, scale, shift, relu):
     B, C, L = t.shape
     if z.shape[0] != B or z.shape[1] != C or min_idx_i32.shape != (B, L):
         raise SonetHipError("z must be B x C x M and min_idx B x L")
+    _chk_cvec(C, scale=scale, shift=shift)
     with _lib.on_device(dev), _timed("node_add_affine_act"):
         check(_lib.load().sonet_node_add_affine_act_f32(ptr(t), ptr(z), ptr(min_idx_i32), ptr(scale), ptr(shift), int(bool(relu)),
                                                         B, C, L, z.shape[2], stream_ptr()), "sonet_node_add_affine_act_f32")
@@ -613,6 +622,8 @@ def node_gather_lead_affine_act(z, gidx, lead, wl, scale, shift, relu):
     L, NL = gidx.shape[1], lead.shape[1]
     if gidx.shape[0] != B or lead.shape[0] != B or lead.shape[2] != L or tuple(wl.shape) != (C, NL) or scale.numel() != C or shift.numel() != C:
         raise SonetHipError("node_gather_lead_affine_act: z B x C x M, gidx B x L, lead B x NL x L, wl C x NL, scale / shift C")
+    _chk_cvec(C, scale=scale, shift=shift)
+    gidx, lead = _aligned16(gidx), _aligned16(lead)              # (16-byte loads when L % 4 == 0; the C entry refuses misaligned ones)
     out = torch.empty((B, C, L), dtype=z.dtype, device=dev)
     lib = _lib.load()
     fn = lib.sonet_node_gather_lead_affine_act_f32 if z.dtype == torch.float32 else lib.sonet_node_gather_lead_affine_act_bf16
@@ -2347,6 +2358,11 @@ def linear_act(x, weight, scale, shift, relu):
     dev = _same_device(x, weight, scale, shift)
     B, Cin = x.shape
     Cout = weight.shape[0]
+    if weight.shape[1] != Cin:
+        raise SonetHipError("linear_act: x B x Cin, weight Cout x Cin, got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    if scale.numel() != Cout or shift.numel() != Cout or scale.dtype != torch.float32 or shift.dtype != torch.float32:
+        raise SonetHipError("linear_act: scale / shift must hold Cout = %d float32 elements" % Cout)
+    x, weight = _aligned16(x), _aligned16(weight)                 # (16-byte loads when Cin % 4 == 0; the C entry refuses misaligned ones)
     y = torch.empty((B, Cout), dtype=torch.float32, device=dev)
     with _lib.on_device(dev), _timed("linear_act_%dx%d" % (Cin, Cout)):
         check(_lib.load().sonet_linear_act_f32(ptr(x), ptr(weight), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cin, Cout, stream_ptr()),
