@@ -1071,6 +1071,9 @@ static int fused_pool_impl(const char *what, const float *x_sorted, int Cin0, co
     SONET_REQUIRE(x_sorted && wstream && affine && ids_sorted && pos0 && node_off && count && ws && out, "%s: NULL pointer", what);
     SONET_REQUIRE(B > 0 && L > 0 && M > 0 && Cin0 >= 1 && Cin0 <= 16, "%s: bad size B=%d L=%d M=%d Cin0=%d", what, B, L, M, Cin0);
     if (B > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B=%d > 65535", what, B);
+    // the kernel forms the byte offsets of all 16 input rows, (row * L + column) * 4, in 32 bits (rows >= Cin0 rely on the descriptor's range
+    // check, which a wrapped offset would pass); the store variant never gets there, its 384-row output panel refuses first
+    if (16.0 * L * 4.0 >= 4.0e9) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: a per-cloud input panel of 16 rows exceeds 4 GiB", what);
     hipStream_t st = sonet::as_stream(stream);
     const long long npool = (long long)B * M * (32 * T3);
     const int tpc = sonet::ceil_div(L, TPTS);

@@ -262,6 +262,9 @@ def require_device(device):
     call -- an environment lookup -- and an op wrapper runs a hundred times per training step.)"""
     if device.index in _device_ok:
         return
+    if device.type != "cuda" and torch.cuda.is_available():
+        # (a CPU tensor on a machine that HAS a GPU: without this the kernel would be launched on host pointers)
+        raise SonetHipError("sonet_hip needs its tensors on an MI355X (gfx950) GPU, got one on %s; there is no CPU fallback" % device)
     if not torch.cuda.is_available():
         raise SonetHipError("sonet_hip needs an MI355X (gfx950) GPU; torch.cuda.is_available() is False "
                             "and there is no CPU fallback")

@@ -99,6 +99,30 @@ def _chk_cvec(C, **vecs):
             raise SonetHipError("%s must hold C = %d elements, got %d" % (name, C, t.numel()))
 
 
+def _chk_member(t, name, dtype, shape):
+    """A tensor that a kernel indexes on the strength of the launch sizes alone (the members of a sorted grouping, a packed weight stream):
+    dtype, shape and contiguity must be exactly what the kernel reads -- an int64 or strided id tensor would be read as int32 words.
+    Attribute checks only (no launch, no sync); the device is checked with the other operands (``_same_device``)."""
+    if not isinstance(t, torch.Tensor):
+        raise SonetHipError("%s must be a torch.Tensor" % name)
+    if t.dtype != dtype:
+        raise SonetHipError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise SonetHipError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise SonetHipError("%s must be contiguous" % name)
+
+
+def _chk_sort_group(sg, M):
+    """The members of a ``som_sort_group`` result that the pooled first PointNet reads unchecked: int32, contiguous, B x L / B / B x M."""
+    x = sg["x_aug_sorted"]
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise SonetHipError("x_aug_sorted must be a 3-D torch.Tensor")
+    B, _, L = x.shape
+    for name, shape in (("ids_sorted", (B, L)), ("pos0", (B,)), ("node_off", (B, int(M))), ("count", (B, int(M)))):
+        _chk_member(sg[name], name, torch.int32, shape)
+
+
 def _aligned16(t):
     """``t`` itself when its first element sits on a 16-byte boundary, else a fresh copy (allocations are aligned far beyond 16 bytes).  For
     the operands a kernel reads with 16-byte loads on the strength of a LENGTH test alone (linear_act: x and W when Cin % 4 == 0;
@@ -1969,6 +1993,7 @@ def pointresnet_pack(w1, w2, w3, w4):
 def pointresnet_fused(x, wstream, affine, want_p16=False):
     """x B x Cin0 x L f32 -> B x 384 x L f32 (whole first PointNet, eval BN folded into ``affine`` 832 x 2).
     want_p16: -> (y, P16 planes of y), written by the same launch (the operand format of ``pointmlp_h3p``)."""
+    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_pack_size(),))
     _chk(x, "x", torch.float32, 3)
     _chk(affine, "affine", torch.float32, 2)
     if tuple(affine.shape) != (832, 2):
@@ -1995,8 +2020,12 @@ def pointresnet_fused_pool(sg, wstream, affine, M, want_p16=False):
     """First PointNet + per-node max-pool in one pass over node-sorted points (``sg`` = som_sort_group result)
     -> B x 384 x M f32.  want_p16: -> (that, ``P16`` 1 x 384 x Lm): the same map pre-split on the flat column axis of the node-level stage."""
     x_sorted = sg["x_aug_sorted"]
+    _chk_sort_group(sg, M)
+    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_pack_size(),))
     _chk(x_sorted, "x_sorted", torch.float32, 3)
     _chk(affine, "affine", torch.float32, 2)
+    if tuple(affine.shape) != (832, 2):
+        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
     dev = _same_device(x_sorted, wstream, affine, sg["ids_sorted"], sg["pos0"], sg["node_off"], sg["count"])
     B, Cin0, L = x_sorted.shape
     lib = _lib.load()
@@ -2033,6 +2062,7 @@ def pointresnet_bf16_pack(w1, w2, w3, w4):
 
 def pointresnet_bf16(x, wstream, affine):
     """x B x Cin0 x L f32 -> B x 384 x L bfloat16: whole first PointNet in bf16 (eval BN folded into ``affine`` 832 x 2)."""
+    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_bf16_pack_size(),))
     _chk(x, "x", torch.float32, 3)
     _chk(affine, "affine", torch.float32, 2)
     if tuple(affine.shape) != (832, 2):
@@ -2052,8 +2082,12 @@ def pointresnet_bf16_pool(sg, wstream, affine, M):
     """bf16 first PointNet + per-node max-pool in one pass over node-sorted points (``sg`` = som_sort_group result)
     -> B x 384 x M f32 holding bf16-representable values (the maxima of the bf16 features the store variant writes)."""
     x_sorted = sg["x_aug_sorted"]
+    _chk_sort_group(sg, M)
+    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_bf16_pack_size(),))
     _chk(x_sorted, "x_sorted", torch.float32, 3)
     _chk(affine, "affine", torch.float32, 2)
+    if tuple(affine.shape) != (832, 2):
+        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
     dev = _same_device(x_sorted, wstream, affine, sg["ids_sorted"], sg["pos0"], sg["node_off"], sg["count"])
     B, Cin0, L = x_sorted.shape
     lib = _lib.load()
