@@ -878,6 +878,27 @@ int sonet_upconv3x3_pack_f32(const float *W, void *Wp, int Cin, int Cout, sonet_
 int sonet_upconv3x3_f32(const float *x, const void *Wp, const float *scale, const float *shift, int relu, float *y,
                         int B, int Cin, int Cout, int H, int W, uint32_t *range_log, sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * upconv3x3_dgrad  -- the input gradient of the up-convolution above as one launch (training; so-net_amd/csrc/upconv_bwd.hip)
+ * g [B][Cout][2H][2W] f32 (the gradient of y BEFORE scale / shift / activation, i.e. of conv3x3_pad1(upsample2_nearest(x), W)),
+ * W [Cout][Cin][3][3] f32, dx [B][Cin][H][W] f32 (fully overwritten):
+ *   dx = sum over py, px, dy, dx' in {0, 1} of  wf[py][px][dy][dx']^T . shifted(g[:, :, py::2, px::2], 1 - py - dy, 1 - px - dx')
+ * with the sixteen folded matrices wf of the forward and a zero-padded shift: input pixel (u, v) reads pixel (u + 1 - py - dy,
+ * v + 1 - px - dx') of the parity plane.  Neither the upsampled map nor its gradient is written.  Arithmetic: the three-way bf16 split of
+ * both operands (sonet_pointmlp_x3: six products, smallest first, f32 accumulation in chains of at most 1024 products): f32-class over
+ * the f32 exponent range, so the launch takes no range log.  No atomics: the result is bit-reproducible; the launch can be captured.
+ * sonet_upconv3x3_dgrad_pack_f32 writes sonet_upconv3x3_dgrad_pack_size(Cin, Cout) bytes (0 for an unsupported shape): the transposed
+ * folded weights (f64 sums rounded to f32, three bf16 pieces) in MFMA A-fragment order, rows = Cin in blocks of 32 with zero rows past
+ * Cin; a pack serves every B, H, W.
+ * Alignment: Wpt 16 bytes, g 8 bytes (the two px of a row are one load), dx and W 4 bytes.
+ * Shapes: those of sonet_upconv3x3_f32 -- B >= 1, Cin >= 1 (any: the tail rows are masked on the store), Cout a multiple of
+ * SONET_UPCONV_COUT_BLOCK, 1 <= H, W <= SONET_UPCONV_MAX_HW, B H W < 2^31 - 2^16.  A NULL or misaligned pointer or a non-positive size
+ * returns SONET_ERR_INVALID_ARG, any other shape SONET_ERR_UNSUPPORTED, before any launch.  A workgroup covers SONET_UPCONV_TILE_PIXELS
+ * columns x 32 input channels and stages SONET_UPCONV_K_CHUNK channels of Cout at a time, one py after the other (74 KB of LDS).
+ * ---------------------------------------------------------------------------------------------- */
+size_t sonet_upconv3x3_dgrad_pack_size(int Cin, int Cout);
+int sonet_upconv3x3_dgrad_pack_f32(const float *W, void *Wpt, int Cin, int Cout, sonet_stream_t stream);
+int sonet_upconv3x3_dgrad_f32(const float *g, const void *Wpt, float *dx, int B, int Cin, int Cout, int H, int W, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * VARIANTS build only (make -C so-net_amd/csrc variants -> libsonet_hip_variants.so, -DSONET_VARIANTS): kernels that measured
  * slower than what the product dispatches, kept as tested records of the experiments (tests/variants).  The product library
  * does not export them and reads no environment variable.

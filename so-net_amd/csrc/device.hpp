@@ -152,5 +152,38 @@ __device__ __forceinline__ void p16_split_pair(float x0, float x1, unsigned &h, 
 // channel of element e (0..7) of half h in a 16-channel chunk of a P16 plane
 __device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
 
+// ---- three-way bf16 split of an f32 pair (the "x3" arithmetic: pointmlp_x3.hip, upconv_bwd.hip) ------------------------------------
+// (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
+__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
+    h = cvt_pk_bf16(x0, x1);
+    const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xFFFF0000u);
+    m = cvt_pk_bf16(r0, r1);
+    const float q0 = r0 - __uint_as_float(m << 16), q1 = r1 - __uint_as_float(m & 0xFFFF0000u);
+    l = cvt_pk_bf16(q0, q1);
+}
+
+// The WEIGHT side of the split (the pack kernels: not on a hot path).  split3_pair turns a value whose bf16 rounding is inf -- +-inf, and
+// the finite |w| >= 0x7F7F8000 (3.3895e38) -- into h = inf, m = l = NaN (inf - inf), and a NaN piece makes the whole output row NaN where
+// the f32 product holds +-inf or even a finite value.  Here instead:
+//   finite:  h = the largest finite bf16 of that sign (round towards zero); the residual then fits m and l exactly;
+//   +-inf:   h = m = 0, l = +-inf.  The l piece meets ONLY xh (the product Wl.xh), which has x's sign and is zero only where x is: the row
+//            comes out as inf * x does in f32 -- +-inf, NaN against a zero -- and no 0 * inf arises from the x pieces that happen to be zero.
+// Every other value goes through split3_pair unchanged (bit-identical packs).
+__device__ __forceinline__ void split3_fix_w(float w, unsigned &h, unsigned &m, unsigned &l) {       // one value's pieces in the low 16 bits
+    if ((h & 0x7FFFu) != 0x7F80u) return;
+    if (__builtin_isinf(w)) { l = h; h = 0u; m = 0u; return; }
+    h -= 1u;                                                                 // 0x7F80 -> 0x7F7F, sign kept
+    const float r = w - __uint_as_float(h << 16);
+    m = cvt_pk_bf16(r, 0.f) & 0xFFFFu;
+    l = cvt_pk_bf16(r - __uint_as_float(m << 16), 0.f) & 0xFFFFu;
+}
+__device__ __forceinline__ void split3_pair_w(float w0, float w1, unsigned &h, unsigned &m, unsigned &l) {
+    split3_pair(w0, w1, h, m, l);
+    unsigned h0 = h & 0xFFFFu, m0 = m & 0xFFFFu, l0 = l & 0xFFFFu, h1 = h >> 16, m1 = m >> 16, l1 = l >> 16;
+    split3_fix_w(w0, h0, m0, l0);
+    split3_fix_w(w1, h1, m1, l1);
+    h = h0 | (h1 << 16); m = m0 | (m1 << 16); l = l0 | (l1 << 16);
+}
+
 // cluster mean of the SOM stage (models/networks.py:142): sum / (count + 1e-5), every step rounded to f32 (no reciprocal, no FMA)
 __device__ __forceinline__ float cluster_mean(float sum, float count) { return __fdiv_rn(sum, __fadd_rn(count, 1e-5f)); }

@@ -25,30 +25,9 @@
 //   * the sixteen (parity, tap) A fragments of its Cout block (2 KiB each) -- except those whose shifted operand lies in the padding for
 //     EVERY column of the tile, which are neither read nor multiplied (at 1 x 1: twelve of sixteen).
 // The next chunk's global loads are in flight in registers while this chunk's MFMAs run.
-#include "common.hpp"
+#include "upconv_fold.hpp"               // tile extents, fold_range, acc_row, shape_ok: shared with upconv_bwd.hip
 
 namespace {
-
-
-constexpr int UP_THREADS = 256;
-constexpr int UP_TP = SONET_UPCONV_TILE_PIXELS;            // columns (low-resolution pixels) per workgroup
-constexpr int UP_KC = SONET_UPCONV_K_CHUNK;                // input channels per staged chunk
-constexpr int UP_CB = SONET_UPCONV_COUT_BLOCK;             // output channels per workgroup
-constexpr int UP_MAXHW = SONET_UPCONV_MAX_HW;
-constexpr int UP_NSLOT = UP_TP + 2 * UP_MAXHW + 2;         // staged columns at W = 64
-constexpr int UP_ZS = UP_NSLOT;                            // the slot of zeros
-constexpr int UP_XIT = (2 * UP_NSLOT + UP_THREADS - 1) / UP_THREADS;      // (column, K half) items per thread
-constexpr int UP_FLUSH = 16;                               // chunks per accumulation chain
-static_assert(UP_TP == 128 && UP_KC == 16 && UP_CB == 32, "the kernel below is written for these extents");
-
-// row of Cout a lane holds in accumulator register r (h = lane >> 5)
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// ky (kx) range a (parity, tap) pair sums: parity 0: {0}, {1, 2}; parity 1: {0, 1}, {2}
-__device__ __forceinline__ void fold_range(int par, int tap, int &k0, int &k1) {
-    k0 = tap == 0 ? 0 : (par == 0 ? 1 : 2);
-    k1 = tap == 0 ? (par == 0 ? 0 : 1) : 2;
-}
 
 // ---- weight pack: Wp[ct][kc][pt][form][lane] (uint4 = 8 fp16): pt = (py, px, dy, dx) as 8 py + 4 px + 2 dy + dx; row ct * 32 + (lane & 31),
 // channels 16 kc + 8 (lane >> 5) .. + 7 (zeros past Cin); form 0 = fp16(32 wf), form 1 = fp16(32 wf - form 0) of the folded weight wf (f64 sum
@@ -280,10 +259,6 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_kernel(const UpArgs a
             }
         }
     }
-}
-
-bool shape_ok(int Cin, int Cout, int H, int W) {
-    return Cin >= 1 && Cout >= UP_CB && Cout % UP_CB == 0 && H >= 1 && H <= UP_MAXHW && W >= 1 && W <= UP_MAXHW;
 }
 
 }  // namespace

@@ -1116,6 +1116,76 @@ class MyConv2d(_FusedPointwise):
         return y
 
 
+class _UpConvTrainFn(torch.autograd.Function):
+    """Training-mode ``UpConv`` on the folded kernels (once differentiable).  forward: ``ops.upconv3x3`` with a unit scale (raw = conv +
+    bias), then -- 'batch' -- the batch statistics, coefficients and running-statistics update of ``ops.bn_rider`` + ``ops.channel_stats``
+    and the normalise + ReLU pass; without a norm the bias and the activation ride on the one launch.  backward: the BatchNorm / ReLU
+    backward passes of the point-wise layers give g_raw, ``ops.upconv3x3_dgrad`` the input gradient (the upsampled tensor never exists
+    on that side); the weight gradient is aten's convolution backward (weight only) on the upsampled input, formed here."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, wp, wpt, relu, eps, bn_run):
+        B, Cin, H, W = x.shape
+        Cout = weight.shape[0]
+        dev = x.device
+        ones = _ops.const_vec(Cout, 1.0, dev)
+        b_ = bias.detach().contiguous()
+        ctx.relu, ctx.bn = bool(relu), gamma is not None
+        if ctx.bn:
+            raw = _ops.upconv3x3(x, wp, ones, b_, False, Cout)
+            rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
+            invstd, sc, sh = _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+            raw3 = raw.view(B, Cout, 4 * H * W)
+            mean, var = _ops.channel_stats(raw3)
+            y = _ops.channel_affine_act(raw3, sc, sh, relu).view(B, Cout, 2 * H, 2 * W)
+            ctx.save_for_backward(x, weight, wpt if wpt is not None else x.new_empty(0), sc, sh, raw, mean, invstd, gamma)
+            ctx.mark_non_differentiable(mean, var)
+            ctx.set_materialize_grads(False)
+            return y, mean, var
+        y = _ops.upconv3x3(x, wp, ones, b_, relu, Cout)
+        ctx.save_for_backward(x, weight, wpt if wpt is not None else x.new_empty(0), y if relu else x.new_empty(0))
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, *unused):
+        if gy is None:
+            return (None,) * 10
+        saved = ctx.saved_tensors
+        x, weight, wpt = saved[:3]
+        B, Cin, H, W = x.shape
+        Cout = weight.shape[0]
+        dev = gy.device
+        gy = gy.contiguous()
+        gy3 = gy.view(B, Cout, 4 * H * W)
+        ones, zeros = _ops.const_vec(Cout, 1.0, dev), _ops.const_vec(Cout, 0.0, dev)
+        g_gamma = g_beta = None
+        if ctx.bn:
+            sc, sh, raw, mean, invstd, gamma = saved[3:9]
+            raw3 = raw.view(B, Cout, 4 * H * W)
+            sums = _ops.pointwise_bwd_stats(gy3, raw3, sc, sh, ctx.relu, want_sums=True)
+            a, b, c0, g_gamma, g_beta = _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, float(B * 4 * H * W))
+            g_raw3 = _ops.pointwise_bwd_apply(gy3, raw3, sc, sh, ctx.relu, a, b, c0)
+        elif ctx.relu:
+            y3 = saved[3].view(B, Cout, 4 * H * W)                           # mask source: y > 0 <=> pre-activation > 0
+            g_raw3 = _ops.pointwise_bwd_apply(gy3, y3, ones, zeros, True, ones, zeros, zeros)
+        else:
+            g_raw3 = gy3
+        g_raw = g_raw3.view(B, Cout, 2 * H, 2 * W)
+        g_x = g_w = g_bias = None
+        if ctx.needs_input_grad[0]:
+            g_x = _ops.upconv3x3_dgrad(g_raw, wpt, Cin)
+        if ctx.needs_input_grad[1]:
+            up = F.interpolate(x, scale_factor=2)
+            g_w = torch.ops.aten.convolution_backward(g_raw, up, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                                      (False, True, False))[1]
+        if ctx.needs_input_grad[2]:
+            s1, _ = _ops.pointwise_bwd_stats(g_raw3, g_raw3, ones, zeros, False)          # per-channel sum of g_raw, f64 on the device
+            g_bias = s1.float()
+        return g_x, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None
+
+
 class UpConv(nn.Module):
     """Upsample x2 + 3x3 conv (models/layers.py:214-240); decoder only.
 
@@ -1123,7 +1193,13 @@ class UpConv(nn.Module):
     upsample, conv, bias, BatchNorm and ReLU as ONE launch of the fused up-convolution (``sonet_hip.ops.upconv3x3``, fp16-split
     arithmetic, range-guarded like the point-wise layers) -- when the precision is "h3", the normalization is 'batch' or None, the
     activation 'relu' or None and the shape is one the operator takes.  Everything else -- training, autograd, another precision (the
-    range guard's re-run included), another normalization or shape -- runs the two aten lines below, as without the attribute."""
+    range guard's re-run included), another normalization or shape -- runs the two aten lines below, as without the attribute.
+
+    ``fused_train`` (default False; ``DecoderConv`` sets it from ``opt.decoder_fused_train``): a TRAINING-mode call on an f32 GPU tensor
+    runs ``_UpConvTrainFn`` -- the same forward launch followed by the BatchNorm passes of the point-wise layers, and the folded
+    input-gradient launch (``sonet_hip.ops.upconv3x3_dgrad``) in the backward pass; the weight gradient stays on aten -- under the same
+    conditions on precision, normalization, activation and shape.  The forward launch reports into the open range scope: in training a
+    violation switches the process to "x3" one step late (``ops.run_guarded``), after which the layer is on the aten lines."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, output_padding=0, bias=True,
                  activation=None, normalization=None):
@@ -1131,6 +1207,7 @@ class UpConv(nn.Module):
         self.activation = activation
         self.normalization = normalization
         self.fused = False
+        self.fused_train = False
         self.up_sample = nn.Upsample(scale_factor=2)
         self.conv = MyConv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True,
                              activation=activation, normalization=normalization)
@@ -1162,10 +1239,50 @@ class UpConv(nn.Module):
             self._wup_key = key
         return self._wup
 
+    def _fused_train_ok(self, x):
+        conv = self.conv.conv
+        return (self.fused_train and self.training and _ops.POINTMLP_PRECISION == "h3" and x.dim() == 4 and x.is_cuda
+                and x.dtype == torch.float32 and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
+                and conv.weight.is_cuda and conv.weight.dtype == torch.float32
+                and _ops.upconv3x3_supported(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]))
+
+    def _packed_upconv_dgrad(self):
+        """The input gradient's pack of the 3x3 weight (transposed folded weights), cached like ``_packed_upconv``."""
+        w = self.conv.conv.weight
+        key = (w._version, w.data_ptr(), w.device)
+        if getattr(self, '_wupt_key', None) != key:
+            with torch.no_grad():
+                self._wupt = _ops.upconv3x3_dgrad_pack(w.detach().contiguous())
+            self._wupt_key = key
+        return self._wupt
+
+    def _forward_train(self, x):
+        conv, relu = self.conv, self.activation == 'relu'
+        x = x.contiguous()
+        wpt = self._packed_upconv_dgrad() if (torch.is_grad_enabled() and x.requires_grad) else None
+        w = conv.conv.weight
+        if self.normalization != 'batch':
+            return _UpConvTrainFn.apply(x, w, conv._bias(), None, None, self._packed_upconv(), wpt, relu, 0.0, None)
+        bn = conv.norm
+        n = x.shape[0] * 4 * x.shape[2] * x.shape[3]
+        m = bn.momentum
+        ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
+                and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device)
+        y, mean, var = _UpConvTrainFn.apply(x, w, conv._bias(), bn.weight, bn.bias, self._packed_upconv(), wpt, relu, bn.eps,
+                                            (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None)
+        with torch.no_grad():
+            if not ride and bn.running_mean is not None and m is not None:
+                bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
+                bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
+            conv._affine_key = None                        # (the buffers moved through raw pointers: drop the folded eval affine)
+        return y
+
     def forward(self, x):
         if self._fused_ok(x):
             scale, shift = self.conv._eval_affine()
             return _ops.upconv3x3(x.contiguous(), self._packed_upconv(), scale, shift, self.activation == 'relu', self.conv.conv.out_channels)
+        if self._fused_train_ok(x):
+            return self._forward_train(x)
         return self.conv(self.up_sample(x))
 
 

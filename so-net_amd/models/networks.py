@@ -722,6 +722,10 @@ class DecoderConv(nn.Module):
             up = UpConv(chans[i], chans[i + 1], activation=opt.activation, normalization=opt.normalization)
             # opt.decoder_fused: inference runs each up-convolution as one launch (ops.upconv3x3); absent = the aten layers
             up.fused = bool(getattr(opt, "decoder_fused", False))
+            # opt.decoder_fused_train: training runs the folded forward and input-gradient launches (layers._UpConvTrainFn) -- True = all
+            # six layers, or a collection of layer numbers such as (4, 5, 6); absent = the aten layers
+            ft = getattr(opt, "decoder_fused_train", False)
+            up.fused_train = ft if isinstance(ft, bool) else (ft is not None and (i + 1) in tuple(ft))
             setattr(self, "deconv%d" % (i + 1), up)
             if i >= 3:
                 setattr(self, "conv2pc%d" % (i + 1), ConvToPC(chans[i + 1], opt))

@@ -2637,6 +2637,50 @@ def upconv3x3(x, wp, scale, shift, relu, Cout):
     return y
 
 
+def upconv3x3_dgrad_pack(weight4d):
+    """[Cout][Cin][3][3] f32 -> the pack of the up-convolution's input gradient (int32 tensor): the sixteen folded (parity, tap) weights,
+    transposed (rows = Cin), summed in float64, split into three bf16 pieces, in MFMA A-fragment order."""
+    _chk(weight4d, "weight", torch.float32, 4)
+    Cout, Cin, kh, kw = weight4d.shape
+    if (kh, kw) != (3, 3):
+        raise SonetHipError("upconv3x3_dgrad_pack: a 3x3 kernel, got %dx%d" % (kh, kw))
+    if not upconv3x3_supported(Cin, Cout, 1, 1):
+        raise SonetHipError("upconv3x3_dgrad_pack: Cout = %d is not a multiple of %d" % (Cout, UPCONV_COUT_BLOCK))
+    dev = _same_device(weight4d)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        wpt = torch.empty((lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout) // 4,), dtype=torch.int32, device=dev)
+        check(lib.sonet_upconv3x3_dgrad_pack_f32(ptr(weight4d), ptr(wpt), Cin, Cout, stream_ptr()), "sonet_upconv3x3_dgrad_pack_f32")
+    return wpt
+
+
+def upconv3x3_dgrad(g, wpt, Cin):
+    """The input gradient of conv3x3_pad1(upsample2_nearest(x), w) in one launch (training): g B x Cout x 2H x 2W f32 (the gradient of
+    the convolution's output) -> B x Cin x H x W f32; wpt from ``upconv3x3_dgrad_pack``.  bf16-split (x3) arithmetic: no operand range to
+    guard, so the launch takes no range-log slot."""
+    _chk(g, "g", torch.float32, 4)
+    B, Cout, H2, W2 = g.shape
+    Cin = int(Cin)
+    H, W = H2 // 2, W2 // 2
+    if B < 1 or H2 % 2 or W2 % 2 or not upconv3x3_supported(Cin, Cout, H, W):
+        raise SonetHipError("upconv3x3_dgrad: unsupported shape B=%d Cin=%d Cout=%d 2H=%d 2W=%d (Cout %% %d == 0, 1 <= H, W <= %d)"
+                            % (B, Cin, Cout, H2, W2, UPCONV_COUT_BLOCK, UPCONV_MAX_HW))
+    if not isinstance(wpt, torch.Tensor) or wpt.dtype != torch.int32:
+        raise SonetHipError("upconv3x3_dgrad: an input-gradient pack (ops.upconv3x3_dgrad_pack)")
+    _chk(wpt, "wpt", torch.int32, 1)
+    dev = _same_device(g, wpt)
+    lib = _lib.load()
+    if wpt.numel() * 4 != lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout):
+        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
+                            % (wpt.numel() * 4, lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout), Cin, Cout))
+    if g.data_ptr() % 8 or wpt.data_ptr() % 16:
+        raise SonetHipError("upconv3x3_dgrad: g must be 8-byte and the pack 16-byte aligned")
+    dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev), _timed("upconv3x3_dgrad_%dx%d_%dx%d" % (Cin, Cout, H, W)):
+        check(lib.sonet_upconv3x3_dgrad_f32(ptr(g), ptr(wpt), ptr(dx), B, Cin, Cout, H, W, stream_ptr()), "sonet_upconv3x3_dgrad_f32")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------ segmentation metrics
 SHAPENET_PART_OFFSETS = (0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47, 50)    # models/losses.py:126-143 as a CSR table
 SEG_METRICS_MAX_C = 256

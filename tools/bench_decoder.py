@@ -2,6 +2,7 @@
 launch (ops.upconv3x3, opt.decoder_fused), in ONE process on one MI355X.
 
     python tools/bench_decoder.py [--batch 64] [--rounds 5] [--iters 20] [--points 5000] [--spin-up 1.0] [--skip-forward]
+    python tools/bench_decoder.py --train [--batch 64] [--rounds 5] [--iters 10] [--spin-up 1.0]
 
 After the clock spin-up bench.py uses (untimed calls for --spin-up seconds: an idle MI355X sits at its lowest clock), every pair of
 variants is timed INTERLEAVED -- aten, fused, aten, fused, ... --rounds rounds of --iters calls each, every group bracketed by HIP
@@ -13,6 +14,11 @@ events on the launch stream -- and the median over the rounds is reported:
           (ops.mfma_f16_sustained_rate) = fraction of the three-term matrix ceiling;
   (-)     the whole Decoder.forward (FC decoder + conv pyramid + point heads), eager, option off and on;
   (c)     configs[3] of bench.py: encoder + decoder + two-resolution Chamfer loss, HIP-graph replay on one stream, option off and on.
+--train: the TRAINING step of the same six layers at feature_num 1024, option off (the two aten lines per layer) against
+opt.decoder_fused_train (layers._UpConvTrainFn), interleaved in the same way.  Per layer: the forward (autograd on), forward + backward
+and their difference, and for the fused backward its parts timed on their own -- the folded input gradient (ops.upconv3x3_dgrad), the
+weight gradient (upsample + aten's convolution backward, weight only) and the BatchNorm / ReLU / bias passes; then one training step of
+the whole DecoderConv (forward + backward on fixed cotangents), option off, on, and on for layers (4, 5, 6).
 Prints a table and one JSON line (last line).
 """
 import argparse
@@ -56,6 +62,98 @@ def live_pairs(H, W):
     return ny * nx
 
 
+def train_bench(args):
+    import bench
+    from models import networks as NW
+    from sonet_hip import ops, synth
+    dev = torch.device("cuda", 0)
+    B, F_ = args.batch, 1024
+
+    def make(train_opt):
+        opt = Namespace(gpu_id=0, device=dev, feature_num=F_, activation="relu", normalization="batch", output_fc_pc_num=0,
+                        output_conv_pc_num=4096, decoder_fused_train=train_opt)
+        d = NW.Decoder(opt)
+        synth.fill_state_dict_(d.state_dict(), 2)
+        return d.to(dev).train()
+
+    decs = {"aten": make(False), "fused": make(True), "fused456": make((4, 5, 6))}
+    feat = torch.randn(B, F_, generator=torch.Generator().manual_seed(5)).abs().to(dev)
+    gen = torch.Generator().manual_seed(6)
+    cots = {i: (torch.randn(B, 3, n, generator=gen) * 1e-3).to(dev) for i, n in ((4, 256), (5, 1024), (6, 4096))}
+    result = {"batch": B, "rounds": args.rounds, "iters": args.iters, "train_layers": {}}
+
+    def step(dec):
+        feat.grad = None
+        for p in dec.parameters():
+            p.grad = None
+        dec(feat)
+        sum((getattr(dec, "conv_pc%d" % i) * cots[i]).sum() for i in (4, 5, 6)).backward()
+
+    with torch.no_grad():
+        xs, x = [], feat.view(-1, F_, 1, 1)
+        for i in range(1, 7):
+            xs.append(x)
+            x = getattr(decs["aten"].conv_decoder, "deconv%d" % i)(x)
+    feat = feat.clone().requires_grad_(True)                     # (in training the feature is the encoder's: it needs its gradient)
+    for _ in range(3):
+        for d in decs.values():
+            step(d)
+    torch.cuda.synchronize()
+    bench._spin_up(lambda: [step(d) for d in decs.values()], args.spin_up)
+    print("%-8s %-16s | %9s %9s | %9s %9s | %8s %8s %8s | %7s" % ("layer", "Cin->Cout @ HxW", "aten fwd", "aten bwd", "fused fwd", "fused bwd",
+                                                                 "dgrad", "wgrad", "passes", "step x"))
+    for i in range(1, 7):
+        ma, mf = (getattr(decs[k].conv_decoder, "deconv%d" % i) for k in ("aten", "fused"))
+        xi = xs[i - 1].clone().requires_grad_(True)
+        Cin, Cout, H, W = xi.shape[1], ma.conv.conv.out_channels, xi.shape[2], xi.shape[3]
+        gy = torch.randn(B, Cout, 2 * H, 2 * W, generator=torch.Generator().manual_seed(i)).to(dev) * 1e-3
+
+        def fb(m):
+            xi.grad = None
+            for p in m.parameters():
+                p.grad = None
+            m(xi).backward(gy)
+
+        # the parts of the fused backward on their own operands
+        wpt = ops.upconv3x3_dgrad_pack(mf.conv.conv.weight.detach().contiguous())
+        ones, zeros = ops.const_vec(Cout, 1.0, dev), ops.const_vec(Cout, 0.0, dev)
+        with torch.no_grad():
+            raw = ops.upconv3x3(xi.detach(), mf._packed_upconv(), ones, mf.conv.conv.bias.detach(), False, Cout)
+            raw3, gy3 = raw.view(B, Cout, -1), gy.view(B, Cout, -1)
+            mean, var = ops.channel_stats(raw3)
+            invstd, sc, sh = ops.bn_fwd_coeffs(mean, var, mf.conv.norm.weight, mf.conv.norm.bias, 1e-5)
+            wgt = mf.conv.conv.weight.detach()
+
+        def passes():
+            sums = ops.pointwise_bwd_stats(gy3, raw3, sc, sh, True, want_sums=True)
+            a, b, c0, _gg, _gb = ops.bn_bwd_coeffs(sums, mean, invstd, mf.conv.norm.weight, float(B * 4 * H * W))
+            g_raw3 = ops.pointwise_bwd_apply(gy3, raw3, sc, sh, True, a, b, c0)
+            ops.pointwise_bwd_stats(g_raw3, g_raw3, ones, zeros, False)
+
+        def wgrad():
+            up = torch.nn.functional.interpolate(xi.detach(), scale_factor=2)
+            torch.ops.aten.convolution_backward(gy, up, wgt, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))
+
+        fns = {"aten_fwd": lambda: ma(xi), "aten_fb": lambda: fb(ma), "fused_fwd": lambda: mf(xi), "fused_fb": lambda: fb(mf),
+               "dgrad": lambda: ops.upconv3x3_dgrad(gy, wpt, Cin), "wgrad": wgrad, "passes": passes}
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        t = {k: median(v) for k, v in timed_pairs(fns, args.rounds, args.iters).items()}
+        e = {"shape": "%d->%d @ %dx%d" % (Cin, Cout, H, W)}
+        e.update({k + "_ms": round(v, 4) for k, v in t.items()})
+        e["aten_bwd_ms"], e["fused_bwd_ms"] = round(t["aten_fb"] - t["aten_fwd"], 4), round(t["fused_fb"] - t["fused_fwd"], 4)
+        e["step_speedup"] = round(t["aten_fb"] / t["fused_fb"], 3)
+        print("deconv%d  %-16s | %9.4f %9.4f | %9.4f %9.4f | %8.4f %8.4f %8.4f | %6.2fx" % (
+            i, e["shape"], t["aten_fwd"], e["aten_bwd_ms"], t["fused_fwd"], e["fused_bwd_ms"], t["dgrad"], t["wgrad"], t["passes"], e["step_speedup"]))
+        result["train_layers"]["deconv%d" % i] = e
+    t = {k: median(v) for k, v in timed_pairs({k: (lambda d=d: step(d)) for k, d in decs.items()}, args.rounds, args.iters).items()}
+    print("DecoderConv training step (forward + backward, eager): option off %.4f ms, on %.4f ms (%.2fx), on for layers 4-6 %.4f ms (%.2fx)"
+          % (t["aten"], t["fused"], t["aten"] / t["fused"], t["fused456"], t["aten"] / t["fused456"]))
+    result["decoder_train_step"] = {k + "_ms": round(v, 4) for k, v in t.items()}
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -64,7 +162,10 @@ def main():
     ap.add_argument("--points", type=int, default=5000)
     ap.add_argument("--spin-up", type=float, default=1.0)
     ap.add_argument("--skip-forward", action="store_true", help="layers and Decoder.forward only (no encoder / Chamfer graph)")
+    ap.add_argument("--train", action="store_true", help="the training step: option off against opt.decoder_fused_train")
     args = ap.parse_args()
+    if args.train:
+        return train_bench(args)
     import bench
     from models import losses as LS, networks as NW
     from sonet_hip import ops, synth
