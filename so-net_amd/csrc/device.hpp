@@ -149,6 +149,9 @@ __device__ __forceinline__ void p16_split2(float X0, float X1, unsigned &h, unsi
 __device__ __forceinline__ void p16_split_pair(float x0, float x1, unsigned &h, unsigned &m) {
     p16_split2(32.f * __builtin_amdgcn_fmed3f(x0, -2047.f, 2047.f), 32.f * __builtin_amdgcn_fmed3f(x1, -2047.f, 2047.f), h, m);
 }
+// the WEIGHT side's clamp (the pack kernels): fmin(fmax()) and v_med3_f32 turn a NaN into the lower bound -- a finite weight nobody asked
+// for; two compares keep it, so that the packed pieces of a NaN weight are NaN as its trailer word says.  Every other value: the same bits.
+__device__ __forceinline__ float clamp_keep_nan(float w, float lim) { return w < -lim ? -lim : (w > lim ? lim : w); }
 // channel of element e (0..7) of half h in a 16-channel chunk of a P16 plane
 __device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
 

@@ -72,8 +72,8 @@ __global__ __launch_bounds__(256) void h3p_pack_kernel(const float *__restrict__
         float w0 = (o < Cout && c0 < Cin) ? W[(long long)o * Cin + c0] : 0.f;
         float w1 = (o < Cout && c1 < Cin) ? W[(long long)o * Cin + c1] : 0.f;
         range_track(wr, w0, w1);
-        w0 = 32.f * __builtin_fminf(__builtin_fmaxf(w0, -2047.f), 2047.f);
-        w1 = 32.f * __builtin_fminf(__builtin_fmaxf(w1, -2047.f), 2047.f);
+        w0 = 32.f * clamp_keep_nan(w0, 2047.f);
+        w1 = 32.f * clamp_keep_nan(w1, 2047.f);
         p16_split2(w0, w1, h[p], m[p]);
     }
     uint4 *dst = Wp + (r * 2) * 64 + lane;

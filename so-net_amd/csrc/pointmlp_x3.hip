@@ -63,8 +63,8 @@ __device__ __forceinline__ void split16_pair_med3(float x0, float x1, unsigned &
 }
 // A side: (w0, w1) -> fp16(w), fp16(32 * (w - fp16(w)))
 __device__ __forceinline__ void split16_w(float w0, float w1, unsigned &h, unsigned &res) {
-    w0 = __builtin_fminf(__builtin_fmaxf(w0, -65504.f), 65504.f);
-    w1 = __builtin_fminf(__builtin_fmaxf(w1, -65504.f), 65504.f);
+    w0 = clamp_keep_nan(w0, 65504.f);
+    w1 = clamp_keep_nan(w1, 65504.f);
     h = cvt_pk_f16(w0, w1);
     const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
     res = cvt_pk_f16(32.f * (w0 - (float)hv[0]), 32.f * (w1 - (float)hv[1]));

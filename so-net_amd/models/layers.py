@@ -79,6 +79,10 @@ class _DecayingBatchNorm(_BatchNorm):
     def forward(self, input, epoch=None):
         self._check_input_dim(input)
         self.decay_momentum(epoch)
+        if self.training and self.running_mean is not None:
+            # aten updates the running statistics WITHOUT moving their version counters (its own backward holds them as saved tensors, so
+            # they cannot be moved here either): count the updates instead -- the folded eval-mode affines (``_eval_affine``) key on it
+            self.stats_gen = getattr(self, 'stats_gen', 0) + 1
         return F.batch_norm(input, self.running_mean, self.running_var, self.weight, self.bias,
                             self.training, self.momentum, self.eps)
 
@@ -828,7 +832,7 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
         """(scale, shift) folding the conv bias and the eval-mode BatchNorm (running statistics)."""
         bn = self.norm if self.normalization == 'batch' else None
         ts = [self.conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (self.conv.weight.device,)
+        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (self.conv.weight.device, getattr(bn, 'stats_gen', 0))
         if getattr(self, '_affine_key', None) != key:
             with torch.no_grad():
                 b = self._bias().detach().float()
@@ -1033,7 +1037,7 @@ class MyLinear(_PlainAttrs, nn.Module):
         """(scale, shift) folding the bias and the eval-mode BatchNorm1d into the matrix product."""
         bn = self.norm if self.normalization == 'batch' else None
         ts = [self.linear.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts)
+        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (getattr(bn, 'stats_gen', 0),)
         if getattr(self, '_affine_key', None) != key:
             with torch.no_grad():
                 b = self.linear.bias.detach().float() if self.linear.bias is not None else torch.zeros(self.linear.out_features, device=self.linear.weight.device)

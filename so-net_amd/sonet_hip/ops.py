@@ -1244,6 +1244,7 @@ class _PackRegistry:
         if e is not None and e["ref"]() is None:                       # the storage was recycled by another tensor
             e = None
         if e is None:
+            self._drop_moved(w2d._base if w2d._base is not None else w2d)
             e = self._create(key, w2d, what)
         elif e["version"] != w2d._version:
             self.refresh(w2d.device)
@@ -1267,9 +1268,9 @@ class _PackRegistry:
         total = 64 * ((Cout_p + 31) // 32) * KC
         # (the weakref is to the view's base when there is one: views come and go, the parameter stays)
         base = w2d._base if w2d._base is not None else w2d
-        e = dict(ref=weakref.ref(base), src=w2d, version=w2d._version, buf=buf,
+        # (no strong reference to the weight: only its address, its base's address and the weakref)
+        e = dict(ref=weakref.ref(base), base_ptr=base.data_ptr(), version=w2d._version, buf=buf,
                  rec=(w2d.data_ptr() + off, buf.data_ptr(), rs, cs, total, Cin_p, rows, KC, fl))
-        e["src"] = None                                                 # (no strong reference to the weight: only its address and its weakref)
         self.entries[key] = e
         self.tables.pop(dev.index, None)
         # the entry (and its GPU buffer) goes when the weight goes -- not when some other weight next turns stale (a sweep that builds
@@ -1282,6 +1283,14 @@ class _PackRegistry:
             del self.entries[key]
             self.tables.pop(key[1], None)
 
+    def _drop_moved(self, base):
+        """``module.cpu()`` / ``.to(device)`` and ``p.data = ...`` keep the Parameter -- the weakref stays alive, the version counter goes
+        on -- but give it another storage: an entry made from the old one records an address that may be freed by now.  Such entries go
+        (host bookkeeping only; the new address gets entries of its own)."""
+        here = base.data_ptr()
+        for key, e in [(k, e) for k, e in self.entries.items() if e["ref"]() is base and e["base_ptr"] != here]:
+            self._drop(key, e)
+
     def refresh(self, device):
         """One ``sonet_pack_multi`` launch over every stale entry of ``device``."""
         import numpy as np
@@ -1291,7 +1300,7 @@ class _PackRegistry:
             if key[1] != di:
                 continue
             t = e["ref"]()
-            if t is None:
+            if t is None or t.data_ptr() != e["base_ptr"]:              # the weight is gone, or lives elsewhere now (see _drop_moved)
                 dead.append(key)
             elif e["version"] != t._version:
                 live.append((key, e, t))
