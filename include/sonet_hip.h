@@ -899,6 +899,34 @@ size_t sonet_upconv3x3_dgrad_pack_size(int Cin, int Cout);
 int sonet_upconv3x3_dgrad_pack_f32(const float *W, void *Wpt, int Cin, int Cout, sonet_stream_t stream);
 int sonet_upconv3x3_dgrad_f32(const float *g, const void *Wpt, float *dx, int B, int Cin, int Cout, int H, int W, sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * upconv3x3_wgrad  -- the weight gradient of the up-convolution above, folded (training; so-net_amd/csrc/upconv_wgrad.hip)
+ * g [B][Cout][2H][2W] f32 (the gradient of conv3x3_pad1(upsample2_nearest(x), W), as for the input gradient), x [B][Cin][H][W] f32,
+ * dw [Cout][Cin][3][3] f32 (fully overwritten, the rows past a multiple of 32 of Cin included):
+ *   dWf[py][px][dy][dx'][o][c] = sum over b, i, j of  g[b][o][2i + py][2j + px] * shifted(x, py + dy - 1, px + dx' - 1)[b][c][i][j]
+ *   dw[o][c][ky][kx] = sum of dWf[py][px][dy][dx'][o][c] over the (py, dy) whose fold range holds ky and the (px, dx') whose holds kx
+ * -- sixteen products over B H W columns, then four terms per tap -- with the zero-padded shift of the forward (element (i, j) reads
+ * x[i + sy][j + sx], zero outside the map, never another cloud) and the fold ranges {0}, {1, 2} for parity 0 and {0, 1}, {2} for parity 1.
+ * Neither the upsampled map nor a shifted copy of x is written.  Arithmetic: the three-way bf16 split of both operands (six products,
+ * smallest first, f32 accumulation in chains of SONET_UPWGRAD_FLUSH_COLS <= 1024 products, the chains of a slice added in f32); no
+ * range log.  First launch: a workgroup owns SONET_UPCONV_COUT_BLOCK output channels x SONET_UPWGRAD_CIN_BLOCK input channels over one
+ * slice of the flat column axis, in steps of SONET_UPWGRAD_K_STEP columns, and writes its sixteen partial blocks to ws (78 KB of LDS).  There is one
+ * slice per SONET_UPWGRAD_SLICE_COLS columns, at most SONET_UPWGRAD_MAX_SLICES and at most what 64 MiB of workspace hold: a
+ * function of the shape alone.  Second launch: the slices are added in order in float64, the four-term sum is applied, one rounding.  No
+ * atomics: the result is bit-reproducible on every part; both launches can be captured.  ws: sonet_upconv3x3_wgrad_ws_size bytes (0 for an
+ * unsupported shape; needs no device), every byte the second launch reads is written by the first.
+ * Alignment: g 8 bytes (the two px of a row are one load), x and dw 4 bytes, ws 16 bytes.
+ * Shapes: those of sonet_upconv3x3_dgrad_f32.  A NULL or misaligned pointer or a non-positive size returns SONET_ERR_INVALID_ARG, any other
+ * shape SONET_ERR_UNSUPPORTED, before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define SONET_UPWGRAD_K_STEP 16
+#define SONET_UPWGRAD_CIN_BLOCK 32
+#define SONET_UPWGRAD_FLUSH_COLS 256
+#define SONET_UPWGRAD_SLICE_COLS 512
+#define SONET_UPWGRAD_MAX_SLICES 128
+size_t sonet_upconv3x3_wgrad_ws_size(int B, int Cin, int Cout, int H, int W);
+int sonet_upconv3x3_wgrad_f32(const float *g, const float *x, float *dw, void *ws, int B, int Cin, int Cout, int H, int W,
+                              sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * VARIANTS build only (make -C so-net_amd/csrc variants -> libsonet_hip_variants.so, -DSONET_VARIANTS): kernels that measured
  * slower than what the product dispatches, kept as tested records of the experiments (tests/variants).  The product library
  * does not export them and reads no environment variable.

@@ -1125,16 +1125,17 @@ class _UpConvTrainFn(torch.autograd.Function):
     bias), then -- 'batch' -- the batch statistics, coefficients and running-statistics update of ``ops.bn_rider`` + ``ops.channel_stats``
     and the normalise + ReLU pass; without a norm the bias and the activation ride on the one launch.  backward: the BatchNorm / ReLU
     backward passes of the point-wise layers give g_raw, ``ops.upconv3x3_dgrad`` the input gradient (the upsampled tensor never exists
-    on that side); the weight gradient is aten's convolution backward (weight only) on the upsampled input, formed here."""
+    on that side); the weight gradient is ``ops.upconv3x3_wgrad`` on (g_raw, x) when ``fused_wgrad`` is set -- the upsampled tensor then
+    exists in neither direction -- and otherwise aten's convolution backward (weight only) on the upsampled input, formed here."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, wp, wpt, relu, eps, bn_run):
+    def forward(ctx, x, weight, bias, gamma, beta, wp, wpt, relu, eps, bn_run, fused_wgrad=False):
         B, Cin, H, W = x.shape
         Cout = weight.shape[0]
         dev = x.device
         ones = _ops.const_vec(Cout, 1.0, dev)
         b_ = bias.detach().contiguous()
-        ctx.relu, ctx.bn = bool(relu), gamma is not None
+        ctx.relu, ctx.bn, ctx.fused_wgrad = bool(relu), gamma is not None, bool(fused_wgrad)
         if ctx.bn:
             raw = _ops.upconv3x3(x, wp, ones, b_, False, Cout)
             rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
@@ -1155,7 +1156,7 @@ class _UpConvTrainFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy, *unused):
         if gy is None:
-            return (None,) * 10
+            return (None,) * 11
         saved = ctx.saved_tensors
         x, weight, wpt = saved[:3]
         B, Cin, H, W = x.shape
@@ -1180,14 +1181,16 @@ class _UpConvTrainFn(torch.autograd.Function):
         g_x = g_w = g_bias = None
         if ctx.needs_input_grad[0]:
             g_x = _ops.upconv3x3_dgrad(g_raw, wpt, Cin)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and ctx.fused_wgrad:
+            g_w = _ops.upconv3x3_wgrad(g_raw.contiguous(), x)
+        elif ctx.needs_input_grad[1]:
             up = F.interpolate(x, scale_factor=2)
             g_w = torch.ops.aten.convolution_backward(g_raw, up, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
                                                       (False, True, False))[1]
         if ctx.needs_input_grad[2]:
             s1, _ = _ops.pointwise_bwd_stats(g_raw3, g_raw3, ones, zeros, False)          # per-channel sum of g_raw, f64 on the device
             g_bias = s1.float()
-        return g_x, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None
+        return g_x, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None, None
 
 
 class UpConv(nn.Module):
@@ -1201,9 +1204,13 @@ class UpConv(nn.Module):
 
     ``fused_train`` (default False; ``DecoderConv`` sets it from ``opt.decoder_fused_train``): a TRAINING-mode call on an f32 GPU tensor
     runs ``_UpConvTrainFn`` -- the same forward launch followed by the BatchNorm passes of the point-wise layers, and the folded
-    input-gradient launch (``sonet_hip.ops.upconv3x3_dgrad``) in the backward pass; the weight gradient stays on aten -- under the same
-    conditions on precision, normalization, activation and shape.  The forward launch reports into the open range scope: in training a
-    violation switches the process to "x3" one step late (``ops.run_guarded``), after which the layer is on the aten lines."""
+    input-gradient launch (``sonet_hip.ops.upconv3x3_dgrad``) in the backward pass -- under the same conditions on precision,
+    normalization, activation and shape.  The forward launch reports into the open range scope: in training a violation switches the
+    process to "x3" one step late (``ops.run_guarded``), after which the layer is on the aten lines.
+
+    ``fused_wgrad`` (default False; ``DecoderConv`` sets it from ``opt.decoder_fused_wgrad``) acts only on a call that takes the
+    ``fused_train`` path: the weight gradient is then the folded launch ``sonet_hip.ops.upconv3x3_wgrad`` on the main stream, and the
+    upsampled map is formed in neither direction; without it the weight gradient is aten's convolution backward on the upsampled input."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, output_padding=0, bias=True,
                  activation=None, normalization=None):
@@ -1212,6 +1219,7 @@ class UpConv(nn.Module):
         self.normalization = normalization
         self.fused = False
         self.fused_train = False
+        self.fused_wgrad = False
         self.up_sample = nn.Upsample(scale_factor=2)
         self.conv = MyConv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True,
                              activation=activation, normalization=normalization)
@@ -1266,14 +1274,15 @@ class UpConv(nn.Module):
         wpt = self._packed_upconv_dgrad() if (torch.is_grad_enabled() and x.requires_grad) else None
         w = conv.conv.weight
         if self.normalization != 'batch':
-            return _UpConvTrainFn.apply(x, w, conv._bias(), None, None, self._packed_upconv(), wpt, relu, 0.0, None)
+            return _UpConvTrainFn.apply(x, w, conv._bias(), None, None, self._packed_upconv(), wpt, relu, 0.0, None, bool(self.fused_wgrad))
         bn = conv.norm
         n = x.shape[0] * 4 * x.shape[2] * x.shape[3]
         m = bn.momentum
         ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
                 and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device)
         y, mean, var = _UpConvTrainFn.apply(x, w, conv._bias(), bn.weight, bn.bias, self._packed_upconv(), wpt, relu, bn.eps,
-                                            (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None)
+                                            (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None,
+                                            bool(self.fused_wgrad))
         with torch.no_grad():
             if not ride and bn.running_mean is not None and m is not None:
                 bn.running_mean.mul_(1 - m).add_(mean, alpha=m)

@@ -708,6 +708,12 @@ class ConvToPC(nn.Module):
         return self.conv2(self.conv1(x))
 
 
+def _layer_option(opt, name, layer):
+    """A per-layer decoder option: absent / False, True (every layer) or a collection of layer numbers such as (4, 5, 6) -> bool."""
+    v = getattr(opt, name, False)
+    return v if isinstance(v, bool) else (v is not None and layer in tuple(v))
+
+
 class DecoderConv(nn.Module):
     """Up-convolution pyramid 1x1 -> 64x64 with point heads at 16x16, 32x32 and 64x64 (models/networks.py:393-431)."""
 
@@ -724,8 +730,10 @@ class DecoderConv(nn.Module):
             up.fused = bool(getattr(opt, "decoder_fused", False))
             # opt.decoder_fused_train: training runs the folded forward and input-gradient launches (layers._UpConvTrainFn) -- True = all
             # six layers, or a collection of layer numbers such as (4, 5, 6); absent = the aten layers
-            ft = getattr(opt, "decoder_fused_train", False)
-            up.fused_train = ft if isinstance(ft, bool) else (ft is not None and (i + 1) in tuple(ft))
+            up.fused_train = _layer_option(opt, "decoder_fused_train", i + 1)
+            # opt.decoder_fused_wgrad (same values): on a layer that takes the decoder_fused_train path the weight gradient is the folded
+            # launch (ops.upconv3x3_wgrad) instead of aten's on the upsampled input; without decoder_fused_train it changes nothing
+            up.fused_wgrad = _layer_option(opt, "decoder_fused_wgrad", i + 1)
             setattr(self, "deconv%d" % (i + 1), up)
             if i >= 3:
                 setattr(self, "conv2pc%d" % (i + 1), ConvToPC(chans[i + 1], opt))

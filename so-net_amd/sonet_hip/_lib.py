@@ -168,6 +168,8 @@ SIGNATURES = {
     "sonet_upconv3x3_dgrad_pack_size": [_i, _i],
     "sonet_upconv3x3_dgrad_pack_f32": [_vp, _vp, _i, _i, _vp],
     "sonet_upconv3x3_dgrad_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "sonet_upconv3x3_wgrad_ws_size": [_i, _i, _i, _i, _i],
+    "sonet_upconv3x3_wgrad_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sonet_seg_metrics_ws_size": [_i, _i, _i],
     "sonet_seg_metrics_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_retrieval_chunk_keys": [],
@@ -203,6 +205,7 @@ _RESTYPES = {
     "sonet_chamfer_loss_ws_size": ctypes.c_size_t,
     "sonet_upconv3x3_pack_size": ctypes.c_size_t,
     "sonet_upconv3x3_dgrad_pack_size": ctypes.c_size_t,
+    "sonet_upconv3x3_wgrad_ws_size": ctypes.c_size_t,
     "sonet_seg_metrics_ws_size": ctypes.c_size_t,
     "sonet_retrieval_ws_size": ctypes.c_size_t,
 }

@@ -2690,6 +2690,42 @@ def upconv3x3_dgrad(g, wpt, Cin):
     return dx
 
 
+# Tile extents of csrc/upconv_wgrad.hip (include/sonet_hip.h SONET_UPWGRAD_*): a workgroup covers UPCONV_COUT_BLOCK output channels x
+# UPWGRAD_CIN_BLOCK input channels over one slice of the flat column axis in steps of UPWGRAD_K_STEP columns; an accumulation
+# chain ends every UPWGRAD_FLUSH_COLS columns; one slice per UPWGRAD_SLICE_COLS columns, at most UPWGRAD_MAX_SLICES.
+UPWGRAD_K_STEP = 16
+UPWGRAD_CIN_BLOCK = 32
+UPWGRAD_FLUSH_COLS = 256
+UPWGRAD_SLICE_COLS = 512
+UPWGRAD_MAX_SLICES = 128
+
+
+def upconv3x3_wgrad(g, x):
+    """The weight gradient of conv3x3_pad1(upsample2_nearest(x), w) in the folded form (training): g B x Cout x 2H x 2W f32 (the gradient
+    of the convolution's output), x B x Cin x H x W f32 -> Cout x Cin x 3 x 3 f32.  Two launches under one name: sixteen (parity, tap)
+    products over the B H W columns per slice of that axis, then the float64 sum of the slices and the four-term unfold.  bf16-split (x3)
+    arithmetic: no operand range to guard.  No atomics: bit-reproducible; the call can be captured into a graph."""
+    _chk(g, "g", torch.float32, 4)
+    _chk(x, "x", torch.float32, 4)
+    B, Cout, H2, W2 = g.shape
+    Bx, Cin, H, W = x.shape
+    if B < 1 or Bx != B or H2 != 2 * H or W2 != 2 * W or not upconv3x3_supported(Cin, Cout, H, W):
+        raise SonetHipError("upconv3x3_wgrad: unsupported shape g %s, x %s (g B x Cout x 2H x 2W, x B x Cin x H x W, Cout %% %d == 0, "
+                            "1 <= H, W <= %d)" % (tuple(g.shape), tuple(x.shape), UPCONV_COUT_BLOCK, UPCONV_MAX_HW))
+    dev = _same_device(g, x)
+    lib = _lib.load()
+    nbytes = lib.sonet_upconv3x3_wgrad_ws_size(B, Cin, Cout, H, W)
+    if nbytes == 0:
+        raise SonetHipError("upconv3x3_wgrad: unsupported shape B=%d Cin=%d Cout=%d H=%d W=%d" % (B, Cin, Cout, H, W))
+    if g.data_ptr() % 8 or x.data_ptr() % 4:
+        raise SonetHipError("upconv3x3_wgrad: g must be 8-byte and x 4-byte aligned")
+    dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev), _timed("upconv3x3_wgrad_%dx%d_%dx%d" % (Cin, Cout, H, W)):
+        check(lib.sonet_upconv3x3_wgrad_f32(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cin, Cout, H, W, stream_ptr()), "sonet_upconv3x3_wgrad_f32")
+    return dw
+
+
 # ------------------------------------------------------------------------------------------ segmentation metrics
 SHAPENET_PART_OFFSETS = (0, 4, 6, 8, 12, 16, 19, 22, 24, 28, 30, 36, 38, 41, 44, 47, 50)    # models/losses.py:126-143 as a CSR table
 SEG_METRICS_MAX_C = 256

@@ -18,7 +18,10 @@ events on the launch stream -- and the median over the rounds is reported:
 opt.decoder_fused_train (layers._UpConvTrainFn), interleaved in the same way.  Per layer: the forward (autograd on), forward + backward
 and their difference, and for the fused backward its parts timed on their own -- the folded input gradient (ops.upconv3x3_dgrad), the
 weight gradient (upsample + aten's convolution backward, weight only) and the BatchNorm / ReLU / bias passes; then one training step of
-the whole DecoderConv (forward + backward on fixed cotangents), option off, on, and on for layers (4, 5, 6).
+the whole DecoderConv (forward + backward on fixed cotangents), option off, on, and on for layers (4, 5, 6).  A third variant,
+opt.decoder_fused_train plus opt.decoder_fused_wgrad, is interleaved with the two: per layer the folded weight-gradient launch
+(ops.upconv3x3_wgrad, column "wgrad hip") beside the aten weight gradient it replaces (column "wgrad") and the layer's step with it, and
+the DecoderConv step with it on all six layers and on (4, 5, 6).
 Prints a table and one JSON line (last line).
 """
 import argparse
@@ -69,14 +72,15 @@ def train_bench(args):
     dev = torch.device("cuda", 0)
     B, F_ = args.batch, 1024
 
-    def make(train_opt):
+    def make(train_opt, wgrad_opt=False):
         opt = Namespace(gpu_id=0, device=dev, feature_num=F_, activation="relu", normalization="batch", output_fc_pc_num=0,
-                        output_conv_pc_num=4096, decoder_fused_train=train_opt)
+                        output_conv_pc_num=4096, decoder_fused_train=train_opt, decoder_fused_wgrad=wgrad_opt)
         d = NW.Decoder(opt)
         synth.fill_state_dict_(d.state_dict(), 2)
         return d.to(dev).train()
 
-    decs = {"aten": make(False), "fused": make(True), "fused456": make((4, 5, 6))}
+    decs = {"aten": make(False), "fused": make(True), "fused456": make((4, 5, 6)), "wgrad": make(True, True),
+            "wgrad456": make((4, 5, 6), (4, 5, 6))}
     feat = torch.randn(B, F_, generator=torch.Generator().manual_seed(5)).abs().to(dev)
     gen = torch.Generator().manual_seed(6)
     cots = {i: (torch.randn(B, 3, n, generator=gen) * 1e-3).to(dev) for i, n in ((4, 256), (5, 1024), (6, 4096))}
@@ -100,10 +104,11 @@ def train_bench(args):
             step(d)
     torch.cuda.synchronize()
     bench._spin_up(lambda: [step(d) for d in decs.values()], args.spin_up)
-    print("%-8s %-16s | %9s %9s | %9s %9s | %8s %8s %8s | %7s" % ("layer", "Cin->Cout @ HxW", "aten fwd", "aten bwd", "fused fwd", "fused bwd",
-                                                                 "dgrad", "wgrad", "passes", "step x"))
+    print("%-8s %-16s | %9s %9s | %9s %9s %9s | %8s %8s %9s %8s | %7s %7s" % (
+        "layer", "Cin->Cout @ HxW", "aten fwd", "aten bwd", "fused fwd", "fused bwd", "+wgrad bwd", "dgrad", "wgrad", "wgrad hip", "passes",
+        "step x", "+wgrad x"))
     for i in range(1, 7):
-        ma, mf = (getattr(decs[k].conv_decoder, "deconv%d" % i) for k in ("aten", "fused"))
+        ma, mf, mw = (getattr(decs[k].conv_decoder, "deconv%d" % i) for k in ("aten", "fused", "wgrad"))
         xi = xs[i - 1].clone().requires_grad_(True)
         Cin, Cout, H, W = xi.shape[1], ma.conv.conv.out_channels, xi.shape[2], xi.shape[3]
         gy = torch.randn(B, Cout, 2 * H, 2 * W, generator=torch.Generator().manual_seed(i)).to(dev) * 1e-3
@@ -134,8 +139,10 @@ def train_bench(args):
             up = torch.nn.functional.interpolate(xi.detach(), scale_factor=2)
             torch.ops.aten.convolution_backward(gy, up, wgt, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))
 
+        xd = xi.detach()
         fns = {"aten_fwd": lambda: ma(xi), "aten_fb": lambda: fb(ma), "fused_fwd": lambda: mf(xi), "fused_fb": lambda: fb(mf),
-               "dgrad": lambda: ops.upconv3x3_dgrad(gy, wpt, Cin), "wgrad": wgrad, "passes": passes}
+               "wgrad_fb": lambda: fb(mw), "dgrad": lambda: ops.upconv3x3_dgrad(gy, wpt, Cin), "wgrad": wgrad,
+               "wgrad_hip": lambda: ops.upconv3x3_wgrad(gy, xd), "passes": passes}
         for fn in fns.values():
             for _ in range(3):
                 fn()
@@ -143,13 +150,17 @@ def train_bench(args):
         e = {"shape": "%d->%d @ %dx%d" % (Cin, Cout, H, W)}
         e.update({k + "_ms": round(v, 4) for k, v in t.items()})
         e["aten_bwd_ms"], e["fused_bwd_ms"] = round(t["aten_fb"] - t["aten_fwd"], 4), round(t["fused_fb"] - t["fused_fwd"], 4)
-        e["step_speedup"] = round(t["aten_fb"] / t["fused_fb"], 3)
-        print("deconv%d  %-16s | %9.4f %9.4f | %9.4f %9.4f | %8.4f %8.4f %8.4f | %6.2fx" % (
-            i, e["shape"], t["aten_fwd"], e["aten_bwd_ms"], t["fused_fwd"], e["fused_bwd_ms"], t["dgrad"], t["wgrad"], t["passes"], e["step_speedup"]))
+        e["wgrad_bwd_ms"] = round(t["wgrad_fb"] - t["fused_fwd"], 4)
+        e["step_speedup"], e["wgrad_step_speedup"] = round(t["aten_fb"] / t["fused_fb"], 3), round(t["aten_fb"] / t["wgrad_fb"], 3)
+        print("deconv%d  %-16s | %9.4f %9.4f | %9.4f %9.4f %9.4f | %8.4f %8.4f %9.4f %8.4f | %6.2fx %6.2fx" % (
+            i, e["shape"], t["aten_fwd"], e["aten_bwd_ms"], t["fused_fwd"], e["fused_bwd_ms"], e["wgrad_bwd_ms"], t["dgrad"], t["wgrad"],
+            t["wgrad_hip"], t["passes"], e["step_speedup"], e["wgrad_step_speedup"]))
         result["train_layers"]["deconv%d" % i] = e
     t = {k: median(v) for k, v in timed_pairs({k: (lambda d=d: step(d)) for k, d in decs.items()}, args.rounds, args.iters).items()}
     print("DecoderConv training step (forward + backward, eager): option off %.4f ms, on %.4f ms (%.2fx), on for layers 4-6 %.4f ms (%.2fx)"
           % (t["aten"], t["fused"], t["aten"] / t["fused"], t["fused456"], t["aten"] / t["fused456"]))
+    print("... with decoder_fused_wgrad as well: on %.4f ms (%.2fx), both on for layers 4-6 %.4f ms (%.2fx)"
+          % (t["wgrad"], t["aten"] / t["wgrad"], t["wgrad456"], t["aten"] / t["wgrad456"]))
     result["decoder_train_step"] = {k + "_ms": round(v, 4) for k, v in t.items()}
     print(json.dumps(result))
 
