@@ -405,6 +405,16 @@ int sonet_knn_gather_bwd_bf16(const uint16_t *g, const int64_t *knn_I, float *gx
 size_t sonet_node_gather_bwd_ws_size(int B, int M, int L);
 int sonet_node_gather_bwd_f32(const float *g, const int32_t *ids, float *gx, void *ws, int B, int C, int M, int L, sonet_stream_t stream);
 int sonet_node_gather_bwd_bf16(const uint16_t *g, const int32_t *ids, float *gx, void *ws, int B, int C, int M, int L, sonet_stream_t stream);
+/* sonet_pointwise_bwd_apply_f32 and sonet_node_gather_bwd_f32 of what it stores in ONE pass over (gy, raw) -- the backward of a layer with a
+ * per-node addend (sonet_pointmlp_h3_nodeadd_stats_f32): g_raw [B][C][L] = a[c]*(gy*mask) + b[c]*raw + c0[c] and gz [B][C][M] = its sum
+ * over every node's columns in ascending column order, one f32 chain per (b, c, m): the bits of the two launches.  No atomics.
+ *   ws: sonet_pointwise_bwd_apply_nodesum_ws_size(B, M, L) bytes; M <= 1024; ids outside [0, M) contribute nowhere.
+ *   sonet_pointwise_bwd_apply_nodesum_tile(): columns per tile of the pass (the sums are carried from tile to tile). */
+size_t sonet_pointwise_bwd_apply_nodesum_ws_size(int B, int M, int L);
+int sonet_pointwise_bwd_apply_nodesum_tile(void);
+int sonet_pointwise_bwd_apply_nodesum_f32(const float *gy, const float *raw, const float *scale, const float *shift, int relu,
+                                          const float *a, const float *b, const float *c0, const int32_t *ids, int M,
+                                          float *g_raw, float *gz, void *ws, int B, int C, int L, sonet_stream_t stream);
 
 /* The same layer with bf16 STORAGE and bf16 MFMA (BASELINE configs[1] "bf16"; the reference is f32-only, so this is the
  * reduced-precision twin of models/layers.py:282-296, not a bit-compatible replacement): x1, x2, y are bfloat16 bit
@@ -579,6 +589,12 @@ int sonet_pointmlp_x3_stats_f32(const float *x1, int C1, const float *x2, int C2
 int sonet_pointmlp_h3_nodeadd_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3, const float *scale,
                                   const float *shift, int relu, float *y, int B, int Cout, int L,
                                   const float *zadd, const int32_t *zidx, int ZM, sonet_stream_t stream);
+/* ... that also returns the batch statistics of y over (B, L) from the epilogue, as sonet_pointmlp_h3_stats_f32: the TRAINING forward of
+ * that layer (the addend is part of what is stored and of what the statistics see).  stats_ws: sonet_pointmlp_stats_ws_size bytes. */
+int sonet_pointmlp_h3_nodeadd_stats_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3, const float *scale,
+                                        const float *shift, int relu, float *y, int B, int Cout, int L,
+                                        const float *zadd, const int32_t *zidx, int ZM, void *stats_ws,
+                                        float *mean, float *var, sonet_stream_t stream);
 
 /* bf16 twin: statistics of the STORED bf16 values (what the normalise pass and the backward read). */
 size_t sonet_pointmlp_bf16_stats_ws_size(int B, int Cout, int L);

@@ -157,6 +157,110 @@ __global__ __launch_bounds__(256) void node_gather_bwd_kernel(const T *__restric
     gx[t] = s;
 }
 
+// The BatchNorm / ReLU backward of a layer (bwd_apply_kernel of pointwise_bwd.hip, operation for operation) and the per-node sums of what
+// it stores in ONE pass over (gy, raw): the gradient of a per-node addend (segmenter layer 1 in its node-wise form) is the sum of
+// g_raw over every node's columns, and a second launch would read the stored tensor again.  A workgroup owns ANS_ROWS channel rows of
+// one cloud and walks them in tiles of ANS_TILE columns: g_raw is computed, stored and kept in LDS; then one thread per (row, node)
+// adds the node's columns of the tile -- the next entries of its inverse list, which ascends -- to the partial sum it carries from tile
+// to tile: one f32 chain per (b, c, m) in ascending column order, the bits of node_gather_bwd_kernel.  A pair p = row * M + m is always
+// served by thread p % ANS_THREADS, so its partial sum and list cursor need no barrier of their own.
+constexpr int ANS_ROWS = 4, ANS_TILE = 1024, ANS_THREADS = 256;
+template <bool VEC>
+__global__ __launch_bounds__(ANS_THREADS) void bwd_apply_nodesum_kernel(const float *__restrict__ gy, const float *__restrict__ raw,
+                                                                         const float *__restrict__ scale, const float *__restrict__ shift, int relu,
+                                                                         const float *__restrict__ ca, const float *__restrict__ cb,
+                                                                         const float *__restrict__ cc, const int32_t *__restrict__ off,
+                                                                         const int32_t *__restrict__ list, float *__restrict__ out,
+                                                                         float *__restrict__ gz, int C, int L, int M, int row_groups)
+{
+    extern __shared__ float ans_lds[];
+    float *tile = ans_lds;                                    // [ANS_ROWS][ANS_TILE] g_raw of the current tile
+    float *psum = tile + ANS_ROWS * ANS_TILE;                 // [ANS_ROWS * M] partial sums
+    int *cur = reinterpret_cast<int *>(psum + (size_t)ANS_ROWS * M);     // [ANS_ROWS * M] next list entry of the pair
+    const size_t b = blockIdx.x / (unsigned)row_groups;
+    const int c_first = (int)(blockIdx.x % (unsigned)row_groups) * ANS_ROWS;
+    const int nrows = min(ANS_ROWS, C - c_first);
+    const int32_t *o = off + b * (size_t)(M + 1);
+    const int32_t *lst = list + b * (size_t)L;
+    const int npairs = nrows * M;
+    for (int p = threadIdx.x; p < npairs; p += ANS_THREADS) {
+        psum[p] = 0.f;
+        cur[p] = o[p % M];
+    }
+    float sc[ANS_ROWS], sh[ANS_ROWS], a[ANS_ROWS], bb[ANS_ROWS], c0[ANS_ROWS];
+#pragma unroll
+    for (int r = 0; r < ANS_ROWS; ++r) {
+        const int c = min(c_first + r, C - 1);
+        sc[r] = scale[c]; sh[r] = shift[c]; a[r] = ca[c]; bb[r] = cb[c]; c0[r] = cc[c];
+    }
+    const size_t row0 = (b * (size_t)C + (size_t)c_first) * (size_t)L;
+    for (int t0 = 0; t0 < L; t0 += ANS_TILE) {
+        const int tlen = min(ANS_TILE, L - t0);
+        __syncthreads();                                      // (the walk over the previous tile is over)
+#pragma unroll
+        for (int r = 0; r < ANS_ROWS; ++r) {
+            if (r >= nrows) break;
+            const size_t base = row0 + (size_t)r * (size_t)L + (size_t)t0;
+            if constexpr (VEC) {                              // (L % 4 == 0 and 16-byte aligned operands: so is every row and tile)
+                for (int i = threadIdx.x * 4; i < tlen; i += ANS_THREADS * 4) {
+                    const float4 rv = *reinterpret_cast<const float4 *>(raw + base + i);
+                    const float4 gv = *reinterpret_cast<const float4 *>(gy + base + i);
+                    const float rr[4] = {rv.x, rv.y, rv.z, rv.w};
+                    float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+                    float ov[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (relu && !(__fmaf_rn(rr[e], sc[r], sh[r]) > 0.f)) gg[e] = 0.f;
+                        ov[e] = __fmaf_rn(a[r], gg[e], __fmaf_rn(bb[r], rr[e], c0[r]));
+                    }
+                    const float4 o4 = make_float4(ov[0], ov[1], ov[2], ov[3]);
+                    *reinterpret_cast<float4 *>(out + base + i) = o4;
+                    *reinterpret_cast<float4 *>(tile + r * ANS_TILE + i) = o4;
+                }
+            } else {
+                for (int i = threadIdx.x; i < tlen; i += ANS_THREADS) {
+                    const float rv = raw[base + i];
+                    float gv = gy[base + i];
+                    if (relu && !(__fmaf_rn(rv, sc[r], sh[r]) > 0.f)) gv = 0.f;
+                    const float ov = __fmaf_rn(a[r], gv, __fmaf_rn(bb[r], rv, c0[r]));
+                    out[base + i] = ov;
+                    tile[r * ANS_TILE + i] = ov;
+                }
+            }
+        }
+        __syncthreads();
+        const int tend = t0 + tlen;
+        for (int p = threadIdx.x; p < npairs; p += ANS_THREADS) {
+            const int r = p / M, m = p - r * M;
+            const int end = o[m + 1];
+            const float *tr = tile + r * ANS_TILE;            // (every column read lies in [t0, tend): the list ascends)
+            int k = cur[p];
+            float s = psum[p];
+            bool more = true;
+            while (more && k < end) {
+                // four list entries per round trip (clamped to the node's own range), added strictly in list order
+                int col[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) col[e] = lst[min(k + e, end - 1)];
+                const int n = min(4, end - k);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (more && e < n) {
+                        if (col[e] < tend) { s += tr[col[e] - t0]; ++k; }
+                        else more = false;
+                    }
+                }
+            }
+            psum[p] = s;
+            cur[p] = k;
+        }
+    }
+    for (int p = threadIdx.x; p < npairs; p += ANS_THREADS) {
+        const int r = p / M, m = p - r * M;
+        gz[(b * (size_t)C + (size_t)(c_first + r)) * (size_t)M + (size_t)m] = psum[p];
+    }
+}
+
 }  // namespace
 
 template <typename T>
@@ -254,4 +358,37 @@ extern "C" int sonet_node_gather_bwd_f32(const float *g, const int32_t *ids, flo
 extern "C" int sonet_node_gather_bwd_bf16(const uint16_t *g, const int32_t *ids, float *gx, void *ws, int B, int C, int M, int L, sonet_stream_t stream)
 {
     return node_gather_bwd_impl("sonet_node_gather_bwd_bf16", g, ids, gx, ws, B, C, M, L, stream);
+}
+
+extern "C" size_t sonet_pointwise_bwd_apply_nodesum_ws_size(int B, int M, int L)
+{
+    return sonet_node_gather_bwd_ws_size(B, M, L);               // the inverse lists of node_inverse_kernel
+}
+
+extern "C" int sonet_pointwise_bwd_apply_nodesum_tile(void) { return ANS_TILE; }
+
+/* sonet_pointwise_bwd_apply_f32 and sonet_node_gather_bwd_f32 of what it stores, in one pass over (gy, raw): g_raw [B][C][L] and
+ * gz[b][c][m] = the sum of g_raw[b][c][l] over the columns with ids[b][l] == m in ascending column order (one f32 chain), the bits of
+ * the two launches.  No atomics, no host synchronisation. */
+extern "C" int sonet_pointwise_bwd_apply_nodesum_f32(const float *gy, const float *raw, const float *scale, const float *shift, int relu,
+                                                     const float *a, const float *b, const float *c0, const int32_t *ids, int M,
+                                                     float *g_raw, float *gz, void *ws, int B, int C, int L, sonet_stream_t stream)
+{
+    const char *what = "sonet_pointwise_bwd_apply_nodesum_f32";
+    SONET_REQUIRE(gy && raw && scale && shift && a && b && c0 && ids && g_raw && gz && ws, "%s: NULL pointer", what);
+    SONET_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, "%s: bad size B=%d C=%d M=%d L=%d", what, B, C, M, L);
+    if (M > 1024) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: M=%d > 1024", what, M);
+    const int row_groups = sonet::ceil_div(C, ANS_ROWS);
+    const long long nwg = (long long)B * row_groups;
+    if (nwg > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too large", what);
+    int32_t *off = reinterpret_cast<int32_t *>(ws), *list = off + (size_t)B * (M + 1);
+    hipStream_t s = sonet::as_stream(stream);
+    hipLaunchKernelGGL(node_inverse_kernel, dim3((unsigned)B), dim3(1024), 0, s, ids, M, L, off, list);
+    const size_t lds = ((size_t)ANS_ROWS * ANS_TILE + 2 * (size_t)ANS_ROWS * M) * sizeof(float);      // <= 48 KiB at M = 1024
+    const bool vec = L % 4 == 0 && (((uintptr_t)gy | (uintptr_t)raw | (uintptr_t)g_raw) & 15) == 0;
+    if (vec) hipLaunchKernelGGL(bwd_apply_nodesum_kernel<true>, dim3((unsigned)nwg), dim3(ANS_THREADS), lds, s, gy, raw, scale, shift, relu,
+                                a, b, c0, off, list, g_raw, gz, C, L, M, row_groups);
+    else     hipLaunchKernelGGL(bwd_apply_nodesum_kernel<false>, dim3((unsigned)nwg), dim3(ANS_THREADS), lds, s, gy, raw, scale, shift, relu,
+                                a, b, c0, off, list, g_raw, gz, C, L, M, row_groups);
+    return sonet::launched(what);
 }

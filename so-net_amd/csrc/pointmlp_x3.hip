@@ -650,6 +650,9 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
             // a second pass over the tensor.  A row's 32 columns sit in the 32 lanes of a half wave: four DPP adds + one swizzle per
             // quantity, all lanes active (a padded column stores to an out-of-range offset -- dropped by the descriptor -- and adds 0).
             const unsigned voy_s = pv ? voy : 0x7FFFFF00u;
+            // (the addend form below exists in the plain fp16-split instantiations only: x3_run_impl launches no other with both)
+            constexpr bool ZSTATS = F16 && !ZADD && !SEGPOOL && !XAFF && !BNB;
+            if (!ZSTATS || zadd == nullptr) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const unsigned so_tile = (unsigned)((ct0 + mt) * 32) * rowB;
@@ -664,6 +667,31 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                     const float sv = pv ? v : 0.f;
                     const float s1 = row32_sum(sv), s2 = row32_sum(sv * sv);
                     if (j == 0) red[wave][mt * 32 + orow + 4 * h] = make_float2(s1, s2);
+                }
+            }
+            } else {
+                // ... of a layer with a per-node addend (the training forward of the segmenter's first layer): the addend is gathered
+                // and added as in the branch below, operation for operation; a padded column's lane reads no addend and adds 0
+                const int zm = zidx[b * L + lc];
+                const bool zok = pv && (unsigned)zm < (unsigned)ZM;
+                const float *zb = zadd + ((size_t)b * Cout) * ZM + (zok ? zm : 0);
+                const float unscale = F16 ? 32.f : 1.f;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const unsigned so_tile = (unsigned)((ct0 + mt) * 32) * rowB;
+                    const float2 *aff = affine + (ct0 + mt - ct_begin) * 32 + 4 * h;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int orow = (r & 3) + 8 * (r >> 2);
+                        const float2 ss = aff[orow];
+                        const float zv = zok ? zb[(size_t)((ct0 + mt) * 32 + orow + 4 * h) * ZM] : 0.f;
+                        float v = __fmaf_rn(acc[mt][r], ss.x, __fmaf_rn(zv, ss.x * unscale, ss.y));
+                        if (relu) v = (v < 0.f) ? 0.f : v;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy_s, so_tile + (unsigned)orow * rowB, 0);
+                        const float sv = pv ? v : 0.f;
+                        const float s1 = row32_sum(sv), s2 = row32_sum(sv * sv);
+                        if (j == 0) red[wave][mt * 32 + orow + 4 * h] = make_float2(s1, s2);
+                    }
                 }
             }
             __syncthreads();
@@ -1212,6 +1240,7 @@ static int x3_run_impl(const X3Run &r)
     SONET_REQUIRE(!bnbp || ((bnbp->praw == nullptr) == (bnbp->pstats == nullptr) && (bnbp->pstats == nullptr) == (r.psums == nullptr) &&
                             (!bnbp->praw || (bnbp->psc && bnbp->psh))), "%s: the sums of the layer below need praw, psc, psh, a workspace and the output", what);
     SONET_REQUIRE(!bnbp || !bnbp->yadd || !bnbp->pstats, "%s: an accumulated output and the sums of the layer below do not combine", what);
+    SONET_REQUIRE(!(zadd && stats_ws) || (f16 && !gidx && !kmax), "%s: the statistics of a layer with a per-node addend take the plain fp16-split layer", what);
     const BnbArgs bnb = bnbp ? *bnbp : BnbArgs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     if (const int rc = sonet::check_layer_shape(what, x2 != nullptr, B, C1, C2, Cout, L)) return rc;
     if (Cout % 32 != 0) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout=%d must be a multiple of 32", what, Cout);
@@ -1250,6 +1279,7 @@ static int x3_run_impl(const X3Run &r)
     int h3r = h3r_pick && !zadd;
     sonet::knob_int("SONET_POINTMLP_H3R", &h3r);                 // bench-only: 0 = the first-generation pipeline
     if (NC == 0 && !segpool && !xaff && f16 && CT % H3R_MT == 0 && (kmax || h3r != 0)) NC = 1;
+    if (zadd && stats_ws) NC = 0;                                // (statistics of a layer with a per-node addend: the staged kernel's epilogue only)
     if (NC != 0) {
         const int gpc_n = sonet::ceil_div(L, 32 * NC);
         const long long ngroups_n = (long long)B * gpc_n, nwg_n = sonet::ceil_div64(ngroups_n, (long long)X3_WAVES);
@@ -1486,6 +1516,22 @@ extern "C" int sonet_pointmlp_h3_stats_xaff_f32(const float *x1, int C1, const f
     X3Run r{"sonet_pointmlp_h3_stats_xaff_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
     r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
     r.xaff = &xa;
+    return x3_run_impl(r);
+}
+
+/* sonet_pointmlp_h3_nodeadd_f32 that also returns the batch statistics of y, as sonet_pointmlp_h3_stats_f32 does: the training forward
+ * of a layer whose per-node and per-cloud input channels were multiplied once per node (zadd).  The addend is part of what is stored
+ * and of what the statistics see. */
+extern "C" int sonet_pointmlp_h3_nodeadd_stats_f32(const float *x1, int C1, const float *x2, int C2, const void *Wp3, const float *scale,
+                                                   const float *shift, int relu, float *y, int B, int Cout, int L,
+                                                   const float *zadd, const int32_t *zidx, int ZM, void *stats_ws,
+                                                   float *mean, float *var, sonet_stream_t stream)
+{
+    SONET_REQUIRE(zadd && zidx && ZM > 0, "sonet_pointmlp_h3_nodeadd_stats_f32: NULL pointer or ZM <= 0");
+    SONET_REQUIRE(stats_ws && mean && var, "sonet_pointmlp_h3_nodeadd_stats_f32: NULL pointer");
+    X3Run r{"sonet_pointmlp_h3_nodeadd_stats_f32", true, x1, C1, x2, C2, Wp3, scale, shift, relu, y, B, Cout, L, stream};
+    r.zadd = zadd; r.zidx = zidx; r.ZM = ZM;
+    r.stats_ws = reinterpret_cast<double *>(stats_ws); r.mean = mean; r.var = var;
     return x3_run_impl(r);
 }
 

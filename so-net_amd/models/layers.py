@@ -518,6 +518,83 @@ class _PointwiseFn(torch.autograd.Function):
         return g_x1, g_x2, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None, None, None, None, None, None
 
 
+class _NodewiseLayerFn(torch.autograd.Function):
+    """Training-mode BatchNorm (+ ReLU) layer whose input concatenates per-column channels x_p = cat(x1, x2), channels that are constant
+    per node x_n = cat(node_lead, node_maps) (B x Cn x M, broadcast back through ``ids``) and channels that are constant per cloud
+    x_g = cat(glob_lead, glob) (B x Cg) -- segmenter layer 1 -- in its split form, in both directions:
+
+        raw = W_p . x_p + (W_n . x_n + W_g . x_g)[node of the column] + bias
+
+    forward: the per-node block on the layer kernel over M columns per cloud, a B-row matmul for the per-cloud block, then ONE launch
+    over the columns (``ops.pointmlp_nodeadd_stats``: the addend and the batch statistics in the epilogue) and the normalise pass.
+    backward: ``pointwise_bwd_stats`` -> ``bn_bwd_coeffs`` -> ``ops.pointwise_bwd_apply_nodesum`` (g_raw and its per-node sums gz in one
+    pass); the gradient of the per-node block is a function of gz alone: W_n^T . gz, gz . x_n^T, and sum_m gz for the per-cloud block;
+    the per-column block's weight gradient is one launch over cat(x1, x2).
+    Neither the broadcast tensors nor their gradients exist.  x2, node_lead and glob_lead get no gradient (the reference detaches them).
+
+    ``split`` = (wp_point, wp_node, w_glob, wpt_x1, wpt_maps, cols): the h3 packs of W_p and W_n, W_g as a matrix, the transposed (x3)
+    packs of W's x1 and node_maps columns, and cols = the (lo, hi) column ranges in W of (x1, x2 parts ..., node_lead, node_maps,
+    glob_lead, glob) -- ``Segmenter._layer1_split_train``."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, node_lead, node_maps, glob_lead, glob, weight2d, bias, gamma, beta, ids, split, relu, eps, bn_run):
+        wp_point, wp_node, w_glob = split[:3]
+        Cout = weight2d.shape[0]
+        dev = x1.device
+        ones, zeros = _ops.const_vec(Cout, 1.0, dev), _ops.const_vec(Cout, 0.0, dev)
+        x_n = torch.cat((node_lead, node_maps), dim=1).contiguous()
+        x_g = torch.cat((glob_lead, glob), dim=1)
+        z = (_ops.pointmlp(x_n, wp_node, ones, zeros, False, Cout) + (x_g @ w_glob.t()).unsqueeze(2)).contiguous()
+        rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
+        invstd, sc, sh = _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+        raw, mean, var = _ops.pointmlp_nodeadd_stats(x1, wp_point, bias.detach().contiguous(), Cout, z, ids, x2=x2)
+        y = _ops.channel_affine_act(raw, sc, sh, relu)
+        # (the first ten in the order of _PointwiseFn's 'batch' mode: x1, x2, weight2d, sc, sh, raw, mean, invstd, gamma, zeros)
+        ctx.save_for_backward(x1, x2, weight2d, sc, sh, raw, mean, invstd, gamma, zeros, x_n, x_g, ids)
+        ctx.mark_non_differentiable(mean, var)
+        ctx.set_materialize_grads(False)
+        ctx.relu, ctx.split, ctx.M, ctx.n_lead = relu, split, x_n.shape[2], glob_lead.shape[1]
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, gy, *unused):
+        if gy is None:
+            return (None,) * 15
+        x1, x2, weight2d, sc, sh, raw, mean, invstd, gamma, zeros, x_n, x_g, ids = ctx.saved_tensors
+        w_glob, wpt_x1, wpt_maps, cols = ctx.split[2:6]
+        gy = gy.contiguous()
+        n = float(raw.shape[0] * raw.shape[2])
+        sums = _ops.pointwise_bwd_stats(gy, raw, sc, sh, ctx.relu, want_sums=True)
+        a, b, c0, g_gamma, g_beta = _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, n)
+        g_raw, gz = _ops.pointwise_bwd_apply_nodesum(gy, raw, sc, sh, ctx.relu, a, b, c0, ids, ctx.M)
+        need = ctx.needs_input_grad
+        gsum = gz.sum(dim=2)                                              # B x Cout: the per-cloud block saw every node's addend
+        g_x1 = _dgrad(g_raw, wpt_x1) if need[0] else None
+        g_maps = _dgrad(gz, wpt_maps) if need[3] else None
+        g_glob = (gsum @ w_glob[:, ctx.n_lead:]) if need[5] else None
+        g_w = None
+        if need[6]:
+            g_w = torch.empty_like(weight2d)
+            (lo, hi), x2_cols, lead_cols, maps_cols, glead_cols, glob_cols = cols
+            # (one weight-gradient launch over cat(x1, x2): g_raw, the large operand, is read once)
+            g_wp = _wgrad(g_raw, torch.cat((x1, x2), dim=1))
+            g_w[:, lo:hi] = g_wp[:, :hi - lo]
+            g_w2 = g_wp[:, hi - lo:]
+            at = 0
+            for lo, hi in x2_cols:                                        # (x2's channels sit in several column blocks of W)
+                g_w[:, lo:hi] = g_w2[:, at:at + hi - lo]
+                at += hi - lo
+            g_wn = _wgrad(gz, x_n)
+            nl = lead_cols[1] - lead_cols[0]
+            g_w[:, lead_cols[0]:lead_cols[1]] = g_wn[:, :nl]
+            g_w[:, maps_cols[0]:maps_cols[1]] = g_wn[:, nl:]
+            g_wg = gsum.t() @ x_g
+            g_w[:, glead_cols[0]:glead_cols[1]] = g_wg[:, :ctx.n_lead]
+            g_w[:, glob_cols[0]:glob_cols[1]] = g_wg[:, ctx.n_lead:]
+        g_bias = zeros.clone() if need[7] else None                       # a bias in front of BatchNorm has no gradient
+        return g_x1, None, None, g_maps, None, g_glob, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None
+
+
 class _PooledLastLayerFn(torch.autograd.Function):
     """Last (norm-free, activation-free) layer of the first PointNet + per-node arg-max pool as ONE autograd node
     (models/layers.py:431 + models/networks.py:180-185).  Outputs (first_pn_out, first_pn_out_masked_max).  When only

@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from sonet_hip import ops as _ops
 from util import som
-from .layers import EquivariantLayer, KNNModule, MyLinear, PointNet, PointResNet, _PlainAttrs  # noqa: F401
+from .layers import EquivariantLayer, KNNModule, MyLinear, PointNet, PointResNet, _NodewiseLayerFn, _PlainAttrs  # noqa: F401
 
 
 def _head_inference(fn):
@@ -597,6 +597,72 @@ class Segmenter(_PlainAttrs, nn.Module):
             h = _ops.node_add_affine_act_(t.float(), z, min_idx_i32, scale, shift, lyr.activation == 'relu')
         return self._tail(self.layer3(self.layer2(h)), k)
 
+    # ---- node-wise layer 1 in TRAINING (``opt.seg_nodewise_train``) -----------------------------------------------------------
+    # The same split in both directions (``layers._NodewiseLayerFn``): the three gathered maps, the expanded feature, the 3356-channel
+    # concat and their gradients are never formed; the per-node block's gradients come from the per-node sums of g_raw.
+    def _layer1_split_train(self):
+        """Per weight version: (h3 pack of W_p, h3 pack of W_n, W_g, transposed x3 packs of W's ``first`` and node-map columns, the
+        column ranges of every block in W)."""
+        lyr = self.layer1
+        w = lyr.conv.weight
+        key = (w._version, w.data_ptr(), w.device)
+        if getattr(self, "_l1t_key", None) != key:
+            with torch.no_grad():
+                W = lyr._weight2d().detach()
+                blk = self._layer1_blocks()
+                cols = lambda names: torch.cat([W[:, blk[n][0]:blk[n][1]] for n in names], dim=1).contiguous()
+                small = [n for n in ("x_dec", "x", "sn") if blk[n][1] > blk[n][0]]
+                maps = (blk["fm_first"][0], blk["fm_final"][1])               # fm_first | fm_knn | fm_final: adjacent in W
+                assert blk["fm_first"][1] == blk["fm_knn"][0] and blk["fm_knn"][1] == blk["fm_final"][0]
+                c_first, c_maps = blk["first"][1] - blk["first"][0], maps[1] - maps[0]
+                ranges = (blk["first"], tuple(blk[n] for n in small), blk["centers"], maps, blk["onehot"], blk["feature"])
+                covered = sum(hi - lo for lo, hi in (ranges[0],) + ranges[1] + ranges[2:])
+                assert covered == W.shape[1], (covered, W.shape[1])
+                self._l1t = (_ops.pointmlp_pack(cols(["first"] + small), "h3"),
+                             _ops.pointmlp_pack(cols(["centers", "fm_first", "fm_knn", "fm_final"]), "h3"),
+                             cols(["onehot", "feature"]),
+                             (_ops.pointmlp_pack_transposed(W, blk["first"][0], c_first, c_first, "x3"), c_first, c_first),
+                             (_ops.pointmlp_pack_transposed(W, maps[0], c_maps, c_maps, "x3"), c_maps, c_maps),
+                             ranges)
+            self._l1t_key = key
+        return self._l1t
+
+    def _nodewise_train_ok(self):
+        """``opt.seg_nodewise_train`` and everything the split training path needs: autograd on, train mode, h3 arithmetic (the weight
+        side of the range guard included), a fusable BatchNorm layer with a ReLU or no activation."""
+        lyr = self.layer1
+        return (bool(getattr(self.opt, "seg_nodewise_train", False)) and torch.is_grad_enabled() and self.training
+                and _ops.POINTMLP_PRECISION == "h3" and lyr._fusable() and lyr.normalization == 'batch' and lyr.norm.training
+                and lyr.activation in ('relu', None) and lyr.conv.weight.is_cuda and lyr.conv.weight.dtype == torch.float32
+                and lyr.conv.out_channels % 32 == 0 and lyr._h3_ok())
+
+    def forward_nodewise_train(self, x_decentered, x, sn, label, first_pn_out, som_node, masked_max, knn_feature_1, final_pn_out, feature,
+                               min_idx_i32):
+        """forward() on the gathered tensors, in training: node-level inputs B x C x M + node ids; differentiable in first_pn_out, the
+        three node-level maps, the feature and layer 1's parameters (the coordinates, normals and the one-hot label carry no gradient)."""
+        B, N, k = x.size()[0], x.size()[2], self.opt.k
+        lyr = self.layer1
+        bn = lyr.norm
+        small = [x_decentered.detach(), torch.cat([x] * k, dim=2)] + ([torch.cat([sn] * k, dim=2)] if self.opt.surface_normal else [])
+        x2 = torch.cat(small, dim=1).detach().float().contiguous()
+        maps = torch.cat([masked_max] + ([knn_feature_1] if self.opt.som_k >= 2 else []) + [final_pn_out], dim=1).float()
+        onehot = torch.zeros(B, 16, dtype=torch.float32, device=x.device)
+        onehot.scatter_(1, label.unsqueeze(1), 1)
+        n = B * k * N
+        m = bn.momentum
+        ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
+                and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device)
+        h, mean, var = _NodewiseLayerFn.apply(lyr._prep(first_pn_out).float(), x2, som_node.detach().float(), maps.contiguous(), onehot,
+                                              feature.float(), lyr._weight2d(), lyr._bias(), bn.weight, bn.bias, min_idx_i32.contiguous(),
+                                              self._layer1_split_train(), lyr.activation == 'relu', bn.eps,
+                                              (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None)
+        with torch.no_grad():                                           # F.batch_norm's running-statistics update (as _FusedPointwise._run)
+            if not ride and bn.running_mean is not None and m is not None:
+                bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
+                bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
+            lyr._affine_key = None
+        return self._tail(self.layer3(self.layer2(h)), k)
+
     def _tail(self, h, k):
         if (h.is_cuda and h.dtype == torch.float32 and k in (2, 3) and not torch.is_grad_enabled() and h.is_contiguous()
                 and h.shape[2] == k * self.opt.input_pc_num and h.shape[0] * h.shape[1] <= 65535):
@@ -651,6 +717,10 @@ def _segmentation_head(encoder, segmenter, pc, sn, label, feature):
                                           encoder.first_pn_out_masked_max.contiguous(), encoder.knn_feature_1.contiguous(),
                                           encoder.final_pn_out.contiguous(), feature, st["a"].min_idx_i32,
                                           first_pn_out_p16=p16)
+    if segmenter._nodewise_train_ok():
+        return segmenter.forward_nodewise_train(encoder.x_decentered, pc, sn, label, encoder.first_pn_out, encoder.som_node,
+                                                encoder.first_pn_out_masked_max, encoder.knn_feature_1, encoder.final_pn_out, feature,
+                                                st["a"].min_idx_i32)
     need_grad = torch.is_grad_enabled() and encoder.first_pn_out_masked_max.requires_grad
     if need_grad:
         # (a fixed-order backward: torch.gather's scatter-adds the ~kN / M copies of a node atomically, in an order that changes per run)

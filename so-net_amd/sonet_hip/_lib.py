@@ -83,6 +83,7 @@ SIGNATURES = {
     "sonet_pointmlp_bf16_stats": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "sonet_pointmlp_bf16_stats_xaff": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "sonet_pointmlp_h3_nodeadd_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
+    "sonet_pointmlp_h3_nodeadd_stats_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "sonet_wgrad_x3_ws_size": [_i, _i, _i, _i],
     "sonet_wgrad_x3_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_wgrad_bf16_ws_size": [_i, _i, _i, _i],
@@ -103,6 +104,9 @@ SIGNATURES = {
     "sonet_node_gather_bwd_ws_size": [_i, _i, _i],
     "sonet_node_gather_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_node_gather_bwd_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "sonet_pointwise_bwd_apply_nodesum_ws_size": [_i, _i, _i],
+    "sonet_pointwise_bwd_apply_nodesum_tile": [],
+    "sonet_pointwise_bwd_apply_nodesum_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_p16_size": [_i, _i, _i],
     "sonet_p16_from_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
     "sonet_p16_to_f32": [_vp, _vp, _i, _i, _i, _vp],
@@ -191,6 +195,7 @@ _RESTYPES = {
     "sonet_node_stage_columns": ctypes.c_size_t,
     "sonet_knn_gather_bwd_ws_size": ctypes.c_size_t,
     "sonet_node_gather_bwd_ws_size": ctypes.c_size_t,
+    "sonet_pointwise_bwd_apply_nodesum_ws_size": ctypes.c_size_t,
     "sonet_pointmlp_h3p_pack_size": ctypes.c_size_t,
     "sonet_pointmlp_h3p_stats_ws_size": ctypes.c_size_t,
     "sonet_pointmlp_bf16_pack_size": ctypes.c_size_t,

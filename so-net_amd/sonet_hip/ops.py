@@ -1752,6 +1752,45 @@ def pointmlp_stats(x1, wp, scale, shift, relu, Cout, x2=None, xaff=None):
     return y, mean, var
 
 
+@_consumes_rider
+def pointmlp_nodeadd_stats(x1, wp, bias, Cout, z, zidx, x2=None):
+    """raw = W . cat(x1, x2) + z[:, :, zidx] + bias and the per-channel (mean, biased var) of raw over (B, L) from the kernel's epilogue,
+    in one launch: the TRAINING forward of a BatchNorm layer whose per-node and per-cloud input channels were multiplied once per node
+    (z B x Cout x M f32, zidx B x L i32, out of range: + 0) -- ``pointmlp_nodeadd`` with the epilogue of ``pointmlp_stats``.  h3 packs
+    only; consumes an armed ``bn_rider``.  -> (raw, mean, var)."""
+    try:
+        if not isinstance(wp, torch.Tensor) or wp.dtype != torch.int8:
+            raise SonetHipError("pointmlp_nodeadd_stats: an h3 pack")
+        _chk(x1, "x", torch.float32, 3)
+        _chk(z, "z", torch.float32, 3)
+        _chk(zidx, "zidx", torch.int32, 2)
+        B, C1, L = x1.shape
+        C2 = 0
+        if x2 is not None:
+            _chk(x2, "x2", torch.float32, 3)
+            if x2.shape[0] != B or x2.shape[2] != L:
+                raise SonetHipError("x2 must be B x C2 x L")
+            C2 = x2.shape[1]
+        _chk_cvec(Cout, bias=bias)
+        dev = _same_device(x1, x2, wp, bias, z, zidx)
+        lib = _lib.load()
+        if wp.numel() != lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout) or tuple(z.shape[:2]) != (B, Cout) or tuple(zidx.shape) != (B, L):
+            raise SonetHipError("pointmlp_nodeadd_stats: pack for Cin=%d Cout=%d, z B x Cout x M, zidx B x L" % (C1 + C2, Cout))
+        raw = torch.empty((B, Cout, L), dtype=torch.float32, device=dev)
+        mean = torch.empty((Cout,), dtype=torch.float32, device=dev)
+        var = torch.empty((Cout,), dtype=torch.float32, device=dev)
+        ws = torch.empty((lib.sonet_pointmlp_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
+        name = "pointmlph3_nodeadd_stats_%dx%d_L%d" % (C1 + C2, Cout, L)
+        _range_arm(name)
+        with _lib.on_device(dev), _timed(name):
+            check(lib.sonet_pointmlp_h3_nodeadd_stats_f32(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(const_vec(Cout, 1.0, dev)), ptr(bias), 0, ptr(raw),
+                                                          B, Cout, L, ptr(z), ptr(zidx), z.shape[2], ptr(ws), ptr(mean), ptr(var), stream_ptr()),
+                  "sonet_pointmlp_h3_nodeadd_stats_f32")
+    finally:
+        _rider_done()
+    return raw, mean, var
+
+
 # ---- third generation of the fp16-split layer: pre-split activations ("P16" planes, csrc/pointmlp_h3p.hip) -------------------------
 class P16:
     """A B x C x L activation in the P16 layout (include/sonet_hip.h): two fp16 planes per value, in MFMA B-fragment order.
@@ -2280,6 +2319,43 @@ def pointwise_bwd_apply(gy, raw, scale, shift, relu, a, b, c0):
         check(fn(ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), ptr(a), ptr(b), ptr(c0), ptr(out), B, C, L, stream_ptr()),
               "sonet_pointwise_bwd_apply")
     return out
+
+
+NODESUM_MAX_NODES = 1024               # include/sonet_hip.h: sonet_pointwise_bwd_apply_nodesum_f32 (as sonet_node_gather_bwd_*)
+
+
+def pointwise_bwd_apply_nodesum_tile():
+    """Columns per tile of ``pointwise_bwd_apply_nodesum``'s pass (the per-node sums are carried from tile to tile)."""
+    return int(_lib.load().sonet_pointwise_bwd_apply_nodesum_tile())
+
+
+def pointwise_bwd_apply_nodesum(gy, raw, scale, shift, relu, a, b, c0, ids, M):
+    """``pointwise_bwd_apply`` and ``node_gather_bwd`` of its result in one pass over (gy, raw): -> (g_raw B x C x L, gz B x C x M) with
+    gz[b][c][m] = the sum of g_raw[b][c][l] over the columns with ids[b][l] == m in ascending column order (ids B x L i32; outside
+    [0, M): nowhere).  The bits of the two launches; f32 only; M <= 1024."""
+    # (sizes first -- attribute checks that need no device --, then the tensors themselves)
+    if not isinstance(gy, torch.Tensor) or gy.dim() != 3:
+        raise SonetHipError("gy must be a 3-D torch.Tensor")
+    B, C, L = gy.shape
+    M = int(M)
+    if M <= 0 or M > NODESUM_MAX_NODES:
+        raise SonetHipError("pointwise_bwd_apply_nodesum: 1 <= M <= %d, got %d" % (NODESUM_MAX_NODES, M))
+    _chk_member(ids, "ids", torch.int32, (B, L))
+    _chk(gy, "gy", torch.float32, 3)
+    _chk(raw, "raw", torch.float32, 3)
+    if raw.shape != gy.shape:
+        raise SonetHipError("raw must have gy's shape %s, got %s" % (tuple(gy.shape), tuple(raw.shape)))
+    _chk_cvec(C, scale=scale, shift=shift, a=a, b=b, c0=c0)
+    dev = _same_device(gy, raw, scale, shift, a, b, c0, ids)
+    lib = _lib.load()
+    g_raw = torch.empty_like(gy)
+    gz = torch.empty((B, C, M), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib.sonet_pointwise_bwd_apply_nodesum_ws_size(B, M, L),), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev), _timed("pointwise_bwd_apply_nodesum"):
+        check(lib.sonet_pointwise_bwd_apply_nodesum_f32(ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), ptr(a), ptr(b), ptr(c0),
+                                                        ptr(ids), M, ptr(g_raw), ptr(gz), ptr(ws), B, C, L, stream_ptr()),
+              "sonet_pointwise_bwd_apply_nodesum_f32")
+    return g_raw, gz
 
 
 P16_ONLY = _os.environ.get("SONET_P16_ONLY", "1") != "0"        # segmenter: the fused first PointNet writes only the P16 planes of first_pn_out
