@@ -374,6 +374,14 @@ int sonet_pointmlp_h3p(const void *x1p, int C1, int L1, const int32_t *gidx, con
  * every 128-column block holds G groups (G GK <= 128), group g of block i is output column i G + g (< ngout).  Exactly one output:
  * yp = P16 planes (Lout >= ngout columns, the first ngout written) of the maxima (KNNModule's max over the neighbours, models/layers.py:365; G <= 16) or y = f32
  * [ngout][Cout] (the global max over a cloud's M nodes = the feature vector, models/networks.py:197; G <= 2, GK % 4 == 0).  NaN wins.
+ * sonet_knn_layer2_gmax_p16 (so-net_amd/csrc/knn_layer.hip): sonet_knn_stage_input_p16 followed by sonet_pointmlp_h3p_gmax with P16 out, in ONE
+ *   launch -- h1 is built in LDS as the operand of KNNModule's second layer and never reaches memory.  rec, z_p16 (1 x Cin x Lm), wl, scale1,
+ *   shift1, relu1 as sonet_knn_stage_input_p16 takes them; Wp = the h3p pack of the second layer [Cout][Cin], scale2, shift2, relu2; GK = K,
+ *   G = min(16, 128 / K), ngout = B M, Lout >= ngout as in sonet_pointmlp_h3p_gmax.  yp receives the planes the two launches write, bit for
+ *   bit (the columns from ngout on are not written); the launch's slot of the range log receives what their two slots receive: word 1 = the
+ *   pack's weight word, word 2 = the larger of h1's and the output planes' maxima.  SONET_ERR_UNSUPPORTED, before anything is launched,
+ *   unless Cout % 128 == 0, Cout <= 512, Cin % 16 == 0, Cin <= 512, G GK <= 128 and every panel stays below 2 GiB: the caller then takes
+ *   the two launches.
  * sonet_p16_flat_to_bcm_f32: planes of a flat 1 x C x (B M) activation -> f32 [B][C][M] (an intermediate map a caller asks for). */
 size_t sonet_knn_stage_columns(int B, int M, int K);
 size_t sonet_node_stage_columns(int B, int M);
@@ -383,6 +391,9 @@ int sonet_knn_stage_input_p16(const void *rec, const void *z_p16, const float *w
                               int B, int M, int K, int C, void *h1_p16, sonet_stream_t stream);
 int sonet_pointmlp_h3p_gmax(const void *x1p, int C1, const void *x2p, int C2, const void *Wp, const float *scale, const float *shift,
                             int relu, int Cout, int L, int GK, int G, int ngout, int Lout, float *y, void *yp, sonet_stream_t stream);
+int sonet_knn_layer2_gmax_p16(const void *rec, const void *z_p16, const float *wl, const float *scale1, const float *shift1, int relu1,
+                              int B, int M, int K, int Cin, const void *Wp, const float *scale2, const float *shift2, int relu2,
+                              int Cout, int GK, int G, int ngout, int Lout, void *yp, sonet_stream_t stream);
 int sonet_p16_flat_to_bcm_f32(const void *p16, float *x, int B, int C, int M, sonet_stream_t stream);
 
 /* Node-level pieces of the training step (so-net_amd/csrc/node_train.hip).

@@ -155,6 +155,23 @@ __device__ __forceinline__ float clamp_keep_nan(float w, float lim) { return w <
 // channel of element e (0..7) of half h in a 16-channel chunk of a P16 plane
 __device__ __forceinline__ int p16_channel(int h, int e) { return 4 * h + (e & 3) + 8 * (e >> 2); }
 
+// ---- group-max epilogues of the node-level stage (pointmlp_h3p.hip EPI 4 / 5, knn_layer.hip): a tile's 32 x 128 post-activation values
+// pass through LDS, rows GM_STRIDE floats apart; the max over a group's columns is taken left to right, NaN wins like torch.max.
+constexpr int GM_STRIDE = 136;                                 // floats per staged row: 128 columns + 8 (rows 4 apart land 32 banks apart)
+__device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
+// P16 out: the maxima (m0, m1) of element pair p (rows 2 (p & 1) + 8 (p >> 1) + {0, 1} of half h2 of 16-channel chunk `chunk` of the
+// output) of output column n_out -> range log, clamp (the values are 32 x already: split_lo is the unscaled lower bound, 0 with ReLU),
+// split, one dword into each form's plane of yp (Lout columns per plane)
+__device__ __forceinline__ void gmax_p16_store(float m0, float m1, float split_lo, RangeAcc &yr, void *yp, int chunk, int h2, int p,
+                                               size_t Lout, size_t n_out) {
+    range_track(yr, m0, m1);
+    unsigned hv, mv;
+    p16_split2(__builtin_amdgcn_fmed3f(m0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(m1, split_lo * 32.f, 65504.f), hv, mv);
+    unsigned *dst = reinterpret_cast<unsigned *>(static_cast<char *>(yp) + ((((size_t)chunk * 2) * 2 + h2) * Lout + n_out) * 16) + p;
+    dst[0] = hv;
+    dst[Lout * 8] = mv;                                        // form 1: two half planes (2 x Lout x 16 bytes) further
+}
+
 // ---- three-way bf16 split of an f32 pair (the "x3" arithmetic: pointmlp_x3.hip, upconv_bwd.hip) ------------------------------------
 // (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {

@@ -17,6 +17,7 @@
 // sonet_knn_stage_input_p16 turns the records and z (pre-split: two 16-byte gathers per lane and chunk) into h1 as P16 planes -- the
 // operand format of the next layer.
 #include "common.hpp"
+#include "knn_h1.hpp"
 
 namespace {
 
@@ -118,15 +119,11 @@ __global__ __launch_bounds__(256) void knn_stage_input_kernel(const int4 *__rest
         const int grp = (int)blockIdx.y + j * gstride;
         const int c = (grp * KS_CPW + i) * 16 + p16_channel(h, e);
         const bool in = grp < ngrp && c < C;
-        coef[0][t] = in ? 32.f * wl[c * 3 + 0] : 0.f;
-        coef[1][t] = in ? 32.f * wl[c * 3 + 1] : 0.f;
-        coef[2][t] = in ? 32.f * wl[c * 3 + 2] : 0.f;
-        coef[3][t] = in ? scale[c] : 0.f;
-        coef[4][t] = in ? 32.f * shift[c] : 0.f;
+#pragma unroll
+        for (int kind = 0; kind < 5; ++kind) coef[kind][t] = knn_h1_coef(kind, in, c, wl, scale, shift);
     }
-    const bool valid = r.x != -2, ok = r.x >= 0;
-    const f32x2_t d0 = {__int_as_float(r.y), __int_as_float(r.y)}, d1 = {__int_as_float(r.z), __int_as_float(r.z)},
-                d2 = {__int_as_float(r.w), __int_as_float(r.w)};
+    const KnnCol kcol = knn_col(r);
+    const bool ok = kcol.ok;
     RangeAcc xr = {0, 0u};
     const float lo = relu ? 0.f : -65504.f;                              // ReLU and the lower clamp of the split are one v_med3_f32
     // (plane p = (chunk, form, half) of a P16 tensor with L columns starts at p L)
@@ -155,31 +152,15 @@ __global__ __launch_bounds__(256) void knn_stage_input_kernel(const int4 *__rest
 #pragma unroll
         for (int i = 0; i < KS_CPW; ++i) {
             if (grp * KS_CPW + i >= KC) break;
-            const unsigned zh[4] = {zhq[i].x, zhq[i].y, zhq[i].z, zhq[i].w}, zm[4] = {zmq[i].x, zmq[i].y, zmq[i].z, zmq[i].w};
-            unsigned hv[4], mv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                                // elements 2 q, 2 q + 1: two consecutive channels
-                const int slot = (j * KS_CPW + i) * 16 + hh * 8 + 2 * q;
-                const f32x2_t w0 = *reinterpret_cast<const f32x2_t *>(&coef[0][slot]), w1 = *reinterpret_cast<const f32x2_t *>(&coef[1][slot]),
-                            w2 = *reinterpret_cast<const f32x2_t *>(&coef[2][slot]), sc = *reinterpret_cast<const f32x2_t *>(&coef[3][slot]),
-                            sh = *reinterpret_cast<const f32x2_t *>(&coef[4][slot]);
-                const f16x2_t zh2 = __builtin_bit_cast(f16x2_t, zh[q]), zm2 = __builtin_bit_cast(f16x2_t, zm[q]);
-                // 32 z = hi + residual (exact: two fp16 values whose exponents are at most 11 apart)
-                f32x2_t a = __builtin_convertvector(zh2, f32x2_t) + __builtin_convertvector(zm2, f32x2_t);
-                a = __builtin_elementwise_fma(w0, d0, a);                // (the reference's order: z, then the three coordinate channels)
-                a = __builtin_elementwise_fma(w1, d1, a);
-                a = __builtin_elementwise_fma(w2, d2, a);
-                a = __builtin_elementwise_fma(a, sc, sh);                // 32 x the pre-activation
-                if (!valid) a = f32x2_t{0.f, 0.f};
-                range_track(xr, a[0], a[1]);
-                // (a NaN leaves v_med3_f32 as the lower bound, as in split_act; the range log has seen it)
-                p16_split2(__builtin_amdgcn_fmed3f(a[0], lo, 65504.f), __builtin_amdgcn_fmed3f(a[1], lo, 65504.f), hv[q], mv[q]);
-            }
+            const int slot = (j * KS_CPW + i) * 16 + hh * 8;
+            const float *const cf[5] = {&coef[0][slot], &coef[1][slot], &coef[2][slot], &coef[3][slot], &coef[4][slot]};
+            uint4 hv, mv;
+            knn_h1_half(zhq[i], zmq[i], cf, kcol, lo, xr, hv, mv);
 #ifdef SONET_VARIANTS
-            if ((abl & 1) && hv[0] != 0x12345u) { hq += 4 * Lp; continue; }    // (ablation: no stores)
+            if ((abl & 1) && hv.x != 0x12345u) { hq += 4 * Lp; continue; }    // (ablation: no stores)
 #endif
-            hq[0] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
-            hq[2 * Lp] = make_uint4(mv[0], mv[1], mv[2], mv[3]);
+            hq[0] = hv;
+            hq[2 * Lp] = mv;
             hq += 4 * Lp;
         }
     };
@@ -198,16 +179,8 @@ __global__ __launch_bounds__(256) void knn_stage_input_kernel(const int4 *__rest
         }
     }
     if (rlog != nullptr) {
-        // (32 x was tracked: take the factor out of the exponent; a negative value only matters without the ReLU)
-        unsigned bits;
-        if (relu) {
-            const unsigned pos = xr.mp > 0 ? (unsigned)xr.mp : 0u, nan_neg = xr.mn > 0xFF800000u ? (xr.mn & 0x7FFFFFFFu) : 0u;
-            bits = pos > nan_neg ? pos : nan_neg;
-        } else {
-            bits = range_amax_bits(xr);
-        }
-        unsigned wm = wave_umax(bits);
-        wm = wm > (5u << 23) ? wm - (5u << 23) : 0u;
+        // (32 x was tracked: the factor leaves through the exponent; a negative value only matters without the ReLU)
+        const unsigned wm = range_x32_out(wave_umax(range_act_bits(xr, relu)));
         if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = wm;
         __syncthreads();
         if (threadIdx.x == 0) {

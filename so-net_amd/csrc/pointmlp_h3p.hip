@@ -229,8 +229,7 @@ __device__ __forceinline__ void sched_pair() {
 // the columns themselves -- KNNModule's max over the K neighbours of a node (models/layers.py:365; EPI 4: P16 planes out) and the global
 // max over a cloud's M nodes (models/networks.py:197; EPI 5: f32 [cloud][Cout]).  A tile's 32 x 128 post-activation values pass through
 // LDS (17 KiB) one tile at a time; NaN wins like torch.max.
-constexpr int GM_STRIDE = 136;                                 // floats per staged row: 128 columns + 8 (rows 4 apart land 32 banks apart)
-__device__ __forceinline__ float nan_max(float m, float v) { return (v > m || v != v) ? v : m; }
+// (GM_STRIDE, nan_max and gmax_p16_store: device.hpp, shared with knn_layer.hip)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int MT, int NC, int OCC, int EPI, int OUT>
@@ -440,14 +439,8 @@ __global__ __launch_bounds__(P_THREADS, OCC) void pointmlp_h3p_kernel(const H3pA
                         }
                         const long long n_out = (long long)wg_col * a.G + g;
                         if (n_out < a.ngout) {
-                            range_track(yr, m0, m1);
-                            unsigned hv, mv;
                             // (OUT == 2: the affine table made the values 32 x already, like the plain P16 epilogue)
-                            p16_split2(__builtin_amdgcn_fmed3f(m0, split_lo * 32.f, 65504.f), __builtin_amdgcn_fmed3f(m1, split_lo * 32.f, 65504.f), hv, mv);
-                            unsigned *dst = reinterpret_cast<unsigned *>(static_cast<char *>(a.yp)
-                                + ((((size_t)((ct0 + mt) * 2 + qq) * 2) * 2 + h2) * (size_t)a.Lout + (size_t)n_out) * 16) + p;
-                            dst[0] = hv;
-                            dst[(size_t)a.Lout * 8] = mv;                  // form 1: two half planes (2 x Lout x 16 bytes) further
+                            gmax_p16_store(m0, m1, split_lo, yr, a.yp, (ct0 + mt) * 2 + qq, h2, p, (size_t)a.Lout, (size_t)n_out);
                         }
                     }
                 } else {

@@ -258,7 +258,7 @@ class Encoder(_PlainAttrs, nn.Module):
 
     # ---- no-grad node-level stage on the flat column axis (csrc/node_stage.hip) ---------------------------------------------------
     def _node_stage_ok(self, B, M, node_knn_I):
-        """KNNModule + final PointNet + global max as five launches on pre-split activations: eval, no autograd, h3 arithmetic, the
+        """KNNModule + final PointNet + global max as four launches (five without ``ops.KNN_FUSED_LAYER2``) on pre-split activations: eval, no autograd, h3 arithmetic, the
         standard two-layer modules, 64 or 128 nodes (a cloud's nodes = one or half a 128-column block)."""
         opt = self.opt
         if not (_ops.NODE_STAGE_P16 and _ops.GATHER_NODE_STAGE and _ops.P16_CHAINS and _ops.POINTMLP_PRECISION == "h3" and opt.som_k >= 2) \
@@ -290,11 +290,17 @@ class Encoder(_PlainAttrs, nn.Module):
         z = _ops.pointmlp_h3p(xp, k1._packed_p16(lambda: k1._weight2d().detach()[:, 3:], "feat"), _ops.const_vec(C1, 1.0, dev),
                               _ops.const_vec(C1, 0.0, dev), False, C1, out="p16", tag="flat")
         s1, t1 = k1._eval_affine()
-        h1 = _ops.knn_stage_input(prep, z, k1._lead_cols(3), s1, t1, k1.activation == 'relu')
-        center, cp = prep["center"], prep["center_p16"]
-        # layer 2 + max over the K neighbours (models/layers.py:352-365)
         s2, t2 = k2._eval_affine()
-        knn = _ops.pointmlp_h3p_gmax(h1, k2._packed_p16(), s2, t2, k2.activation == 'relu', k2.conv.out_channels, K, G, B * M, out="p16", Lout=xp.L)
+        center, cp = prep["center"], prep["center_p16"]
+        C2 = k2.conv.out_channels
+        if _ops.KNN_FUSED_LAYER2 and _ops.knn_layer2_supported(C1, C2, K, B, M, xp.L):
+            # the rest of layer 1 per neighbour copy, layer 2 and the max over the K neighbours in one launch: h1 stays in LDS
+            knn = _ops.knn_layer2_gmax(prep, z, k1._lead_cols(3), s1, t1, k1.activation == 'relu', k2._packed_p16(), s2, t2,
+                                       k2.activation == 'relu', C2, xp.L)
+        else:
+            h1 = _ops.knn_stage_input(prep, z, k1._lead_cols(3), s1, t1, k1.activation == 'relu')
+            # layer 2 + max over the K neighbours (models/layers.py:352-365)
+            knn = _ops.pointmlp_h3p_gmax(h1, k2._packed_p16(), s2, t2, k2.activation == 'relu', C2, K, G, B * M, out="p16", Lout=xp.L)
         # final PointNet on cat(center, knn feature) (models/networks.py:191-196): the 3 centre channels as the second panel
         s3, t3 = f1._eval_affine()
         h3 = _ops.pointmlp_h3p(knn, f1._packed_p16(lambda: torch.cat((f1._weight2d().detach()[:, 3:], f1._weight2d().detach()[:, :3]), dim=1), "rot3"),

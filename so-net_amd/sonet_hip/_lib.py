@@ -130,6 +130,7 @@ SIGNATURES = {
     "sonet_knn_stage_prepare_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "sonet_knn_stage_input_p16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "sonet_pointmlp_h3p_gmax": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "sonet_knn_layer2_gmax_p16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "sonet_node_stage_columns": [_i, _i],
     "sonet_p16_flat_to_bcm_f32": [_vp, _vp, _i, _i, _i, _vp],
     "sonet_som_sort_group_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

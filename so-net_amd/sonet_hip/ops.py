@@ -865,8 +865,11 @@ NODE_LINEAR_SPLIT = _os.environ.get("SONET_NODE_LINEAR_SPLIT", "1") != "0"
 # no-grad h3 chains of point-wise layers hand their activations on pre-split (P16 planes, csrc/pointmlp_h3p.hip) instead of as f32
 P16_CHAINS = _os.environ.get("SONET_P16_CHAINS", "1") != "0"
 # no-grad node-level stage (KNNModule + final PointNet + global max) on the third-generation layer, flat column axis, max-over-group
-# epilogues (csrc/node_stage.hip): 5 launches instead of 8.  0 = the round-4 stage (second-generation layers + planes_max / lastdim_max)
+# epilogues (csrc/node_stage.hip): 5 launches instead of 8 (4 with KNN_FUSED_LAYER2 below).  0 = the round-4 stage (second-generation layers + planes_max / lastdim_max)
 NODE_STAGE_P16 = _os.environ.get("SONET_NODE_STAGE_P16", "1") != "0"
+# ... with KNNModule's second layer building its own input in LDS (csrc/knn_layer.hip): 4 launches, h1 never written.  0 = knn_stage_input +
+# pointmlp_h3p_gmax; the same planes and range words either way
+KNN_FUSED_LAYER2 = _os.environ.get("SONET_KNN_FUSED_LAYER2", "1") != "0"
 # bf16 training: the last layer of the first PointNet + the per-node arg-max pool in one launch, first_pn_out never written (0 = store + index_max)
 POOLED_TRAIN_EPILOGUE = _os.environ.get("SONET_POOLED_TRAIN_EPILOGUE", "1") != "0"
 # f32-class training: the same on node-sorted columns (sonet_pointmlp_h3_segpool_f32; 0 = store + index_max)
@@ -2011,6 +2014,55 @@ def knn_stage_input(prep, z, wl, scale, shift, relu):
         check(_lib.load().sonet_knn_stage_input_p16(ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(scale), ptr(shift), int(bool(relu)),
                                                     prep["B"], prep["M"], prep["K"], C, ptr(h1.data), stream_ptr()), "sonet_knn_stage_input_p16")
     return h1
+
+
+KNN_LAYER2_MAX_C = 512                # csrc/knn_layer.hip: Cin and Cout at most (its coefficient tables are static LDS)
+
+
+def knn_layer2_supported(Cin, Cout, K, B=1, M=1, Lout=None):
+    """The shapes ``sonet_knn_layer2_gmax_p16`` takes (it refuses the others with SONET_ERR_UNSUPPORTED before launching), its panel
+    limits included: a caller that gets False takes ``knn_stage_input`` + ``pointmlp_h3p_gmax``."""
+    if not (Cout % 128 == 0 and 0 < Cout <= KNN_LAYER2_MAX_C and Cin % 16 == 0 and 0 < Cin <= KNN_LAYER2_MAX_C
+            and 1 <= K <= 128 and min(16, 128 // K) * K <= 128 and B > 0 and M > 0):
+        return False
+    G = min(16, 128 // K)
+    Lm = node_stage_columns(B, M)
+    Lout = Lm if Lout is None else int(Lout)
+    nblk = (B * M + G - 1) // G
+    KCP = (Cin + 127) // 128 * 8
+    return (nblk <= 0x7FFFFFFF and (Cin // 16) * 64.0 * Lm < 2.0e9 and (Cout // 16) * 64.0 * Lout < 2.0e9
+            and (Cout // 32) * KCP * 2048.0 < 2.0e9)
+
+
+def knn_layer2_gmax(prep, z, wl, s1, t1, relu1, wp, s2, t2, relu2, Cout, Lout):
+    """``knn_stage_input`` + ``pointmlp_h3p_gmax(..., out="p16")`` in one launch (``sonet_knn_layer2_gmax_p16``): h1 is built in LDS.
+    prep, z, wl, s1, t1, relu1 as ``knn_stage_input`` takes them; wp, s2, t2, relu2 = KNNModule's second layer (h3p pack C x Cout)
+    -> ``P16`` 1 x Cout x Lout, the maxima over each node's K neighbour copies in columns 0 .. B M - 1, pad columns zero."""
+    if not isinstance(z, P16) or z.B != 1 or z.L != node_stage_columns(prep["B"], prep["M"]):
+        raise SonetHipError("knn_layer2_gmax: z is a P16 1 x C x Lm activation")
+    if wp.dtype != torch.int32:
+        raise SonetHipError("knn_layer2_gmax: an h3p pack (ops.pointmlp_h3p_pack)")
+    _chk(wl, "wl", torch.float32, 2)
+    for n_, v_ in (("s1", s1), ("t1", t1), ("s2", s2), ("t2", t2)):
+        _chk(v_, n_, torch.float32, 1)
+    C = z.C
+    if tuple(wl.shape) != (C, 3) or s1.numel() != C or t1.numel() != C or s2.numel() != Cout or t2.numel() != Cout:
+        raise SonetHipError("knn_layer2_gmax: wl C x 3, s1 / t1 C, s2 / t2 Cout")
+    dev = _same_device(prep["rec"], z.data, wl, s1, t1, wp, s2, t2)
+    lib = _lib.load()
+    if wp.numel() * 4 != lib.sonet_pointmlp_h3p_pack_size(C, Cout):
+        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
+                            % (wp.numel() * 4, lib.sonet_pointmlp_h3p_pack_size(C, Cout), C, Cout))
+    B, M, K, G = prep["B"], prep["M"], prep["K"], prep["G"]
+    ngout, Lout = B * M, int(Lout)
+    yp = p16_flat(Cout, Lout, ngout, dev)
+    name = "pointmlph3p_knn_gmax%d_%dx%d_L%d" % (K, C, Cout, ngout * K)
+    _range_arm(name)
+    with _lib.on_device(dev), _timed(name):
+        check(lib.sonet_knn_layer2_gmax_p16(ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(s1), ptr(t1), int(bool(relu1)), B, M, K, C,
+                                            ptr(wp), ptr(s2), ptr(t2), int(bool(relu2)), int(Cout), K, G, ngout, Lout, ptr(yp.data),
+                                            stream_ptr()), "sonet_knn_layer2_gmax_p16")
+    return yp
 
 
 def p16_flat_to_bcm(p, B, M):

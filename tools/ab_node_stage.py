@@ -2,7 +2,11 @@
 the flat stage of round 5 (B) in ONE process on ONE box, windows alternating A B A B ... : box-to-box and run-to-run clock differences
 (+-5 % on the fused first PointNet alone) are larger than the difference the stage makes, so only an interleaved comparison says anything.
 
-  python tools/ab_node_stage.py [--rounds 10] [--steps 40] [--in-flight 3]"""
+  python tools/ab_node_stage.py [--rounds 10] [--steps 40] [--in-flight 3] [--variant flat|knn_layer2]
+
+--variant knn_layer2: both sides run the flat stage; A forms the KNN layer's input with knn_stage_input + the 512 -> 512 group-max launch,
+B with the one launch of csrc/knn_layer.hip (ops.KNN_FUSED_LAYER2).  Per round and side one window; "every round favours B" and the spread
+inside a side against the median gain are printed for the in-flight figure."""
 import argparse
 import os
 import statistics
@@ -23,6 +27,7 @@ def main():
     ap.add_argument("--in-flight", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--points", type=int, default=5000)
+    ap.add_argument("--variant", choices=("flat", "knn_layer2"), default="flat")
     args = ap.parse_args()
     import bench
     from models import networks as NW
@@ -41,11 +46,14 @@ def main():
     streams = [torch.cuda.Stream(device=dev) for _ in range(P)]
     graphs = {}
     with torch.no_grad():
-        for tag, flag in (("A_round4_stage", False), ("B_flat_stage", True)):
-            ops.NODE_STAGE_P16 = flag
+        knob = "NODE_STAGE_P16" if args.variant == "flat" else "KNN_FUSED_LAYER2"
+        TA, TB = ("A_round4_stage", "B_flat_stage") if args.variant == "flat" else ("A_two_launches", "B_one_launch")
+        for tag, flag in ((TA, False), (TB, True)):
+            setattr(ops, knob, flag)
             graphs[tag] = [GraphedForward(fwd, (i_["pc"], i_["sn"], i_["node"], i_["node_knn_I"]), warmup=2) for i_ in inps]
-    ops.NODE_STAGE_P16 = True
-    fa, fb = graphs["A_round4_stage"][0].static_output, graphs["B_flat_stage"][0].static_output
+            print("%s: %s" % (tag, " ".join(n for n in graphs[tag][0].range.names if "knn" in n or "gmax" in n)))
+    setattr(ops, knob, True)
+    fa, fb = graphs[TA][0].static_output, graphs[TB][0].static_output
     torch.cuda.synchronize()
     print("scores: max |A - B| = %.3g (max |A| = %.3g)" % (float((fa - fb).abs().max()), float(fa.abs().max())))
 
@@ -67,7 +75,7 @@ def main():
     # spin up the clocks
     t_end = time.perf_counter() + 1.5
     while time.perf_counter() < t_end:
-        run("A_round4_stage", P, P)
+        run(TA, P, P)
     torch.cuda.synchronize()
     res = {(t, p): [] for t in graphs for p in (1, P)}
     for r in range(args.rounds):
@@ -75,12 +83,18 @@ def main():
             for tag in graphs:
                 res[(tag, p)].append(window(tag, p))
     for p in (1, P):
-        a, b = res[("A_round4_stage", p)], res[("B_flat_stage", p)]
+        a, b = res[(TA, p)], res[(TB, p)]
         ma, mb = statistics.median(a), statistics.median(b)
-        print("in flight %d: A (round-4 stage) median %.4f ms [min %.4f]   B (flat stage) median %.4f ms [min %.4f]   A / B = %.4f   clouds/s B = %.0f"
-              % (p, ma, min(a), mb, min(b), ma / mb, B / mb * 1e3))
+        print("in flight %d: %s median %.4f ms [min %.4f]   %s median %.4f ms [min %.4f]   A / B = %.4f   clouds/s B = %.0f"
+              % (p, TA, ma, min(a), TB, mb, min(b), ma / mb, B / mb * 1e3))
         print("   A windows: " + " ".join("%.4f" % v for v in a))
         print("   B windows: " + " ".join("%.4f" % v for v in b))
+        # the rule of a same-process A/B: every round on B's side, and the median gain at least twice the largest difference between
+        # consecutive rounds of either side
+        gains = [x - y for x, y in zip(a, b)]
+        step = max(max(abs(v[i + 1] - v[i]) for i in range(len(v) - 1)) for v in (a, b)) if len(a) > 1 else float("nan")
+        print("   A - B per round: %s   rounds favouring B: %d / %d   median gain %.4f ms   largest round-to-round step inside a side %.4f ms"
+              % (" ".join("%.4f" % v for v in gains), sum(v > 0 for v in gains), len(gains), statistics.median(gains), step))
 
 
 if __name__ == "__main__":

@@ -61,6 +61,8 @@ def main():
         ("knn_stage_input 512 x %d" % prep["Lp"], 0.0, lambda: ops.knn_stage_input(prep, z, wl, s1, t1, True), False),
         ("knn 512->512 gmax9 L%d" % prep["Lp"], 2.0 * 512 * 512 * B * M * K,
          lambda: ops.pointmlp_h3p_gmax(h1, w2, s2, t2, True, 512, K, prep["G"], B * M, out="p16", Lout=Lm), True),
+        ("knn input + 512->512 gmax9, one launch", 2.0 * 512 * 512 * B * M * K,
+         lambda: ops.knn_layer2_gmax(prep, z, wl, s1, t1, True, w2, s2, t2, True, 512, Lm), False),
         ("knn 512->512 plain -> p16 (no max)", 2.0 * 512 * 512 * B * M * K, lambda: ops.pointmlp_h3p(h1, w2, s2, t2, True, 512, out="p16"), True),
         ("final 515->768 L%d -> p16" % Lm, 2.0 * 515 * 768 * Lm, lambda: ops.pointmlp_h3p(knn, w3, s3, t3, True, 768, x2=prep["center_p16"], out="p16"), True),
         ("final 768->1024 gmax64 L%d" % Lm, 2.0 * 768 * 1024 * Lm, lambda: ops.pointmlp_h3p_gmax(h3, w4, s4, t4, False, 1024, M, 128 // M, B, out="f32"), True),
@@ -93,6 +95,14 @@ def main():
                 print("%-44s %-22s %s" % (name, tag, str(e)[:80]))
     for k in ("SONET_H3P_SHAPE", "SONET_H3P_NSLAB"):
         os.environ.pop(k, None)
+    # the one-launch KNN layer holds a CU per workgroup: its grid runs in rounds of (CUs) workgroups, so beside the kernel time the CU time
+    # (workgroups x mean workgroup time / CUs) is what the launch costs a forward whose other kernels fill the gaps
+    nwg = prep["Lp"] // 128
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ms = timeit(lambda: ops.knn_layer2_gmax(prep, z, wl, s1, t1, True, w2, s2, t2, True, 512, Lm))
+    rounds = -(-nwg // cus)
+    print("one-launch KNN layer: %d workgroups on %d CUs = %d rounds; kernel %.4f ms -> mean workgroup time %.4f ms, CU time %.4f ms"
+          % (nwg, cus, rounds, ms, ms / rounds, nwg * (ms / rounds) / cus))
 
 
 if __name__ == "__main__":
