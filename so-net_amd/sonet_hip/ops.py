@@ -57,24 +57,25 @@ class kernel_timing:
         return {k: dict(count=v[0], total_ms=v[1], mean_ms=v[1] / v[0]) for k, v in out.items()}
 
 
-class _timed:
-    __slots__ = ("name", "e0")
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        if _TIMING is not None:
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if _TIMING is not None:
+def _launch(dev, label, fn, *args, what=None):
+    """One C-ABI launch: ``fn(*args, stream)`` on the current stream of ``dev``, its status checked (``what``: the name the error message
+    carries, by default the entry point's own).  Under ``kernel_timing`` an event pair goes around it under ``label`` (None: never timed).
+    The device is exchanged inline -- no context-manager objects on a path that runs a hundred times per training step."""
+    prev = torch.cuda._exchange_device(dev.index if dev.index is not None else -1)
+    try:
+        if _TIMING is None or label is None:
+            check(fn(*args, stream_ptr()), what or fn.__name__)
+            return
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        try:
+            check(fn(*args, stream_ptr()), what or fn.__name__)
+        finally:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
-            _TIMING.append((self.name, self.e0, e1))
-        return False
+            _TIMING.append((label, e0, e1))
+    finally:
+        torch.cuda._maybe_exchange_device(prev)
 
 
 def _chk(t, name, dtype=None, dim=None):
@@ -90,11 +91,12 @@ def _chk(t, name, dtype=None, dim=None):
         raise SonetHipError("%s must be %d-D, got shape %s" % (name, dim, tuple(t.shape)))
 
 
-def _chk_cvec(C, **vecs):
-    """Per-channel operands of the BatchNorm / ReLU passes: the kernels index them by channel with no length of their own, so each must be a
-    contiguous float32 tensor of exactly C elements (attribute checks only: no launch, no sync)."""
+def _chk_cvec(C, dim=None, **vecs):
+    """Per-channel operands (the coefficients of the BatchNorm / ReLU passes, the scale / shift / bias of a layer): the kernels index them
+    by channel with no length of their own, so each must be a contiguous float32 tensor of exactly C elements -- ``dim``-D where the
+    wrapper has always asked for that (attribute checks only: no launch, no sync)."""
     for name, t in vecs.items():
-        _chk(t, name, torch.float32)
+        _chk(t, name, torch.float32, dim)
         if t.numel() != C:
             raise SonetHipError("%s must hold C = %d elements, got %d" % (name, C, t.numel()))
 
@@ -145,45 +147,101 @@ def _same_device(*ts):
     return dev
 
 
+def _by_dtype(lib, stem, t):
+    """The f32 or bf16 entry point of a pair: ``lib.<stem>_f32`` / ``lib.<stem>_bf16`` by the storage of ``t``."""
+    return getattr(lib, stem + ("_bf16" if t.dtype == torch.bfloat16 else "_f32"))
+
+
+def _ws(size, dev, *dims):
+    """The byte workspace of a launch on ``dev``: ``size`` bytes, or what the library's size query ``size(*dims)`` asks for."""
+    return torch.empty((size(*dims) if callable(size) else size,), dtype=torch.uint8, device=dev)
+
+
+def _idx_val(B, C, K, dev):
+    """The (arg-max position i32, value f32) outputs of a pooled call, B x C x K each."""
+    return torch.empty((B, C, int(K)), dtype=torch.int32, device=dev), torch.empty((B, C, int(K)), dtype=torch.float32, device=dev)
+
+
+def _layer_inputs(x1, x2, dtype, L=None):
+    """-> (B, C1, C2, L) of a layer call on x1 B x C1 x L (checked by the caller) and, when given, x2 B x C2 x L: a contiguous CUDA tensor of
+    ``dtype`` (None: ``P16`` planes, which carry their own sizes).  L: the column count x2 is held to when x1 is gathered (``gidx``)."""
+    B, C1, L1 = x1.shape
+    L = L1 if L is None else L
+    C2 = 0
+    if x2 is not None:
+        if dtype is not None:
+            _chk(x2, "x2", dtype, 3)
+        if x2.shape[0] != B or x2.shape[2] != L:
+            raise SonetHipError("x2 must be B x C2 x L")
+        C2 = x2.shape[1]
+    return B, C1, C2, L
+
+
+# kind of weight pack -> (tensor dtype that marks the flavour, size query, bytes per unit of the query's result)
+_PACKS = {"f32": (torch.float32, "sonet_pointmlp_pack_size", 4), "x3": (torch.uint8, "sonet_pointmlp_x3_pack_size", 1),
+          "h3": (torch.int8, "sonet_pointmlp_x3_pack_size", 1), "bf16": (torch.int16, "sonet_pointmlp_bf16_pack_size", 1),
+          "h3p": (torch.int32, "sonet_pointmlp_h3p_pack_size", 1), "upconv": (torch.int32, "sonet_upconv3x3_pack_size", 1),
+          "upconv-dgrad": (torch.int32, "sonet_upconv3x3_dgrad_pack_size", 1)}
+
+
+def _pack_bytes(lib, kind, Cin, Cout):
+    _, query, unit = _PACKS[kind]
+    return getattr(lib, query)(Cin, Cout) * unit
+
+
+def _pack_empty(lib, kind, Cin, Cout, dev):
+    """An uninitialised pack of ``kind`` for a Cout x Cin weight."""
+    dtype = _PACKS[kind][0]
+    return torch.empty((_pack_bytes(lib, kind, Cin, Cout) // dtype.itemsize,), dtype=dtype, device=dev)
+
+
+def _chk_pack(lib, wp, kind, Cin, Cout, say=None):
+    """``wp`` (its dtype already told the caller the kind) has the length of a ``kind`` pack for Cin x Cout, compared in bytes.
+    say: None -> the short message, "elements" / "bytes" -> the message with both sizes in that unit."""
+    want, item = _pack_bytes(lib, kind, Cin, Cout), _PACKS[kind][0].itemsize
+    if wp.numel() * item != want:
+        if say is None:
+            raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (Cin, Cout))
+        unit = item if say == "elements" else 1
+        raise SonetHipError("packed weight has %d %s, expected %d for Cin=%d Cout=%d" % (wp.numel() * item // unit, say, want // unit, Cin, Cout))
+
+
+def _chk_index(index, B, Np, row_max=None):
+    """The node ids of an ``index_max*`` call (int32, checked by the caller) are B x N'; row_max, when given, is a 2-D int32 tensor."""
+    if tuple(index.shape) != (B, Np):
+        raise SonetHipError("index must be B x N' = %s, got %s" % ((B, Np), tuple(index.shape)))
+    if row_max is not None:
+        _chk(row_max, "row_max", torch.int32, 2)
+
+
 # ------------------------------------------------------------------------------------------ index_max
 def index_max(data, index, K):
     """data BxCxN' f32|bf16, index BxN' i32 -> BxCxK i32 (include/sonet_hip.h: sonet_index_max_*)."""
     _chk(data, "data", dim=3)
     _chk(index, "index", torch.int32, 2)
-    if data.dtype not in (torch.float32, torch.bfloat16):
-        raise SonetHipError("data must be float32 or bfloat16, got %s" % data.dtype)
+    _chk_f32_or_bf16(data, "data")
     B, C, Np = data.shape
-    if tuple(index.shape) != (B, Np):
-        raise SonetHipError("index must be B x N' = %s, got %s" % ((B, Np), tuple(index.shape)))
+    _chk_index(index, B, Np)
     dev = _same_device(data, index)
     out = torch.empty((B, C, int(K)), dtype=torch.int32, device=dev)
     if out.numel() == 0 or Np == 0:
         return out.zero_()
-    lib = _lib.load()
-    with _lib.on_device(dev), _timed("index_max"):
-        fn = lib.sonet_index_max_f32 if data.dtype == torch.float32 else lib.sonet_index_max_bf16
-        check(fn(ptr(data), ptr(index), ptr(out), B, C, Np, int(K), stream_ptr()), "sonet_index_max")
+    _launch(dev, "index_max", _by_dtype(_lib.load(), "sonet_index_max", data), ptr(data), ptr(index), ptr(out), B, C, Np, int(K), what="sonet_index_max")
     return out
 
 
 def index_max_gather(data, index, K, row_max=None):
     """index_max + the masked gather of models/networks.py:185 in one pass -> (idx i32, val f32) BxCxK."""
     _chk(data, "data", dim=3)
-    if data.dtype not in (torch.float32, torch.bfloat16):
-        raise SonetHipError("data must be float32 or bfloat16, got %s" % data.dtype)
+    _chk_f32_or_bf16(data, "data")
     _chk(index, "index", torch.int32, 2)
     B, C, Np = data.shape
-    if tuple(index.shape) != (B, Np):
-        raise SonetHipError("index must be B x N' = %s, got %s" % ((B, Np), tuple(index.shape)))
-    if row_max is not None:
-        _chk(row_max, "row_max", torch.int32, 2)
+    _chk_index(index, B, Np, row_max)
     dev = _same_device(data, index, row_max)
-    idx = torch.empty((B, C, int(K)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, C, int(K)), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    fn = lib.sonet_index_max_gather_f32 if data.dtype == torch.float32 else lib.sonet_index_max_gather_bf16
-    with _lib.on_device(dev), _timed("index_max_gather" if data.dtype == torch.float32 else "index_max_gather_bf16"):
-        check(fn(ptr(data), ptr(index), ptr(row_max), ptr(idx), ptr(val), B, C, Np, int(K), stream_ptr()), "sonet_index_max_gather")
+    idx, val = _idx_val(B, C, K, dev)
+    fn = _by_dtype(_lib.load(), "sonet_index_max_gather", data)
+    _launch(dev, "index_max_gather" if data.dtype == torch.float32 else "index_max_gather_bf16", fn, ptr(data), ptr(index), ptr(row_max), ptr(idx), ptr(val), B,
+            C, Np, int(K), what="sonet_index_max_gather")
     return idx, val
 
 
@@ -213,13 +271,7 @@ def pointmlp_bf16_pool(x1, wp, scale, shift, relu, Cout, ids, M, row_max=None, x
     never written.  -> (idx i32, val f32) B x Cout x M: exactly ``index_max_gather(pointmlp(...), ids, M, row_max)``.
     xaff = (s1, h1, relu1[, s2, h2, relu2]): x1 / x2 are RAW outputs of BatchNorm layers, normalised by the operand load."""
     _chk(x1, "x", torch.bfloat16, 3)
-    B, C1, L = x1.shape
-    C2 = 0
-    if x2 is not None:
-        _chk(x2, "x2", torch.bfloat16, 3)
-        if x2.shape[0] != B or x2.shape[2] != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.shape[1]
+    B, C1, C2, L = _layer_inputs(x1, x2, torch.bfloat16)
     if wp.dtype != torch.int16:
         raise SonetHipError("pointmlp_bf16_pool: a bf16 pack")
     _chk(ids, "ids", torch.int32, 2)
@@ -227,22 +279,17 @@ def pointmlp_bf16_pool(x1, wp, scale, shift, relu, Cout, ids, M, row_max=None, x
         raise SonetHipError("ids must be B x L")
     if row_max is not None:
         _chk(row_max, "row_max", torch.int32, 2)
-    _chk(scale, "scale", torch.float32, 1)
-    _chk(shift, "shift", torch.float32, 1)
+    _chk_cvec(Cout, 1, scale=scale, shift=shift)
     dev = _same_device(x1, x2, wp, scale, shift, ids, row_max)
     lib = _lib.load()
-    if wp.numel() != lib.sonet_pointmlp_bf16_pack_size(C1 + C2, Cout) // 2:
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C1 + C2, Cout))
-    idx = torch.empty((B, Cout, int(M)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, Cout, int(M)), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("pointmlpbf16_pool_%dx%d_L%d%s" % (C1 + C2, Cout, L, "_xaff" if xaff is not None else "")):
-        if xaff is not None:
-            check(lib.sonet_pointmlp_bf16_pool_xaff(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(ids), ptr(row_max),
-                                                    ptr(idx), ptr(val), B, Cout, L, int(M), *_xaff_args(xaff, C1, C2, dev), stream_ptr()),
-                  "sonet_pointmlp_bf16_pool_xaff")
-        else:
-            check(lib.sonet_pointmlp_bf16_pool(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(ids), ptr(row_max),
-                                               ptr(idx), ptr(val), B, Cout, L, int(M), stream_ptr()), "sonet_pointmlp_bf16_pool")
+    _chk_pack(lib, wp, "bf16", C1 + C2, Cout)
+    idx, val = _idx_val(B, Cout, M, dev)
+    args = (ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(ids), ptr(row_max), ptr(idx), ptr(val), B, Cout, L, int(M))
+    name = "pointmlpbf16_pool_%dx%d_L%d" % (C1 + C2, Cout, L)
+    if xaff is not None:
+        _launch(dev, name + "_xaff", lib.sonet_pointmlp_bf16_pool_xaff, *args, *_xaff_args(xaff, C1, C2, dev))
+    else:
+        _launch(dev, name, lib.sonet_pointmlp_bf16_pool, *args)
     return idx, val
 
 
@@ -260,13 +307,7 @@ def pointmlp_h3_segpool(x1, wp, scale, shift, relu, Cout, ids_sorted, pos0, M, r
     -> (idx i32, val f32) B x Cout x M: ``index_max_gather(pointmlp(...), ids_sorted, M, row_max)`` with pos0[b] (and the value there) in
     place of position 0 for bins nothing beat and for masked nodes."""
     _chk(x1, "x", torch.float32, 3)
-    B, C1, L = x1.shape
-    C2 = 0
-    if x2 is not None:
-        _chk(x2, "x2", torch.float32, 3)
-        if x2.shape[0] != B or x2.shape[2] != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.shape[1]
+    B, C1, C2, L = _layer_inputs(x1, x2, torch.float32)
     if wp.dtype != torch.int8:
         raise SonetHipError("pointmlp_h3_segpool: an h3 pack")
     _chk(ids_sorted, "ids_sorted", torch.int32, 2)
@@ -275,22 +316,17 @@ def pointmlp_h3_segpool(x1, wp, scale, shift, relu, Cout, ids_sorted, pos0, M, r
         raise SonetHipError("ids_sorted must be B x L and pos0 B")
     if row_max is not None:
         _chk(row_max, "row_max", torch.int32, 2)
-    _chk(scale, "scale", torch.float32, 1)
-    _chk(shift, "shift", torch.float32, 1)
+    _chk_cvec(Cout, 1, scale=scale, shift=shift)
     dev = _same_device(x1, x2, wp, scale, shift, ids_sorted, pos0, row_max)
     lib = _lib.load()
-    if wp.numel() != lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout):
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C1 + C2, Cout))
-    idx = torch.empty((B, Cout, int(M)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, Cout, int(M)), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.sonet_pointmlp_h3_segpool_ws_size(B, Cout, int(M)),), dtype=torch.uint8, device=dev)
+    _chk_pack(lib, wp, "h3", C1 + C2, Cout)
+    idx, val = _idx_val(B, Cout, M, dev)
+    ws = _ws(lib.sonet_pointmlp_h3_segpool_ws_size, dev, B, Cout, int(M))
     name = "pointmlph3_segpool_%dx%d_L%d" % (C1 + C2, Cout, L)
     _range_arm(name)
     xa = _xaff_args(xaff, C1, C2, dev) if xaff is not None else (None, None, None, None, 0)
-    with _lib.on_device(dev), _timed(name + ("_xaff" if xaff is not None else "")):
-        check(lib.sonet_pointmlp_h3_segpool_f32(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(ids_sorted), ptr(pos0),
-                                                ptr(row_max), int(M), ptr(ws), ptr(idx), ptr(val), B, Cout, L, *xa, stream_ptr()),
-              "sonet_pointmlp_h3_segpool_f32")
+    _launch(dev, name + ("_xaff" if xaff is not None else ""), lib.sonet_pointmlp_h3_segpool_f32, ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift),
+            int(bool(relu)), ptr(ids_sorted), ptr(pos0), ptr(row_max), int(M), ptr(ws), ptr(idx), ptr(val), B, Cout, L, *xa)
     return idx, val
 
 
@@ -299,16 +335,11 @@ def index_max_gather_p16(planes, index, K, row_max=None):
     layer multiplies -> (idx i32, val f32) B x C x K."""
     _chk(index, "index", torch.int32, 2)
     B, C, Np = planes.shape
-    if tuple(index.shape) != (B, Np):
-        raise SonetHipError("index must be B x N' = %s, got %s" % ((B, Np), tuple(index.shape)))
-    if row_max is not None:
-        _chk(row_max, "row_max", torch.int32, 2)
+    _chk_index(index, B, Np, row_max)
     dev = _same_device(planes.data, index, row_max)
-    idx = torch.empty((B, C, int(K)), dtype=torch.int32, device=dev)
-    val = torch.empty((B, C, int(K)), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("index_max_gather_p16"):
-        check(_lib.load().sonet_index_max_gather_p16(ptr(planes.data), ptr(index), ptr(row_max), ptr(idx), ptr(val), B, C, Np, int(K), stream_ptr()),
-              "sonet_index_max_gather_p16")
+    idx, val = _idx_val(B, C, K, dev)
+    _launch(dev, "index_max_gather_p16", _lib.load().sonet_index_max_gather_p16, ptr(planes.data), ptr(index), ptr(row_max), ptr(idx), ptr(val), B, C, Np,
+            int(K))
     return idx, val
 
 
@@ -331,12 +362,11 @@ def som_assign(x, node, k, want_i64=False):
     r.min_idx_i32 = torch.empty((B, r.k * N), dtype=torch.int32, device=dev)
     r.min_idx_i64 = torch.empty((B, r.k * N), dtype=torch.int64, device=dev) if want_i64 else None
     # one allocation, sums first (8-byte aligned), counts right behind: the library clears both with a single memset
-    ws = torch.empty((B * 3 * M * 8 + B * M * 4,), dtype=torch.uint8, device=dev)
+    ws = _ws(B * 3 * M * 8 + B * M * 4, dev)
     r.sum_ws = ws[:B * 3 * M * 8].view(torch.float64).view(B, 3, M)
     r.count = ws[B * 3 * M * 8:].view(torch.int32).view(B, M)
-    with _lib.on_device(dev), _timed("som_assign"):
-        check(_lib.load().sonet_som_assign_f32(ptr(x), ptr(node), B, N, M, r.k, ptr(r.min_idx_i32), ptr(r.min_idx_i64),
-                                               ptr(r.count), ptr(r.sum_ws), stream_ptr()), "sonet_som_assign_f32")
+    _launch(dev, "som_assign", _lib.load().sonet_som_assign_f32, ptr(x), ptr(node), B, N, M, r.k, ptr(r.min_idx_i32), ptr(r.min_idx_i64), ptr(r.count),
+            ptr(r.sum_ws))
     return r
 
 
@@ -368,9 +398,8 @@ def som_train(x, node0, w, lr):
         raise SonetHipError("w must be T x M x M (or T x M x rows x cols) with T = len(lr) = %d, M = %d, got %s" % (T, M, tuple(w.shape)))
     dev = _same_device(x, node0, w, lr)
     out = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("som_train"):
-        check(_lib.load().sonet_som_train_f32(ptr(x), ptr(node0), int(shared), ptr(w) if T else None, ptr(lr) if T else None, T, B, N, M,
-                                              ptr(out), stream_ptr()), "sonet_som_train_f32")
+    _launch(dev, "som_train", _lib.load().sonet_som_train_f32, ptr(x), ptr(node0), int(shared), ptr(w) if T else None, ptr(lr) if T else None, T, B, N, M,
+            ptr(out))
     return out
 
 
@@ -389,11 +418,8 @@ def som_group(x, sn, a, want_centers=False, want_decentered=False, want_augmente
     out["centers"] = torch.empty((B, 3, kN), dtype=torch.float32, device=dev) if want_centers else None
     out["x_decentered"] = torch.empty((B, 3, kN), dtype=torch.float32, device=dev) if want_decentered else None
     out["x_augmented"] = torch.empty((B, 6, kN), dtype=torch.float32, device=dev) if want_augmented else None
-    with _lib.on_device(dev), _timed("som_group"):
-        check(_lib.load().sonet_som_group_f32(ptr(x), ptr(sn), ptr(a.min_idx_i32), ptr(a.count), ptr(a.sum_ws),
-                                              B, N, M, k, ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["centers"]),
-                                              ptr(out["x_decentered"]), ptr(out["x_augmented"]), stream_ptr()),
-              "sonet_som_group_f32")
+    _launch(dev, "som_group", _lib.load().sonet_som_group_f32, ptr(x), ptr(sn), ptr(a.min_idx_i32), ptr(a.count), ptr(a.sum_ws), B, N, M, k,
+            ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["centers"]), ptr(out["x_decentered"]), ptr(out["x_augmented"]))
     return out
 
 
@@ -411,11 +437,8 @@ def som_sort_group(x, sn, a):
                pos0=torch.empty((B,), dtype=torch.int32, device=dev),
                node_off=torch.empty((B, M), dtype=torch.int32, device=dev), count=a.count)
     cursor = torch.empty((B, M), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("som_sort_group"):
-        check(_lib.load().sonet_som_sort_group_f32(ptr(x), ptr(sn), ptr(a.min_idx_i32), ptr(a.count), ptr(a.sum_ws), B, N, M, k,
-                                                   ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]),
-                                                   ptr(out["ids_sorted"]), ptr(out["pos0"]), ptr(out["node_off"]), ptr(cursor), stream_ptr()),
-              "sonet_som_sort_group_f32")
+    _launch(dev, "som_sort_group", _lib.load().sonet_som_sort_group_f32, ptr(x), ptr(sn), ptr(a.min_idx_i32), ptr(a.count), ptr(a.sum_ws), B, N, M, k,
+            ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]), ptr(out["ids_sorted"]), ptr(out["pos0"]), ptr(out["node_off"]), ptr(cursor))
     return out
 
 
@@ -449,7 +472,7 @@ def som_assign_sort(x, sn, node, k, want_i64=False, knn=None, deterministic=Fals
                ids_sorted=torch.empty((B, kN), dtype=torch.int32, device=dev),
                pos0=torch.empty((B,), dtype=torch.int32, device=dev),
                node_off=torch.empty((B, M), dtype=torch.int32, device=dev), count=r.count)
-    ws = torch.empty((lib.sonet_som_assign_sort_ws_size(B, N, M, k),), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.sonet_som_assign_sort_ws_size, dev, B, N, M, k)
     if knn is not None:
         knn_I, K, avg = knn
         _chk(knn_I, "knn_I", torch.int64, 3)
@@ -461,20 +484,15 @@ def som_assign_sort(x, sn, node, k, want_i64=False, knn=None, deterministic=Fals
         Lp = int(lib.sonet_knn_stage_columns(B, M, int(K)))
         prep = dict(center=torch.empty((B, 3, M), dtype=torch.float32, device=dev), center_p16=p16_flat(3, Lm, B * M, dev),
                     rec=torch.empty((Lp, 4), dtype=torch.int32, device=dev), B=B, M=M, K=int(K), G=min(16, 128 // int(K)), Lp=Lp)
-        with _lib.on_device(dev), _timed("som_assign_sort"):
-            check(lib.sonet_som_assign_sort_knn_f32(ptr(x), ptr(sn), ptr(node), B, N, M, k, ptr(r.min_idx_i32), ptr(r.min_idx_i64), ptr(r.count),
-                                                    ptr(r.sum_ws), ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]),
-                                                    ptr(out["ids_sorted"]), ptr(out["pos0"]), ptr(out["node_off"]), ptr(ws),
-                                                    ptr(knn_I), KI, int(K), int(bool(avg)), ptr(prep["center"]), ptr(prep["center_p16"].data), ptr(prep["rec"]),
-                                                    stream_ptr()), "sonet_som_assign_sort_knn_f32")
+        _launch(dev, "som_assign_sort", lib.sonet_som_assign_sort_knn_f32, ptr(x), ptr(sn), ptr(node), B, N, M, k, ptr(r.min_idx_i32), ptr(r.min_idx_i64),
+                ptr(r.count), ptr(r.sum_ws), ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]), ptr(out["ids_sorted"]), ptr(out["pos0"]),
+                ptr(out["node_off"]), ptr(ws), ptr(knn_I), KI, int(K), int(bool(avg)), ptr(prep["center"]), ptr(prep["center_p16"].data), ptr(prep["rec"]))
         out["knn_prep"] = prep
         return r, out
     fn = lib.sonet_som_assign_sort_det_f32 if deterministic else lib.sonet_som_assign_sort_f32
-    with _lib.on_device(dev), _timed("som_assign_sort_det" if deterministic else "som_assign_sort"):
-        check(fn(ptr(x), ptr(sn), ptr(node), B, N, M, k, ptr(r.min_idx_i32), ptr(r.min_idx_i64), ptr(r.count),
-                                            ptr(r.sum_ws), ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]),
-                                            ptr(out["ids_sorted"]), ptr(out["pos0"]), ptr(out["node_off"]), ptr(ws), stream_ptr()),
-              "sonet_som_assign_sort_f32")
+    _launch(dev, "som_assign_sort_det" if deterministic else "som_assign_sort", fn, ptr(x), ptr(sn), ptr(node), B, N, M, k, ptr(r.min_idx_i32),
+            ptr(r.min_idx_i64), ptr(r.count), ptr(r.sum_ws), ptr(out["som_node"]), ptr(out["row_max"]), ptr(out["x_aug_sorted"]), ptr(out["ids_sorted"]),
+            ptr(out["pos0"]), ptr(out["node_off"]), ptr(ws), what="sonet_som_assign_sort_f32")
     return r, out
 
 
@@ -483,8 +501,7 @@ def som_mask(min_idx_i32, M):
     dev = _same_device(min_idx_i32)
     B, kN = min_idx_i32.shape
     mask = torch.empty((B, kN, int(M)), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("som_mask"):
-        check(_lib.load().sonet_som_mask_i32(ptr(min_idx_i32), ptr(mask), B, kN, int(M), stream_ptr()), "sonet_som_mask_i32")
+    _launch(dev, "som_mask", _lib.load().sonet_som_mask_i32, ptr(min_idx_i32), ptr(mask), B, kN, int(M))
     return mask
 
 
@@ -496,9 +513,7 @@ def node_gather(feat, min_idx_i32):
     B, C, M = feat.shape
     kN = min_idx_i32.shape[1]
     out = torch.empty((B, C, kN), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("node_gather"):
-        check(_lib.load().sonet_node_gather_f32(ptr(feat), ptr(min_idx_i32), ptr(out), B, C, M, kN, stream_ptr()),
-              "sonet_node_gather_f32")
+    _launch(dev, "node_gather", _lib.load().sonet_node_gather_f32, ptr(feat), ptr(min_idx_i32), ptr(out), B, C, M, kN)
     return out
 
 
@@ -515,10 +530,9 @@ def node_gather_bwd(g, min_idx_i32, M):
         raise SonetHipError("node_gather_bwd: min_idx must be B x kN with the kN of the gradient")
     lib = _lib.load()
     gx = torch.empty((B, C, M), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.sonet_node_gather_bwd_ws_size(B, M, L),), dtype=torch.uint8, device=dev)
-    fn = lib.sonet_node_gather_bwd_bf16 if g.dtype == torch.bfloat16 else lib.sonet_node_gather_bwd_f32
-    with _lib.on_device(dev), _timed("node_gather_bwd"):
-        check(fn(ptr(g), ptr(min_idx_i32), ptr(gx), ptr(ws), B, C, M, L, stream_ptr()), "sonet_node_gather_bwd")
+    ws = _ws(lib.sonet_node_gather_bwd_ws_size, dev, B, M, L)
+    fn = _by_dtype(lib, "sonet_node_gather_bwd", g)
+    _launch(dev, "node_gather_bwd", fn, ptr(g), ptr(min_idx_i32), ptr(gx), ptr(ws), B, C, M, L, what="sonet_node_gather_bwd")
     return gx
 
 
@@ -558,41 +572,48 @@ def node_add_affine_act_(t, z, min_idx_i32, scale, shift, relu):
     if z.shape[0] != B or z.shape[1] != C or min_idx_i32.shape != (B, L):
         raise SonetHipError("z must be B x C x M and min_idx B x L")
     _chk_cvec(C, scale=scale, shift=shift)
-    with _lib.on_device(dev), _timed("node_add_affine_act"):
-        check(_lib.load().sonet_node_add_affine_act_f32(ptr(t), ptr(z), ptr(min_idx_i32), ptr(scale), ptr(shift), int(bool(relu)),
-                                                        B, C, L, z.shape[2], stream_ptr()), "sonet_node_add_affine_act_f32")
+    _launch(dev, "node_add_affine_act", _lib.load().sonet_node_add_affine_act_f32, ptr(t), ptr(z), ptr(min_idx_i32), ptr(scale), ptr(shift), int(bool(relu)), B,
+            C, L, z.shape[2])
     return t
+
+
+def _xaff3(xaff, C, who, ref):
+    """xaff = (scale, shift, relu) of ONE operand with C channels -> the C ABI's three arguments; ``who``: the start of the length message."""
+    xs, xh, xr = xaff
+    _chk(xs, "xaff scale", torch.float32, 1)
+    _chk(xh, "xaff shift", torch.float32, 1)
+    if xs.numel() != C or xh.numel() != C:
+        raise SonetHipError("%s = %d coefficients" % (who, C))
+    _same_device(ref, xs, xh)
+    return ptr(xs), ptr(xh), int(bool(xr))
+
+
+def _wgrad(g, x, xaff, dtype, who, ws_size, fn, fn_xaff, label):
+    """The dense weight gradient sum_b g[b] . x[b]^T of ``wgrad_x3`` / ``wgrad_bf16`` (``label``: a format with a %s for the sizes)."""
+    _chk(g, "g", dtype, 3)
+    _chk(x, "x", dtype, 3)
+    dev = _same_device(g, x)
+    B, Cout, L = g.shape
+    if x.shape[0] != B or x.shape[2] != L:
+        raise SonetHipError("%s: g B x Cout x L and x B x Cin x L" % who)
+    Cin = x.shape[1]
+    dw = torch.empty((Cout, Cin), dtype=torch.float32, device=dev)
+    if g.numel() == 0 or x.numel() == 0:
+        return dw.zero_()
+    args = (ptr(g), ptr(x), ptr(dw), ptr(_ws(ws_size, dev, B, Cout, Cin, L)), B, Cout, Cin, L)
+    if xaff is not None:
+        _launch(dev, label[1] % (Cout, Cin, L), fn_xaff, *args, *_xaff3(xaff, Cin, who + ": xaff needs Cin", x))
+    else:
+        _launch(dev, label[0] % (Cout, Cin, L), fn, *args)
+    return dw
 
 
 def wgrad_x3(g, x, xaff=None):
     """sum_b g[b] . x[b]^T: g B x Cout x L, x B x Cin x L (f32) -> Cout x Cin f32, bf16 x 3 split of both operands on the matrix cores.
     xaff = (scale, shift, relu): x holds the RAW output of a BatchNorm layer, the operand split applies act(x * scale[c] + shift[c]) first."""
-    _chk(g, "g", torch.float32, 3)
-    _chk(x, "x", torch.float32, 3)
-    dev = _same_device(g, x)
-    B, Cout, L = g.shape
-    if x.shape[0] != B or x.shape[2] != L:
-        raise SonetHipError("wgrad_x3: g B x Cout x L and x B x Cin x L")
-    Cin = x.shape[1]
     lib = _lib.load()
-    dw = torch.empty((Cout, Cin), dtype=torch.float32, device=dev)
-    if g.numel() == 0 or x.numel() == 0:
-        return dw.zero_()
-    ws = torch.empty((lib.sonet_wgrad_x3_ws_size(B, Cout, Cin, L),), dtype=torch.uint8, device=dev)
-    if xaff is not None:
-        xs, xh, xr = xaff
-        _chk(xs, "xaff scale", torch.float32, 1)
-        _chk(xh, "xaff shift", torch.float32, 1)
-        if xs.numel() != Cin or xh.numel() != Cin:
-            raise SonetHipError("wgrad_x3: xaff needs Cin = %d coefficients" % Cin)
-        _same_device(g, xs, xh)
-        with _lib.on_device(dev), _timed("wgradx3_xaff_%dx%d_L%d" % (Cout, Cin, L)):
-            check(lib.sonet_wgrad_x3_xaff_f32(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cout, Cin, L, ptr(xs), ptr(xh), int(bool(xr)), stream_ptr()),
-                  "sonet_wgrad_x3_xaff_f32")
-        return dw
-    with _lib.on_device(dev), _timed("wgradx3_%dx%d_L%d" % (Cout, Cin, L)):
-        check(lib.sonet_wgrad_x3_f32(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cout, Cin, L, stream_ptr()), "sonet_wgrad_x3_f32")
-    return dw
+    return _wgrad(g, x, xaff, torch.float32, "wgrad_x3", lib.sonet_wgrad_x3_ws_size, lib.sonet_wgrad_x3_f32, lib.sonet_wgrad_x3_xaff_f32,
+                  ("wgradx3_%dx%d_L%d", "wgradx3_xaff_%dx%d_L%d"))
 
 
 def wgrad_bf16_xaff_ok(B, Cout, Cin, L):
@@ -604,32 +625,9 @@ def wgrad_bf16(g, x, xaff=None):
     """sum_b g[b] . x[b]^T for bfloat16 operands: g B x Cout x L, x B x Cin x L -> Cout x Cin f32 (one bf16 MFMA per product, f32
     accumulation and partials, fixed-order reduction: ``sonet_wgrad_bf16``).  xaff = (scale, shift, relu): x holds the RAW output of a
     BatchNorm layer, normalised by the operand path (``sonet_wgrad_bf16_xaff``; ``wgrad_bf16_xaff_ok`` shapes)."""
-    _chk(g, "g", torch.bfloat16, 3)
-    _chk(x, "x", torch.bfloat16, 3)
-    dev = _same_device(g, x)
-    B, Cout, L = g.shape
-    if x.shape[0] != B or x.shape[2] != L:
-        raise SonetHipError("wgrad_bf16: g B x Cout x L and x B x Cin x L")
-    Cin = x.shape[1]
     lib = _lib.load()
-    dw = torch.empty((Cout, Cin), dtype=torch.float32, device=dev)
-    if g.numel() == 0 or x.numel() == 0:
-        return dw.zero_()
-    ws = torch.empty((lib.sonet_wgrad_bf16_ws_size(B, Cout, Cin, L),), dtype=torch.uint8, device=dev)
-    if xaff is not None:
-        xs, xh, xr = xaff
-        _chk(xs, "xaff scale", torch.float32, 1)
-        _chk(xh, "xaff shift", torch.float32, 1)
-        if xs.numel() != Cin or xh.numel() != Cin:
-            raise SonetHipError("wgrad_bf16: xaff needs Cin = %d coefficients" % Cin)
-        _same_device(x, xs, xh)
-        with _lib.on_device(dev), _timed("wgradbf16_%dx%d_L%d_xaff" % (Cout, Cin, L)):
-            check(lib.sonet_wgrad_bf16_xaff(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cout, Cin, L, ptr(xs), ptr(xh), int(bool(xr)), stream_ptr()),
-                  "sonet_wgrad_bf16_xaff")
-        return dw
-    with _lib.on_device(dev), _timed("wgradbf16_%dx%d_L%d" % (Cout, Cin, L)):
-        check(lib.sonet_wgrad_bf16(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cout, Cin, L, stream_ptr()), "sonet_wgrad_bf16")
-    return dw
+    return _wgrad(g, x, xaff, torch.bfloat16, "wgrad_bf16", lib.sonet_wgrad_bf16_ws_size, lib.sonet_wgrad_bf16, lib.sonet_wgrad_bf16_xaff,
+                  ("wgradbf16_%dx%d_L%d", "wgradbf16_%dx%d_L%d_xaff"))
 
 
 def node_gather_lead_affine_act(z, gidx, lead, wl, scale, shift, relu):
@@ -650,10 +648,9 @@ def node_gather_lead_affine_act(z, gidx, lead, wl, scale, shift, relu):
     gidx, lead = _aligned16(gidx), _aligned16(lead)              # (16-byte loads when L % 4 == 0; the C entry refuses misaligned ones)
     out = torch.empty((B, C, L), dtype=z.dtype, device=dev)
     lib = _lib.load()
-    fn = lib.sonet_node_gather_lead_affine_act_f32 if z.dtype == torch.float32 else lib.sonet_node_gather_lead_affine_act_bf16
-    with _lib.on_device(dev), _timed("node_gather_lead%s_%dx%d_L%d" % ("" if z.dtype == torch.float32 else "bf16", NL, C, L)):
-        check(fn(ptr(z), ptr(gidx), ptr(lead), ptr(wl), ptr(scale), ptr(shift), int(bool(relu)), ptr(out), B, C, L, M, NL, stream_ptr()),
-              "sonet_node_gather_lead_affine_act")
+    fn = _by_dtype(lib, "sonet_node_gather_lead_affine_act", z)
+    _launch(dev, "node_gather_lead%s_%dx%d_L%d" % ("" if z.dtype == torch.float32 else "bf16", NL, C, L), fn, ptr(z), ptr(gidx), ptr(lead), ptr(wl), ptr(scale),
+            ptr(shift), int(bool(relu)), ptr(out), B, C, L, M, NL, what="sonet_node_gather_lead_affine_act")
     return out
 
 
@@ -663,8 +660,7 @@ def knn_self(node, K):
     dev = _same_device(node)
     B, _, M = node.shape
     out = torch.empty((B, M, int(K)), dtype=torch.int64, device=dev)
-    with _lib.on_device(dev), _timed("knn_self"):
-        check(_lib.load().sonet_knn_self_f32(ptr(node), ptr(out), B, M, int(K), stream_ptr()), "sonet_knn_self_f32")
+    _launch(dev, "knn_self", _lib.load().sonet_knn_self_f32, ptr(node), ptr(out), B, M, int(K))
     return out
 
 
@@ -725,12 +721,9 @@ def assemble_batch(src, offsets, nodes_src, idx, N, K, flags, seed, step, replay
              bad=torch.empty((B,), dtype=torch.int32, device=dev))
     if want_draws:
         r["draws"] = torch.zeros((B, D), dtype=torch.float64, device=dev)
-    with _lib.on_device(dev), _timed("assemble_batch"):
-        check(_lib.load().sonet_assemble_batch_f32(
-            ptr(src), src.shape[1], ptr(offsets), S, ptr(nodes_src), ptr(idx), B, N, M, K, flags, _i64(seed), _i64(step), ptr(replay_idx) if replay_idx is not None else None,
-            ptr(replay_draws) if replay_draws is not None else None, ptr(r["draws"]) if want_draws else None,
-            ptr(r["pc"]), ptr(r["sn"]), ptr(r["node"]), ptr(r["chosen"]), ptr(r["knn_I"]), ptr(r["bad"]), stream_ptr()),
-            "sonet_assemble_batch_f32")
+    _launch(dev, "assemble_batch", _lib.load().sonet_assemble_batch_f32, ptr(src), src.shape[1], ptr(offsets), S, ptr(nodes_src), ptr(idx), B, N, M, K, flags,
+            _i64(seed), _i64(step), ptr(replay_idx) if replay_idx is not None else None, ptr(replay_draws) if replay_draws is not None else None,
+            ptr(r["draws"]) if want_draws else None, ptr(r["pc"]), ptr(r["sn"]), ptr(r["node"]), ptr(r["chosen"]), ptr(r["knn_I"]), ptr(r["bad"]))
     return r
 
 
@@ -744,9 +737,7 @@ def knn_group(coord, feat, knn_I, center_avg):
     K = knn_I.shape[2]
     center = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
     out = torch.empty((B, 3 + C, M, K), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("knn_group"):
-        check(_lib.load().sonet_knn_group_f32(ptr(coord), ptr(feat), ptr(knn_I), B, C, M, K, int(bool(center_avg)), ptr(center), ptr(out),
-                                              stream_ptr()), "sonet_knn_group_f32")
+    _launch(dev, "knn_group", _lib.load().sonet_knn_group_f32, ptr(coord), ptr(feat), ptr(knn_I), B, C, M, K, int(bool(center_avg)), ptr(center), ptr(out))
     return center, out
 
 
@@ -761,8 +752,7 @@ def lastdim_max(x):
     out = torch.empty(x.shape[:-1], dtype=torch.float32, device=dev)
     if out.numel() == 0:
         return out
-    with _lib.on_device(dev), _timed("lastdim_max"):
-        check(_lib.load().sonet_lastdim_max_f32(ptr(x), ptr(out), out.numel(), K, stream_ptr()), "sonet_lastdim_max_f32")
+    _launch(dev, "lastdim_max", _lib.load().sonet_lastdim_max_f32, ptr(x), ptr(out), out.numel(), K)
     return out
 
 
@@ -776,8 +766,7 @@ def knn_gather(x, knn_I):
     K = knn_I.shape[2]
     dev = _same_device(x, knn_I)
     out = torch.empty((B, C, M, K), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("knn_gather"):
-        check(_lib.load().sonet_knn_gather_f32(ptr(x), ptr(knn_I), ptr(out), B, C, M, K, stream_ptr()), "sonet_knn_gather_f32")
+    _launch(dev, "knn_gather", _lib.load().sonet_knn_gather_f32, ptr(x), ptr(knn_I), ptr(out), B, C, M, K)
     return out
 
 
@@ -793,10 +782,9 @@ def knn_gather_bwd(g, knn_I, M):
     dev = _same_device(g, knn_I)
     lib = _lib.load()
     gx = torch.empty((B, C, M), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.sonet_knn_gather_bwd_ws_size(B, M, K),), dtype=torch.uint8, device=dev)
-    fn = lib.sonet_knn_gather_bwd_bf16 if g.dtype == torch.bfloat16 else lib.sonet_knn_gather_bwd_f32
-    with _lib.on_device(dev), _timed("knn_gather_bwd"):
-        check(fn(ptr(g), ptr(knn_I), ptr(gx), ptr(ws), B, C, M, K, stream_ptr()), "sonet_knn_gather_bwd")
+    ws = _ws(lib.sonet_knn_gather_bwd_ws_size, dev, B, M, K)
+    fn = _by_dtype(lib, "sonet_knn_gather_bwd", g)
+    _launch(dev, "knn_gather_bwd", fn, ptr(g), ptr(knn_I), ptr(gx), ptr(ws), B, C, M, K, what="sonet_knn_gather_bwd")
     return gx
 
 
@@ -812,9 +800,8 @@ class _LastDimMax(torch.autograd.Function):
         out = torch.empty(xc.shape[:-1], dtype=xc.dtype, device=xc.device)
         idx = torch.empty(xc.shape[:-1], dtype=torch.int32, device=xc.device)
         lib = _lib.load()
-        fn = lib.sonet_lastdim_argmax_bf16 if xc.dtype == torch.bfloat16 else lib.sonet_lastdim_argmax_f32
-        with _lib.on_device(xc.device), _timed("lastdim_argmax"):
-            check(fn(ptr(xc), ptr(out), ptr(idx), rows, K, stream_ptr()), "sonet_lastdim_argmax")
+        fn = _by_dtype(lib, "sonet_lastdim_argmax", xc)
+        _launch(xc.device, "lastdim_argmax", fn, ptr(xc), ptr(out), ptr(idx), rows, K, what="sonet_lastdim_argmax")
         ctx.save_for_backward(idx)
         ctx.K = K
         return out
@@ -825,9 +812,8 @@ class _LastDimMax(torch.autograd.Function):
         gc = g.contiguous()
         gx = torch.empty(tuple(gc.shape) + (ctx.K,), dtype=gc.dtype, device=gc.device)
         lib = _lib.load()
-        fn = lib.sonet_lastdim_max_bwd_bf16 if gc.dtype == torch.bfloat16 else lib.sonet_lastdim_max_bwd_f32
-        with _lib.on_device(gc.device), _timed("lastdim_max_bwd"):
-            check(fn(ptr(gc), ptr(idx), ptr(gx), gc.numel(), ctx.K, stream_ptr()), "sonet_lastdim_max_bwd")
+        fn = _by_dtype(lib, "sonet_lastdim_max_bwd", gc)
+        _launch(gc.device, "lastdim_max_bwd", fn, ptr(gc), ptr(idx), ptr(gx), gc.numel(), ctx.K, what="sonet_lastdim_max_bwd")
         return gx
 
 
@@ -841,6 +827,15 @@ def lastdim_max_autograd(x):
 # ------------------------------------------------------------------------------------------ pointmlp
 import os as _os
 
+
+def _env(name, default):
+    return _os.environ.get("SONET_" + name, default)
+
+
+def _flag(name, default="1"):
+    """A SONET_<name> switch of the environment: on unless it reads "0"."""
+    return _env(name, default) != "0"
+
 # arithmetic of the fused point-wise layer:
 #   "f32": exact-f32 MFMA (v_mfma_f32_32x32x2_f32), bitwise an f32 fma chain
 #   "x3" : bf16 MFMA on a 3-way bf16 split of both operands (six terms), f32 accumulate: f32-class accuracy (the
@@ -850,36 +845,36 @@ import os as _os
 #   "h3" : fp16 MFMA on a two-piece fp16 split with scaled residuals (three terms): the same accuracy at half the
 #          matrix work, fp16 operand RANGE (|x| <= 2047 clamped, relative precision fades below ~1e-4) -- DEFAULT for
 #          the forward layers (coordinates, normalised activations); gradients (dgrad) always use "x3"
-POINTMLP_PRECISION = _os.environ.get("SONET_POINTMLP_PRECISION", "h3")
+POINTMLP_PRECISION = _env("POINTMLP_PRECISION", "h3")
 
 
 # run the encoder's first PointNet (eval mode, "x3" arithmetic) as one fused kernel
-FUSE_POINTRESNET = _os.environ.get("SONET_FUSE_POINTRESNET", "1") != "0"
+FUSE_POINTRESNET = _flag("FUSE_POINTRESNET")
 # ... and pool it per node in the same kernel (no first_pn_out in HBM unless a caller reads the attribute)
-FUSE_POOL = _os.environ.get("SONET_FUSE_POOL", "1") != "0"
+FUSE_POOL = _flag("FUSE_POOL")
 # no-grad node-level stage (KNNModule + final PointNet) without the gathered tensor and without concats: the neighbour
 # gather happens in the first layer's operand loads, narrow leading panels go last through a rotated weight pack (h3 only)
-GATHER_NODE_STAGE = _os.environ.get("SONET_GATHER_NODE_STAGE", "1") != "0"
+GATHER_NODE_STAGE = _flag("GATHER_NODE_STAGE")
 # KNNModule layer 1 as (layer on the M node features) + gather + coordinate channels instead of a layer over K * M gathered columns
-NODE_LINEAR_SPLIT = _os.environ.get("SONET_NODE_LINEAR_SPLIT", "1") != "0"
+NODE_LINEAR_SPLIT = _flag("NODE_LINEAR_SPLIT")
 # no-grad h3 chains of point-wise layers hand their activations on pre-split (P16 planes, csrc/pointmlp_h3p.hip) instead of as f32
-P16_CHAINS = _os.environ.get("SONET_P16_CHAINS", "1") != "0"
+P16_CHAINS = _flag("P16_CHAINS")
 # no-grad node-level stage (KNNModule + final PointNet + global max) on the third-generation layer, flat column axis, max-over-group
 # epilogues (csrc/node_stage.hip): 5 launches instead of 8 (4 with KNN_FUSED_LAYER2 below).  0 = the round-4 stage (second-generation layers + planes_max / lastdim_max)
-NODE_STAGE_P16 = _os.environ.get("SONET_NODE_STAGE_P16", "1") != "0"
+NODE_STAGE_P16 = _flag("NODE_STAGE_P16")
 # ... with KNNModule's second layer building its own input in LDS (csrc/knn_layer.hip): 4 launches, h1 never written.  0 = knn_stage_input +
 # pointmlp_h3p_gmax; the same planes and range words either way
-KNN_FUSED_LAYER2 = _os.environ.get("SONET_KNN_FUSED_LAYER2", "1") != "0"
+KNN_FUSED_LAYER2 = _flag("KNN_FUSED_LAYER2")
 # bf16 training: the last layer of the first PointNet + the per-node arg-max pool in one launch, first_pn_out never written (0 = store + index_max)
-POOLED_TRAIN_EPILOGUE = _os.environ.get("SONET_POOLED_TRAIN_EPILOGUE", "1") != "0"
+POOLED_TRAIN_EPILOGUE = _flag("POOLED_TRAIN_EPILOGUE")
 # f32-class training: the same on node-sorted columns (sonet_pointmlp_h3_segpool_f32; 0 = store + index_max)
-H3_SEGPOOL = _os.environ.get("SONET_H3_SEGPOOL", "1") != "0"
+H3_SEGPOOL = _flag("H3_SEGPOOL")
 # ... and the hidden layers of the first PointNet hand their RAW outputs on: normalise + ReLU is applied by the consumers' operand loads
 # (next layer, weight gradient, pooled weight gradient); the normalised activations are never written (0 = a normalise pass per layer)
-H3_NORM_ON_LOAD = _os.environ.get("SONET_H3_NORM_ON_LOAD", "1") != "0"
+H3_NORM_ON_LOAD = _flag("H3_NORM_ON_LOAD")
 # the sorted training path takes its assignment + node-sorted grouping from the two-launch SOM stage of the no-grad path (0 = som_assign + som_sort_group)
-TRAIN_ASSIGN_SORT = _os.environ.get("SONET_TRAIN_ASSIGN_SORT", "1") != "0"
-WGRAD_KERNEL = _os.environ.get("SONET_WGRAD_KERNEL", "1") != "0"       # 0: torch.bmm (hipBLASLt f32) for the dense weight gradients
+TRAIN_ASSIGN_SORT = _flag("TRAIN_ASSIGN_SORT")
+WGRAD_KERNEL = _flag("WGRAD_KERNEL")       # 0: torch.bmm (hipBLASLt f32) for the dense weight gradients
 
 
 # ---- operand-range guard of the fp16-split ("h3") arithmetic ------------------------------------------------------------------
@@ -889,7 +884,7 @@ WGRAD_KERNEL = _os.environ.get("SONET_WGRAD_KERNEL", "1") != "0"       # 0: torc
 # Encoder.forward (models/networks.py) wraps itself in a scope and recomputes the batch in the range-safe "x3" arithmetic when
 # the log says so -- so the default arithmetic can never hand back clamped features silently.  SONET_RANGE_GUARD=0 turns the
 # whole mechanism off (no log, no read-back).
-RANGE_GUARD = _os.environ.get("SONET_RANGE_GUARD", "1") != "0"
+RANGE_GUARD = _flag("RANGE_GUARD")
 _RANGE_SLOTS = 32
 _B_2047, _B_65504, _B_XLOW, _B_WLOW, _B_WLOW32 = 0x44FFE000, 0x477FE000, 0x3E800000, 0x3B800000, 0x3E000000   # bits of 2047, 65504, 2^-2, 2^-8, 2^-3
 _range_logs = {}            # device index -> int32[_RANGE_SLOTS * 8]
@@ -1175,19 +1170,18 @@ def pointmlp_pack(weight2d, mode="f32"):
     dev = _same_device(weight2d)
     Cout, Cin = weight2d.shape
     lib = _lib.load()
-    with _lib.on_device(dev):
-        if mode == "x3":
-            wp = torch.empty((lib.sonet_pointmlp_x3_pack_size(Cin, Cout),), dtype=torch.uint8, device=dev)
-            check(lib.sonet_pointmlp_x3_pack(ptr(weight2d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_pointmlp_x3_pack")
-        elif mode == "bf16":                                 # bf16 storage / bf16 MFMA (int16 marks the flavour)
-            wp = torch.empty((lib.sonet_pointmlp_bf16_pack_size(Cin, Cout) // 2,), dtype=torch.int16, device=dev)
-            check(lib.sonet_pointmlp_bf16_pack(ptr(weight2d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_pointmlp_bf16_pack")
-        elif mode == "h3":                                   # same size; int8 marks the fp16 flavour
-            wp = torch.empty((lib.sonet_pointmlp_x3_pack_size(Cin, Cout),), dtype=torch.int8, device=dev)
-            check(lib.sonet_pointmlp_h3_pack(ptr(weight2d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_pointmlp_h3_pack")
-        else:
-            wp = torch.empty((lib.sonet_pointmlp_pack_size(Cin, Cout),), dtype=torch.float32, device=dev)
-            check(lib.sonet_pointmlp_pack_f32(ptr(weight2d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_pointmlp_pack_f32")
+    kind = mode if mode in ("x3", "h3", "bf16") else "f32"     # (the dtype of the pack marks its flavour: ``_PACKS``)
+    wp = _pack_empty(lib, kind, Cin, Cout, dev)
+    _launch(dev, None, lib.sonet_pointmlp_pack_f32 if kind == "f32" else getattr(lib, "sonet_pointmlp_%s_pack" % kind), ptr(weight2d), ptr(wp), Cin, Cout)
+    return wp
+
+
+def _pack_strided(lib, kind, src, rs, cs, Cin_p, Cout_p, rows, dev):
+    """-> the bf16 / x3 / h3 pack of the rows x Cin_p f32 matrix at address ``src`` (row and column strides rs, cs in elements), with zero
+    rows up to Cout_p."""
+    wp = _pack_empty(lib, kind, Cin_p, Cout_p, dev)
+    _launch(dev, None, getattr(lib, "sonet_pointmlp_%s_pack_strided" % kind), src, rs, cs, ptr(wp), Cin_p, Cout_p, rows,
+            what="sonet_pointmlp_%s_pack_strided" % ("bf16" if kind == "bf16" else "x3"))
     return wp
 
 
@@ -1200,22 +1194,13 @@ def pointmlp_pack_transposed(weight2d, lo, Ci, Cp, mode):
     if not (0 <= lo and lo + Ci <= Cin and Ci <= Cp):
         raise SonetHipError("pointmlp_pack_transposed: bad block lo=%d Ci=%d Cp=%d of %d columns" % (lo, Ci, Cp, Cin))
     lib = _lib.load()
-    src = weight2d.data_ptr() + 4 * lo
-    with _lib.on_device(dev):
-        if mode == "bf16":
-            wp = torch.empty((lib.sonet_pointmlp_bf16_pack_size(Cout, Cp) // 2,), dtype=torch.int16, device=dev)
-            check(lib.sonet_pointmlp_bf16_pack_strided(src, 1, Cin, ptr(wp), Cout, Cp, Ci, stream_ptr()), "sonet_pointmlp_bf16_pack_strided")
-        elif mode in ("x3", "h3"):
-            wp = torch.empty((lib.sonet_pointmlp_x3_pack_size(Cout, Cp),), dtype=torch.uint8 if mode == "x3" else torch.int8, device=dev)
-            fn = lib.sonet_pointmlp_x3_pack_strided if mode == "x3" else lib.sonet_pointmlp_h3_pack_strided
-            check(fn(src, 1, Cin, ptr(wp), Cout, Cp, Ci, stream_ptr()), "sonet_pointmlp_x3_pack_strided")
-        else:
-            raise SonetHipError("pointmlp_pack_transposed: mode %r" % (mode,))
-    return wp
+    if mode not in ("bf16", "x3", "h3"):
+        raise SonetHipError("pointmlp_pack_transposed: mode %r" % (mode,))
+    return _pack_strided(lib, mode, weight2d.data_ptr() + 4 * lo, 1, Cin, Cout, Cp, Ci, dev)
 
 
 # ---- every stale weight pack of a step in one launch -------------------------------------------------------------------------------
-PACK_REGISTRY = _os.environ.get("SONET_PACK_REGISTRY", "1") != "0"     # 0: a pack launch per layer and flavour (the round-4 behaviour)
+PACK_REGISTRY = _flag("PACK_REGISTRY")     # 0: a pack launch per layer and flavour (the round-4 behaviour)
 
 
 class _PackRegistry:
@@ -1259,14 +1244,7 @@ class _PackRegistry:
         lib = _lib.load()
         fl, off, rs, cs, Cin_p, rows, Cout_p = self._spec(w2d, what)
         dev = w2d.device
-        with _lib.on_device(dev):
-            if fl == 0:
-                buf = torch.empty((lib.sonet_pointmlp_bf16_pack_size(Cin_p, Cout_p) // 2,), dtype=torch.int16, device=dev)
-                check(lib.sonet_pointmlp_bf16_pack_strided(w2d.data_ptr() + off, rs, cs, ptr(buf), Cin_p, Cout_p, rows, stream_ptr()), "sonet_pointmlp_bf16_pack_strided")
-            else:
-                buf = torch.empty((lib.sonet_pointmlp_x3_pack_size(Cin_p, Cout_p),), dtype=torch.uint8 if fl == 1 else torch.int8, device=dev)
-                fn = lib.sonet_pointmlp_x3_pack_strided if fl == 1 else lib.sonet_pointmlp_h3_pack_strided
-                check(fn(w2d.data_ptr() + off, rs, cs, ptr(buf), Cin_p, Cout_p, rows, stream_ptr()), "sonet_pointmlp_x3_pack_strided")
+        buf = _pack_strided(lib, ("bf16", "x3", "h3")[fl], w2d.data_ptr() + off, rs, cs, Cin_p, Cout_p, rows, dev)
         KC = int(lib.sonet_pack_multi_kc(fl, Cin_p))
         total = 64 * ((Cout_p + 31) // 32) * KC
         # (the weakref is to the view's base when there is one: views come and go, the parameter stays)
@@ -1329,8 +1307,7 @@ class _PackRegistry:
             with _lib.on_device(device):
                 tab = (keys, torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(device), blk)
             self.tables[di] = tab
-        with _lib.on_device(device), _timed("pack_multi_%d" % len(live)):
-            check(_lib.load().sonet_pack_multi(ptr(tab[1]), len(live), tab[2], stream_ptr()), "sonet_pack_multi")
+        _launch(device, "pack_multi_%d" % len(live), _lib.load().sonet_pack_multi, ptr(tab[1]), len(live), tab[2])
         for _, e, t in live:
             e["version"] = t._version
 
@@ -1354,25 +1331,18 @@ def pointmlp(x1, wp, scale, shift, relu, Cout, x2=None, out=None, gidx=None, acc
         if wp.dtype not in (torch.int8, torch.int16) or gidx.shape[0] != B:
             raise SonetHipError("pointmlp: a gather index needs an h3 or bf16 pack and B rows")
         L = gidx.shape[1]
-    C2 = 0
-    if x2 is not None:
-        _chk(x2, "x2", xdt, 3)
-        if x2.shape[0] != B or x2.shape[2] != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.shape[1]
-    _chk(scale, "scale", torch.float32, 1)
-    _chk(shift, "shift", torch.float32, 1)
+    _, _, C2, _ = _layer_inputs(x1, x2, xdt, L)
+    _chk_cvec(Cout, 1, scale=scale, shift=shift)
     dev = _same_device(x1, x2, wp, scale, shift, gidx)
     lib = _lib.load()
     h3 = wp.dtype == torch.int8
     x3 = wp.dtype == torch.uint8 or h3
-    want = (lib.sonet_pointmlp_bf16_pack_size(C1 + C2, Cout) // 2 if bf16 else lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout) if x3
-            else lib.sonet_pointmlp_pack_size(C1 + C2, Cout))
-    if wp.numel() != want:
-        raise SonetHipError("packed weight has %d elements, expected %d for Cin=%d Cout=%d" % (wp.numel(), want, C1 + C2, Cout))
+    _chk_pack(lib, wp, "bf16" if bf16 else "x3" if x3 else "f32", C1 + C2, Cout, "elements")
     y = out if out is not None else torch.empty((B, Cout, L), dtype=xdt, device=dev)
     if y.numel() == 0:
         return y
+    head = (ptr(x1), C1, L1, ptr(gidx)) if gidx is not None else (ptr(x1), C1)
+    args = head + (ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)))
     if bf16:
         if y.dtype != torch.bfloat16:
             raise SonetHipError("pointmlp: a bf16 pack writes a bfloat16 output")
@@ -1381,42 +1351,32 @@ def pointmlp(x1, wp, scale, shift, relu, Cout, x2=None, out=None, gidx=None, acc
             if tuple(acc.shape) != (B, Cout, L) or gidx is not None or L % 2:
                 raise SonetHipError("pointmlp: acc must be B x Cout x L (even L, no gather index)")
             _same_device(x1, acc)
-            with _lib.on_device(dev), _timed("pointmlpbf16_acc_%dx%d_L%d" % (C1 + C2, Cout, L)):
-                check(lib.sonet_pointmlp_bf16_acc(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(acc), ptr(y),
-                                                  B, Cout, L, stream_ptr()), "sonet_pointmlp_bf16_acc")
+            _launch(dev, "pointmlpbf16_acc_%dx%d_L%d" % (C1 + C2, Cout, L), lib.sonet_pointmlp_bf16_acc, *args, ptr(acc), ptr(y), B, Cout, L)
             return y
-        with _lib.on_device(dev), _timed("pointmlpbf16_%dx%d_L%d" % (C1 + C2, Cout, L)):
-            if gidx is not None:
-                check(lib.sonet_pointmlp_bf16_gather(ptr(x1), C1, L1, ptr(gidx), ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)),
-                                                     ptr(y), B, Cout, L, stream_ptr()), "sonet_pointmlp_bf16_gather")
-            else:
-                check(lib.sonet_pointmlp_bf16(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y),
-                                              B, Cout, L, stream_ptr()), "sonet_pointmlp_bf16")
+        _launch(dev, "pointmlpbf16_%dx%d_L%d" % (C1 + C2, Cout, L), lib.sonet_pointmlp_bf16_gather if gidx is not None else lib.sonet_pointmlp_bf16,
+                *args, ptr(y), B, Cout, L)
         return y
-    fn = lib.sonet_pointmlp_h3_f32 if h3 else lib.sonet_pointmlp_x3_f32 if x3 else lib.sonet_pointmlp_f32
     name = "pointmlp%s_%dx%d_L%d" % ("h3" if h3 else "x3" if x3 else "", C1 + C2, Cout, L)
     if h3:
         _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        if gidx is not None:
-            check(lib.sonet_pointmlp_h3_gather_f32(ptr(x1), C1, L1, ptr(gidx), ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)),
-                                                   ptr(y), B, Cout, L, stream_ptr()), "sonet_pointmlp_h3_gather_f32")
-        else:
-            check(fn(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y),
-                     B, Cout, L, stream_ptr()), "sonet_pointmlp")
+    if gidx is not None:
+        _launch(dev, name, lib.sonet_pointmlp_h3_gather_f32, *args, ptr(y), B, Cout, L)
+    else:
+        _launch(dev, name, lib.sonet_pointmlp_h3_f32 if h3 else lib.sonet_pointmlp_x3_f32 if x3 else lib.sonet_pointmlp_f32, *args, ptr(y), B, Cout, L,
+                what="sonet_pointmlp")
     return y
 
 
 # f32-class training backward: the BatchNorm / ReLU backward of a layer is applied by the operand load of its input-gradient launch, which also
 # writes g_raw for the weight gradient (sonet_pointmlp_x3_bnb_f32; 0 = a pass of its own, sonet_pointwise_bwd_apply_f32)
-BNB_ON_LOAD = _os.environ.get("SONET_BNB_ON_LOAD", "1") != "0"
+BNB_ON_LOAD = _flag("BNB_ON_LOAD")
 
 
 # ... and, when the layer BELOW handed its raw output on (normalise-on-load), the same launch's epilogue can compute that layer's BatchNorm-backward
 # sums from its output (no statistics pass over (gy, raw) of the layer below).  OFF: measured slower -- the reduction costs the dgrad launch 0.33-0.44 ms
 # for the 0.2-0.3 ms pass it replaces (docs/findings.md R5.9); kept as a tested record.
 # VARIANTS build only (the product library compiles neither this epilogue nor the tail below: ``variants_only()``).
-BWD_STATS_EPILOGUE = _os.environ.get("SONET_BWD_STATS_EPILOGUE", "0") != "0"
+BWD_STATS_EPILOGUE = _flag("BWD_STATS_EPILOGUE", "0")
 
 
 def variants_only():
@@ -1426,7 +1386,31 @@ def variants_only():
 
 # a tensor with two consumers in the first PointNet (the first layer's output): the gradient of the consumer whose backward runs first is added by
 # the store of the other's input-gradient launch (models/layers.py ``_GradCarry``; 0 = autograd's accumulation, a pass over three tensors)
-GRAD_CARRY = _os.environ.get("SONET_GRAD_CARRY", "1") != "0"
+GRAD_CARRY = _flag("GRAD_CARRY")
+
+
+def _bnb_inputs(who, kind, dtype, gy, raw, wpt, scale, shift, coeffs, Cout):
+    """The operands ``pointmlp_x3_bnb`` and ``pointmlp_bf16_bnb`` share: (gy, raw) B x C x L of ``dtype``, a ``kind`` pack for C -> Cout, Cout
+    output coefficients (scale, shift) and C input coefficients each -> (B, C, L, device, library)."""
+    _chk(gy, "gy", dtype, 3)
+    _chk(raw, "raw", dtype, 3)
+    if raw.shape != gy.shape:
+        raise SonetHipError("%s: gy and raw must have the same shape" % who)
+    B, C, L = gy.shape
+    if wpt.dtype != _PACKS[kind][0]:
+        raise SonetHipError("%s: %s %s pack" % (who, "an" if kind == "x3" else "a", kind))
+    for t in (scale, shift):
+        _chk(t, "scale / shift", torch.float32, 1)
+        if t.numel() != Cout:
+            raise SonetHipError("%s: %d output coefficients expected" % (who, Cout))
+    for t in coeffs:
+        _chk(t, "coefficient", torch.float32, 1)
+        if t.numel() != C:
+            raise SonetHipError("%s: %d coefficients expected" % (who, C))
+    dev = _same_device(gy, raw, wpt, scale, shift, *coeffs)
+    lib = _lib.load()
+    _chk_pack(lib, wpt, kind, C, Cout)
+    return B, C, L, dev, lib
 
 
 def pointmlp_x3_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, want_g_raw=True, below=None, acc=None):
@@ -1436,23 +1420,7 @@ def pointmlp_x3_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, wa
     layout of ``pointwise_bwd_stats(..., want_sums=True)``) from the epilogue.
     acc (B x Cout x L, f32): another gradient of the same tensor, computed earlier -- y = the product + acc from the store of this launch (what
     autograd's accumulation of the two would hold, bit for bit); not together with ``below``."""
-    _chk(gy, "gy", torch.float32, 3)
-    _chk(raw, "raw", torch.float32, 3)
-    if raw.shape != gy.shape:
-        raise SonetHipError("pointmlp_x3_bnb: gy and raw must have the same shape")
-    B, C, L = gy.shape
-    if wpt.dtype != torch.uint8:
-        raise SonetHipError("pointmlp_x3_bnb: an x3 pack")
-    for t in (scale, shift):
-        _chk(t, "scale / shift", torch.float32, 1)
-    for t in (a, b, c0, sc, sh):
-        _chk(t, "coefficient", torch.float32, 1)
-        if t.numel() != C:
-            raise SonetHipError("pointmlp_x3_bnb: %d coefficients expected" % C)
-    dev = _same_device(gy, raw, wpt, scale, shift, a, b, c0, sc, sh)
-    lib = _lib.load()
-    if wpt.numel() != lib.sonet_pointmlp_x3_pack_size(C, Cout):
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C, Cout))
+    B, C, L, dev, lib = _bnb_inputs("pointmlp_x3_bnb", "x3", torch.float32, gy, raw, wpt, scale, shift, (a, b, c0, sc, sh), Cout)
     y = torch.empty((B, Cout, L), dtype=torch.float32, device=dev)
     g_raw = torch.empty_like(gy) if want_g_raw else None
     if y.numel() == 0:
@@ -1464,10 +1432,8 @@ def pointmlp_x3_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, wa
         if below is not None or tuple(acc.shape) != (B, Cout, L):
             raise SonetHipError("pointmlp_x3_bnb: acc must be B x Cout x L and does not combine with the sums of the layer below")
         _same_device(gy, acc)
-        with _lib.on_device(dev), _timed("pointmlpx3_bnba_%dx%d_L%d" % (C, Cout, L)):
-            check(lib.sonet_pointmlp_x3_bnb_acc_f32(ptr(gy), ptr(raw), C, ptr(wpt), ptr(scale), ptr(shift), ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh),
-                                                    int(bool(relu)), ptr(g_raw), ptr(acc), ptr(y), B, Cout, L, stream_ptr()),
-                  "sonet_pointmlp_x3_bnb_acc_f32")
+        _launch(dev, "pointmlpx3_bnba_%dx%d_L%d" % (C, Cout, L), lib.sonet_pointmlp_x3_bnb_acc_f32, ptr(gy), ptr(raw), C, ptr(wpt), ptr(scale), ptr(shift),
+                ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh), int(bool(relu)), ptr(g_raw), ptr(acc), ptr(y), B, Cout, L)
         return y, g_raw
     if below is not None:
         praw, psc, psh, prelu = below
@@ -1477,12 +1443,11 @@ def pointmlp_x3_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, wa
         _chk(psc, "psc", torch.float32, 1)
         _chk(psh, "psh", torch.float32, 1)
         _same_device(gy, praw, psc, psh)
-        pws = torch.empty((lib.sonet_pointmlp_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
+        pws = _ws(lib.sonet_pointmlp_stats_ws_size, dev, B, Cout, L)
         sums = torch.empty((2 * Cout,), dtype=torch.float64, device=dev)
-    with _lib.on_device(dev), _timed("pointmlpx3_bnb%s_%dx%d_L%d" % ("s" if below is not None else "", C, Cout, L)):
-        check(lib.sonet_pointmlp_x3_bnb_f32(ptr(gy), ptr(raw), C, ptr(wpt), ptr(scale), ptr(shift), ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh),
-                                            int(bool(relu)), ptr(g_raw), ptr(y), B, Cout, L, ptr(praw), ptr(psc), ptr(psh), int(bool(prelu)),
-                                            ptr(pws), ptr(sums), stream_ptr()), "sonet_pointmlp_x3_bnb_f32")
+    _launch(dev, "pointmlpx3_bnb%s_%dx%d_L%d" % ("s" if below is not None else "", C, Cout, L), lib.sonet_pointmlp_x3_bnb_f32, ptr(gy), ptr(raw), C, ptr(wpt),
+            ptr(scale), ptr(shift), ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh), int(bool(relu)), ptr(g_raw), ptr(y), B, Cout, L, ptr(praw), ptr(psc), ptr(psh),
+            int(bool(prelu)), ptr(pws), ptr(sums))
     if below is not None:
         return y, g_raw, sums
     return y, g_raw
@@ -1497,25 +1462,7 @@ def pointmlp_bf16_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, 
     """bf16((W . g_raw) * scale + shift) [+ acc] with g_raw = bf16(a * (gy masked by raw * sc + sh > 0 when relu) + b * raw + c0) per input
     channel, in one pass over (gy, raw) -- ``pointwise_bwd_apply`` + ``pointmlp`` (or its ``acc`` form) on a bf16 pack, bit for bit
     (``sonet_pointmlp_bf16_bnb``).  -> (y B x Cout x L bf16, g_raw or None)."""
-    _chk(gy, "gy", torch.bfloat16, 3)
-    _chk(raw, "raw", torch.bfloat16, 3)
-    if raw.shape != gy.shape:
-        raise SonetHipError("pointmlp_bf16_bnb: gy and raw must have the same shape")
-    B, C, L = gy.shape
-    if wpt.dtype != torch.int16:
-        raise SonetHipError("pointmlp_bf16_bnb: a bf16 pack")
-    for t in (scale, shift):
-        _chk(t, "scale / shift", torch.float32, 1)
-        if t.numel() != Cout:
-            raise SonetHipError("pointmlp_bf16_bnb: %d output coefficients expected" % Cout)
-    for t in (a, b, c0, sc, sh):
-        _chk(t, "coefficient", torch.float32, 1)
-        if t.numel() != C:
-            raise SonetHipError("pointmlp_bf16_bnb: %d coefficients expected" % C)
-    dev = _same_device(gy, raw, wpt, scale, shift, a, b, c0, sc, sh)
-    lib = _lib.load()
-    if wpt.numel() * wpt.element_size() != lib.sonet_pointmlp_bf16_pack_size(C, Cout):
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C, Cout))
+    B, C, L, dev, lib = _bnb_inputs("pointmlp_bf16_bnb", "bf16", torch.bfloat16, gy, raw, wpt, scale, shift, (a, b, c0, sc, sh), Cout)
     if not pointmlp_bf16_bnb_ok(C, Cout, L):
         raise SonetHipError("pointmlp_bf16_bnb: needs C %% 16 == 0, 32 <= C <= 512, Cout %% 64 == 0, even L (got C=%d Cout=%d L=%d)" % (C, Cout, L))
     if acc is not None:
@@ -1527,9 +1474,8 @@ def pointmlp_bf16_bnb(gy, raw, wpt, scale, shift, a, b, c0, sc, sh, relu, Cout, 
     g_raw = torch.empty_like(gy) if want_g_raw else None
     if y.numel() == 0:
         return y, g_raw
-    with _lib.on_device(dev), _timed("pointmlpbf16_bnb%s_%dx%d_L%d" % ("a" if acc is not None else "", C, Cout, L)):
-        check(lib.sonet_pointmlp_bf16_bnb(ptr(gy), ptr(raw), C, ptr(wpt), ptr(scale), ptr(shift), ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh),
-                                          int(bool(relu)), ptr(g_raw), ptr(acc), ptr(y), B, Cout, L, stream_ptr()), "sonet_pointmlp_bf16_bnb")
+    _launch(dev, "pointmlpbf16_bnb%s_%dx%d_L%d" % ("a" if acc is not None else "", C, Cout, L), lib.sonet_pointmlp_bf16_bnb, ptr(gy), ptr(raw), C, ptr(wpt),
+            ptr(scale), ptr(shift), ptr(a), ptr(b), ptr(c0), ptr(sc), ptr(sh), int(bool(relu)), ptr(g_raw), ptr(acc), ptr(y), B, Cout, L)
     return y, g_raw
 
 
@@ -1541,30 +1487,24 @@ def pointmlp_nodeadd(x1, wp, scale, shift, relu, Cout, z, zidx, x2=None):
     _chk(x1, "x", torch.float32, 3)
     _chk(z, "z", torch.float32, 3)
     _chk(zidx, "zidx", torch.int32, 2)
-    B, C1, L = x1.shape
-    C2 = 0
-    if x2 is not None:
-        _chk(x2, "x2", torch.float32, 3)
-        if x2.shape[0] != B or x2.shape[2] != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.shape[1]
+    B, C1, C2, L = _layer_inputs(x1, x2, torch.float32)
     dev = _same_device(x1, x2, wp, scale, shift, z, zidx)
     lib = _lib.load()
-    if wp.numel() != lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout) or tuple(z.shape[:2]) != (B, Cout) or tuple(zidx.shape) != (B, L):
+    if wp.numel() != _pack_bytes(lib, "h3", C1 + C2, Cout) or tuple(z.shape[:2]) != (B, Cout) or tuple(zidx.shape) != (B, L):
         raise SonetHipError("pointmlp_nodeadd: pack for Cin=%d Cout=%d, z B x Cout x M, zidx B x L" % (C1 + C2, Cout))
+    _chk_cvec(Cout, scale=scale, shift=shift)
     y = torch.empty((B, Cout, L), dtype=torch.float32, device=dev)
     name = "pointmlph3_nodeadd_%dx%d_L%d" % (C1 + C2, Cout, L)
     _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        check(lib.sonet_pointmlp_h3_nodeadd_f32(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L,
-                                                ptr(z), ptr(zidx), z.shape[2], stream_ptr()), "sonet_pointmlp_h3_nodeadd_f32")
+    _launch(dev, name, lib.sonet_pointmlp_h3_nodeadd_f32, ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L,
+            ptr(z), ptr(zidx), z.shape[2])
     return y
 
 
 # backward: the weight gradient of a layer does not depend on its input gradient -- the two run on two HIP streams
-BWD_SIDE_STREAM = _os.environ.get("SONET_BWD_SIDE_STREAM", "1") != "0"
+BWD_SIDE_STREAM = _flag("BWD_SIDE_STREAM")
 # ... of the pooled last layer in particular: its sparse weight gradient beside its sparse input gradient (0 = one after the other)
-POOLED_SIDE_STREAM = _os.environ.get("SONET_POOLED_SIDE_STREAM", "1") != "0"
+POOLED_SIDE_STREAM = _flag("POOLED_SIDE_STREAM")
 _side_streams = {}
 
 
@@ -1634,7 +1574,7 @@ class side_stream:
 
 # weight gradients are not needed before the backward pass is over: their side-stream launches are joined there (0 = at the end of every
 # layer's backward, the behaviour up to round 5's first session)
-DEFER_WGRAD_JOIN = _os.environ.get("SONET_DEFER_WGRAD_JOIN", "1") != "0"
+DEFER_WGRAD_JOIN = _flag("DEFER_WGRAD_JOIN")
 _graph_task_id = getattr(torch._C, "_current_graph_task_id", None)
 _pending_join = {}               # device index -> (main stream, side stream) with launches nobody has waited for yet (under _join_lock)
 _join_queued = [-1]             # id of the autograd graph task whose end-of-pass callback is queued
@@ -1656,16 +1596,16 @@ def _end_of_backward_join():
     join_side_streams()
 
 
-STATS_EPILOGUE = _os.environ.get("SONET_STATS_EPILOGUE", "1") != "0"   # 0: BatchNorm batch statistics by a separate pass (channel_stats)
+STATS_EPILOGUE = _flag("STATS_EPILOGUE")   # 0: BatchNorm batch statistics by a separate pass (channel_stats)
 
 
 # bf16 training (BASELINE configs[1]): the same for the bf16 layers -- the normalise + ReLU pass of the first PointNet's hidden layers (three
 # streams over B x C x kN bf16 tensors per step) is gone; the streaming layer kernel, the pooled last layer and the two weight-gradient kernels
 # apply act(raw * scale + shift) to their operands (sonet_pointmlp_bf16_stats_xaff / _pool_xaff, sonet_wgrad_bf16_xaff, sonet_pooled_wgrad_xaff_xbf16)
-BF16_NORM_ON_LOAD = _os.environ.get("SONET_BF16_NORM_ON_LOAD", "1") != "0"
+BF16_NORM_ON_LOAD = _flag("BF16_NORM_ON_LOAD")
 # ... and the BatchNorm / ReLU backward of the bf16 hidden layers rides on the operand load of the input-gradient launch (sonet_pointmlp_bf16_bnb)
 # instead of being a pass over (gy, raw) that writes g_raw for the launch to read back
-BF16_BNB_ON_LOAD = _os.environ.get("SONET_BF16_BNB_ON_LOAD", "1") != "0"
+BF16_BNB_ON_LOAD = _flag("BF16_BNB_ON_LOAD")
 
 
 def bf16_xaff_ok(B, C1, C2, Cout, L):
@@ -1705,53 +1645,28 @@ def pointmlp_stats(x1, wp, scale, shift, relu, Cout, x2=None, xaff=None):
         raise SonetHipError("pointmlp_stats: an h3, x3 or bf16 pack")
     xdt = torch.bfloat16 if bf16 else torch.float32
     _chk(x1, "x", xdt, 3)
-    B, C1, L = x1.shape
-    C2 = 0
-    if x2 is not None:
-        _chk(x2, "x2", xdt, 3)
-        if x2.shape[0] != B or x2.shape[2] != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.shape[1]
+    B, C1, C2, L = _layer_inputs(x1, x2, xdt)
     dev = _same_device(x1, x2, wp, scale, shift)
     lib = _lib.load()
-    want = lib.sonet_pointmlp_bf16_pack_size(C1 + C2, Cout) // 2 if bf16 else lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout)
-    if wp.numel() != want:
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C1 + C2, Cout))
+    _chk_pack(lib, wp, "bf16" if bf16 else "h3", C1 + C2, Cout)
+    _chk_cvec(Cout, scale=scale, shift=shift)
     y = torch.empty((B, Cout, L), dtype=xdt, device=dev)
     mean = torch.empty((Cout,), dtype=torch.float32, device=dev)
     var = torch.empty((Cout,), dtype=torch.float32, device=dev)
-    if bf16:
-        ws = torch.empty((lib.sonet_pointmlp_bf16_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
-        try:
-            with _lib.on_device(dev), _timed("pointmlpbf16_stats_%dx%d_L%d%s" % (C1 + C2, Cout, L, "_xaff" if xaff is not None else "")):
-                if xaff is not None:
-                    check(lib.sonet_pointmlp_bf16_stats_xaff(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L,
-                                                             ptr(ws), ptr(mean), ptr(var), *_xaff_args(xaff, C1, C2, dev), stream_ptr()),
-                          "sonet_pointmlp_bf16_stats_xaff")
-                else:
-                    check(lib.sonet_pointmlp_bf16_stats(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L,
-                                                        ptr(ws), ptr(mean), ptr(var), stream_ptr()), "sonet_pointmlp_bf16_stats")
-        finally:
-            _rider_done()
-        return y, mean, var
-    ws = torch.empty((lib.sonet_pointmlp_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
-    name = "pointmlp%s_stats_%dx%d_L%d" % ("h3" if h3 else "x3", C1 + C2, Cout, L)
+    ws = _ws(lib.sonet_pointmlp_bf16_stats_ws_size if bf16 else lib.sonet_pointmlp_stats_ws_size, dev, B, Cout, L)
+    args = (ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L, ptr(ws), ptr(mean), ptr(var))
+    name = "pointmlp%s_stats_%dx%d_L%d" % ("bf16" if bf16 else "h3" if h3 else "x3", C1 + C2, Cout, L)
     if h3:
         _range_arm(name)
-    fn = lib.sonet_pointmlp_h3_stats_f32 if h3 else lib.sonet_pointmlp_x3_stats_f32
-    try:
-        with _lib.on_device(dev), _timed(name + ("_xaff" if xaff is not None else "")):
-            if xaff is not None:
-                if not h3:
-                    raise SonetHipError("pointmlp_stats: normalise-on-load needs an h3 pack")
-                check(lib.sonet_pointmlp_h3_stats_xaff_f32(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L,
-                                                           ptr(ws), ptr(mean), ptr(var), *_xaff_args(xaff, C1, C2, dev), stream_ptr()),
-                      "sonet_pointmlp_h3_stats_xaff_f32")
-            else:
-                check(fn(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cout, L, ptr(ws), ptr(mean), ptr(var),
-                         stream_ptr()), "sonet_pointmlp_stats")
-    finally:
-        _rider_done()
+    if xaff is not None:
+        if not (h3 or bf16):
+            raise SonetHipError("pointmlp_stats: normalise-on-load needs an h3 pack")
+        _launch(dev, name + "_xaff", lib.sonet_pointmlp_bf16_stats_xaff if bf16 else lib.sonet_pointmlp_h3_stats_xaff_f32, *args,
+                *_xaff_args(xaff, C1, C2, dev))
+    elif bf16:
+        _launch(dev, name, lib.sonet_pointmlp_bf16_stats, *args)
+    else:
+        _launch(dev, name, lib.sonet_pointmlp_h3_stats_f32 if h3 else lib.sonet_pointmlp_x3_stats_f32, *args, what="sonet_pointmlp_stats")
     return y, mean, var
 
 
@@ -1761,36 +1676,25 @@ def pointmlp_nodeadd_stats(x1, wp, bias, Cout, z, zidx, x2=None):
     in one launch: the TRAINING forward of a BatchNorm layer whose per-node and per-cloud input channels were multiplied once per node
     (z B x Cout x M f32, zidx B x L i32, out of range: + 0) -- ``pointmlp_nodeadd`` with the epilogue of ``pointmlp_stats``.  h3 packs
     only; consumes an armed ``bn_rider``.  -> (raw, mean, var)."""
-    try:
-        if not isinstance(wp, torch.Tensor) or wp.dtype != torch.int8:
-            raise SonetHipError("pointmlp_nodeadd_stats: an h3 pack")
-        _chk(x1, "x", torch.float32, 3)
-        _chk(z, "z", torch.float32, 3)
-        _chk(zidx, "zidx", torch.int32, 2)
-        B, C1, L = x1.shape
-        C2 = 0
-        if x2 is not None:
-            _chk(x2, "x2", torch.float32, 3)
-            if x2.shape[0] != B or x2.shape[2] != L:
-                raise SonetHipError("x2 must be B x C2 x L")
-            C2 = x2.shape[1]
-        _chk_cvec(Cout, bias=bias)
-        dev = _same_device(x1, x2, wp, bias, z, zidx)
-        lib = _lib.load()
-        if wp.numel() != lib.sonet_pointmlp_x3_pack_size(C1 + C2, Cout) or tuple(z.shape[:2]) != (B, Cout) or tuple(zidx.shape) != (B, L):
-            raise SonetHipError("pointmlp_nodeadd_stats: pack for Cin=%d Cout=%d, z B x Cout x M, zidx B x L" % (C1 + C2, Cout))
-        raw = torch.empty((B, Cout, L), dtype=torch.float32, device=dev)
-        mean = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        var = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.sonet_pointmlp_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
-        name = "pointmlph3_nodeadd_stats_%dx%d_L%d" % (C1 + C2, Cout, L)
-        _range_arm(name)
-        with _lib.on_device(dev), _timed(name):
-            check(lib.sonet_pointmlp_h3_nodeadd_stats_f32(ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(const_vec(Cout, 1.0, dev)), ptr(bias), 0, ptr(raw),
-                                                          B, Cout, L, ptr(z), ptr(zidx), z.shape[2], ptr(ws), ptr(mean), ptr(var), stream_ptr()),
-                  "sonet_pointmlp_h3_nodeadd_stats_f32")
-    finally:
-        _rider_done()
+    if not isinstance(wp, torch.Tensor) or wp.dtype != torch.int8:
+        raise SonetHipError("pointmlp_nodeadd_stats: an h3 pack")
+    _chk(x1, "x", torch.float32, 3)
+    _chk(z, "z", torch.float32, 3)
+    _chk(zidx, "zidx", torch.int32, 2)
+    B, C1, C2, L = _layer_inputs(x1, x2, torch.float32)
+    _chk_cvec(Cout, bias=bias)
+    dev = _same_device(x1, x2, wp, bias, z, zidx)
+    lib = _lib.load()
+    if wp.numel() != _pack_bytes(lib, "h3", C1 + C2, Cout) or tuple(z.shape[:2]) != (B, Cout) or tuple(zidx.shape) != (B, L):
+        raise SonetHipError("pointmlp_nodeadd_stats: pack for Cin=%d Cout=%d, z B x Cout x M, zidx B x L" % (C1 + C2, Cout))
+    raw = torch.empty((B, Cout, L), dtype=torch.float32, device=dev)
+    mean = torch.empty((Cout,), dtype=torch.float32, device=dev)
+    var = torch.empty((Cout,), dtype=torch.float32, device=dev)
+    ws = _ws(lib.sonet_pointmlp_stats_ws_size, dev, B, Cout, L)
+    name = "pointmlph3_nodeadd_stats_%dx%d_L%d" % (C1 + C2, Cout, L)
+    _range_arm(name)
+    _launch(dev, name, lib.sonet_pointmlp_h3_nodeadd_stats_f32, ptr(x1), C1, ptr(x2), C2, ptr(wp), ptr(const_vec(Cout, 1.0, dev)), ptr(bias), 0, ptr(raw),
+            B, Cout, L, ptr(z), ptr(zidx), z.shape[2], ptr(ws), ptr(mean), ptr(var))
     return raw, mean, var
 
 
@@ -1836,17 +1740,14 @@ def p16_from_f32(x, scale=None, shift=None, relu=False):
         _chk(shift, "shift", torch.float32, 1)
     name = "p16_from_f32_%d_L%d" % (C, L)
     _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        check(_lib.load().sonet_p16_from_f32(ptr(x), ptr(out.data), B, C, L, ptr(scale), ptr(shift), int(bool(relu)), stream_ptr()),
-              "sonet_p16_from_f32")
+    _launch(dev, name, _lib.load().sonet_p16_from_f32, ptr(x), ptr(out.data), B, C, L, ptr(scale), ptr(shift), int(bool(relu)))
     return out
 
 
 def p16_to_f32(p):
     x = torch.empty((p.B, p.C, p.L), dtype=torch.float32, device=p.device)
     if x.numel():
-        with _lib.on_device(p.device), _timed("p16_to_f32"):
-            check(_lib.load().sonet_p16_to_f32(ptr(p.data), ptr(x), p.B, p.C, p.L, stream_ptr()), "sonet_p16_to_f32")
+        _launch(p.device, "p16_to_f32", _lib.load().sonet_p16_to_f32, ptr(p.data), ptr(x), p.B, p.C, p.L)
     return x
 
 
@@ -1856,9 +1757,8 @@ def pointmlp_h3p_pack(weight2d):
     dev = _same_device(weight2d)
     Cout, Cin = weight2d.shape
     lib = _lib.load()
-    with _lib.on_device(dev):
-        wp = torch.empty((lib.sonet_pointmlp_h3p_pack_size(Cin, Cout) // 4,), dtype=torch.int32, device=dev)
-        check(lib.sonet_pointmlp_h3p_pack(ptr(weight2d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_pointmlp_h3p_pack")
+    wp = _pack_empty(lib, "h3p", Cin, Cout, dev)
+    _launch(dev, None, lib.sonet_pointmlp_h3p_pack, ptr(weight2d), ptr(wp), Cin, Cout)
     return wp
 
 
@@ -1878,15 +1778,10 @@ def pointmlp_h3p(x1, wp, scale, shift, relu, Cout, x2=None, out="f32", gidx=None
         if gidx.shape[0] != B:
             raise SonetHipError("pointmlp_h3p: gidx must have B rows")
         L = gidx.shape[1]
-    C2 = 0
-    if x2 is not None:
-        if x2.B != B or x2.L != L:
-            raise SonetHipError("x2 must be B x C2 x L")
-        C2 = x2.C
-        if C1 % 16 != 0:
-            raise SonetHipError("pointmlp_h3p: with a second input C1 must be a multiple of 16")
-    _chk(scale, "scale", torch.float32, 1)
-    _chk(shift, "shift", torch.float32, 1)
+    _, _, C2, _ = _layer_inputs(x1, x2, None, L)
+    if x2 is not None and C1 % 16 != 0:
+        raise SonetHipError("pointmlp_h3p: with a second input C1 must be a multiple of 16")
+    _chk_cvec(Cout, 1, scale=scale, shift=shift)
     if (z is None) != (zidx is None):
         raise SonetHipError("pointmlp_h3p: z and zidx come together")
     ZM = 0
@@ -1902,23 +1797,19 @@ def pointmlp_h3p(x1, wp, scale, shift, relu, Cout, x2=None, out="f32", gidx=None
     lib = _lib.load()
     # the pack's K range is the concatenation of the inputs' 16-channel chunks
     cin_pack = (C1 + C2) if C2 else C1
-    if wp.numel() * 4 != lib.sonet_pointmlp_h3p_pack_size(cin_pack, Cout):
-        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
-                            % (wp.numel() * 4, lib.sonet_pointmlp_h3p_pack_size(cin_pack, Cout), cin_pack, Cout))
+    _chk_pack(lib, wp, "h3p", cin_pack, Cout, "bytes")
     y = torch.empty((B, Cout, L), dtype=torch.float32, device=dev) if out in ("f32", "both") else None
     yp = p16_empty(B, Cout, L, dev) if out in ("p16", "both") else None
     mean = var = ws = None
     if stats:
         mean = torch.empty((Cout,), dtype=torch.float32, device=dev)
         var = torch.empty((Cout,), dtype=torch.float32, device=dev)
-        ws = torch.empty((lib.sonet_pointmlp_h3p_stats_ws_size(B, Cout, L),), dtype=torch.uint8, device=dev)
+        ws = _ws(lib.sonet_pointmlp_h3p_stats_ws_size, dev, B, Cout, L)
     if B * L * Cout != 0:
         name = "pointmlph3p%s_%dx%d_L%d" % ("_nodeadd" if z is not None else "_stats" if stats else ("_" + tag) if tag else "", C1 + C2, Cout, L)
         _range_arm(name)
-        with _lib.on_device(dev), _timed(name):
-            check(lib.sonet_pointmlp_h3p(ptr(x1.data), C1, L1, ptr(gidx), ptr(x2.data) if x2 is not None else None, C2, ptr(wp), ptr(scale), ptr(shift),
-                                         int(bool(relu)), ptr(y), ptr(yp.data) if yp is not None else None, B, Cout, L, ptr(z), ptr(zidx), ZM,
-                                         ptr(ws), ptr(mean), ptr(var), stream_ptr()), "sonet_pointmlp_h3p")
+        _launch(dev, name, lib.sonet_pointmlp_h3p, ptr(x1.data), C1, L1, ptr(gidx), ptr(x2.data) if x2 is not None else None, C2, ptr(wp), ptr(scale),
+                ptr(shift), int(bool(relu)), ptr(y), ptr(yp.data) if yp is not None else None, B, Cout, L, ptr(z), ptr(zidx), ZM, ptr(ws), ptr(mean), ptr(var))
     if stats:
         return y, mean, var
     return y if out == "f32" else yp if out == "p16" else (y, yp)
@@ -1952,22 +1843,17 @@ def pointmlp_h3p_gmax(x1, wp, scale, shift, relu, Cout, GK, G, ngout, x2=None, o
         raise SonetHipError("pointmlp_h3p_gmax: out is 'p16' or 'f32'")
     C1, L = x1.C, x1.L
     C2 = x2.C if x2 is not None else 0
-    _chk(scale, "scale", torch.float32, 1)
-    _chk(shift, "shift", torch.float32, 1)
+    _chk_cvec(Cout, 1, scale=scale, shift=shift)
     dev = _same_device(x1.data, x2.data if x2 is not None else None, wp, scale, shift)
     lib = _lib.load()
-    if wp.numel() * 4 != lib.sonet_pointmlp_h3p_pack_size(C1 + C2, Cout):
-        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
-                            % (wp.numel() * 4, lib.sonet_pointmlp_h3p_pack_size(C1 + C2, Cout), C1 + C2, Cout))
+    _chk_pack(lib, wp, "h3p", C1 + C2, Cout, "bytes")
     Lout = int(ngout if Lout is None else Lout)
     y = torch.empty((ngout, Cout), dtype=torch.float32, device=dev) if out == "f32" else None
     yp = p16_flat(Cout, Lout, ngout, dev) if out == "p16" else None
     name = "pointmlph3p_gmax%d_%dx%d_L%d" % (GK, C1 + C2, Cout, int(ngout) * int(GK))      # (the columns that count: without the blocks' padding)
     _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        check(lib.sonet_pointmlp_h3p_gmax(ptr(x1.data), C1, ptr(x2.data) if x2 is not None else None, C2, ptr(wp), ptr(scale), ptr(shift),
-                                          int(bool(relu)), Cout, L, int(GK), int(G), int(ngout), Lout, ptr(y), ptr(yp.data) if yp is not None else None,
-                                          stream_ptr()), "sonet_pointmlp_h3p_gmax")
+    _launch(dev, name, lib.sonet_pointmlp_h3p_gmax, ptr(x1.data), C1, ptr(x2.data) if x2 is not None else None, C2, ptr(wp), ptr(scale), ptr(shift),
+            int(bool(relu)), Cout, L, int(GK), int(G), int(ngout), Lout, ptr(y), ptr(yp.data) if yp is not None else None)
     return y if out == "f32" else yp
 
 
@@ -1989,9 +1875,8 @@ def knn_stage_prepare(coord, knn_I, K, center_avg):
     cp = p16_flat(3, Lm, B * M, dev)
     rec = torch.empty((Lp, 4), dtype=torch.int32, device=dev)
     _range_arm("knn_stage_prepare")
-    with _lib.on_device(dev), _timed("knn_stage_prepare"):
-        check(lib.sonet_knn_stage_prepare_f32(ptr(coord), ptr(knn_I), KI, int(bool(center_avg)), B, M, int(K), ptr(center), ptr(cp.data), ptr(rec),
-                                              stream_ptr()), "sonet_knn_stage_prepare_f32")
+    _launch(dev, "knn_stage_prepare", lib.sonet_knn_stage_prepare_f32, ptr(coord), ptr(knn_I), KI, int(bool(center_avg)), B, M, int(K), ptr(center),
+            ptr(cp.data), ptr(rec))
     return dict(center=center, center_p16=cp, rec=rec, B=B, M=M, K=int(K), G=min(16, 128 // int(K)), Lp=Lp)
 
 
@@ -2010,9 +1895,8 @@ def knn_stage_input(prep, z, wl, scale, shift, relu):
     h1 = p16_empty(1, C, prep["Lp"], dev)            # (every column is written: pad columns as zeros)
     name = "knn_stage_input_%dx%d" % (C, prep["B"] * prep["M"] * prep["K"])
     _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        check(_lib.load().sonet_knn_stage_input_p16(ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(scale), ptr(shift), int(bool(relu)),
-                                                    prep["B"], prep["M"], prep["K"], C, ptr(h1.data), stream_ptr()), "sonet_knn_stage_input_p16")
+    _launch(dev, name, _lib.load().sonet_knn_stage_input_p16, ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(scale), ptr(shift), int(bool(relu)), prep["B"],
+            prep["M"], prep["K"], C, ptr(h1.data))
     return h1
 
 
@@ -2050,18 +1934,14 @@ def knn_layer2_gmax(prep, z, wl, s1, t1, relu1, wp, s2, t2, relu2, Cout, Lout):
         raise SonetHipError("knn_layer2_gmax: wl C x 3, s1 / t1 C, s2 / t2 Cout")
     dev = _same_device(prep["rec"], z.data, wl, s1, t1, wp, s2, t2)
     lib = _lib.load()
-    if wp.numel() * 4 != lib.sonet_pointmlp_h3p_pack_size(C, Cout):
-        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
-                            % (wp.numel() * 4, lib.sonet_pointmlp_h3p_pack_size(C, Cout), C, Cout))
+    _chk_pack(lib, wp, "h3p", C, Cout, "bytes")
     B, M, K, G = prep["B"], prep["M"], prep["K"], prep["G"]
     ngout, Lout = B * M, int(Lout)
     yp = p16_flat(Cout, Lout, ngout, dev)
     name = "pointmlph3p_knn_gmax%d_%dx%d_L%d" % (K, C, Cout, ngout * K)
     _range_arm(name)
-    with _lib.on_device(dev), _timed(name):
-        check(lib.sonet_knn_layer2_gmax_p16(ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(s1), ptr(t1), int(bool(relu1)), B, M, K, C,
-                                            ptr(wp), ptr(s2), ptr(t2), int(bool(relu2)), int(Cout), K, G, ngout, Lout, ptr(yp.data),
-                                            stream_ptr()), "sonet_knn_layer2_gmax_p16")
+    _launch(dev, name, lib.sonet_knn_layer2_gmax_p16, ptr(prep["rec"]), ptr(z.data), ptr(wl), ptr(s1), ptr(t1), int(bool(relu1)), B, M, K, C, ptr(wp), ptr(s2),
+            ptr(t2), int(bool(relu2)), int(Cout), K, G, ngout, Lout, ptr(yp.data))
     return yp
 
 
@@ -2070,34 +1950,41 @@ def p16_flat_to_bcm(p, B, M):
     if p.B != 1 or p.L != node_stage_columns(B, M):
         raise SonetHipError("p16_flat_to_bcm: a 1 x C x (B M) activation")
     x = torch.empty((B, p.C, M), dtype=torch.float32, device=p.device)
-    with _lib.on_device(p.device), _timed("p16_flat_to_bcm"):
-        check(_lib.load().sonet_p16_flat_to_bcm_f32(ptr(p.data), ptr(x), B, p.C, M, stream_ptr()), "sonet_p16_flat_to_bcm_f32")
+    _launch(p.device, "p16_flat_to_bcm", _lib.load().sonet_p16_flat_to_bcm_f32, ptr(p.data), ptr(x), B, p.C, M)
     return x
+
+
+def _pointresnet_pack(ws, who, size_fn, fn):
+    for i, w in enumerate(ws):
+        _chk(w, "w%d" % (i + 1), torch.float32, 2)
+    w1, w2, w3, w4 = ws
+    if (w1.shape[0], tuple(w2.shape), tuple(w3.shape), tuple(w4.shape)) != (64, (128, 64), (256, 128), (384, 320)) or w1.shape[1] > 16:
+        raise SonetHipError("%s supports Cin0<=16 -> 64 -> 128 -> 256 -> [320] -> 384 only" % who)
+    dev = _same_device(w1, w2, w3, w4)
+    stream = _ws(size_fn, dev)
+    _launch(dev, None, fn, ptr(w1), ptr(w2), ptr(w3), ptr(w4), w1.shape[1], ptr(stream))
+    return stream
 
 
 def pointresnet_pack(w1, w2, w3, w4):
     """Pack the four [Cout][Cin] f32 weights of the first PointNet into the fused kernel's weight stream."""
-    for i, w in enumerate((w1, w2, w3, w4)):
-        _chk(w, "w%d" % (i + 1), torch.float32, 2)
-    if (w1.shape[0], tuple(w2.shape), tuple(w3.shape), tuple(w4.shape)) != (64, (128, 64), (256, 128), (384, 320)) or w1.shape[1] > 16:
-        raise SonetHipError("pointresnet_fused supports Cin0<=16 -> 64 -> 128 -> 256 -> [320] -> 384 only")
-    dev = _same_device(w1, w2, w3, w4)
     lib = _lib.load()
-    ws = torch.empty((lib.sonet_pointresnet_pack_size(),), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        check(lib.sonet_pointresnet_pack(ptr(w1), ptr(w2), ptr(w3), ptr(w4), w1.shape[1], ptr(ws), stream_ptr()),
-              "sonet_pointresnet_pack")
-    return ws
+    return _pointresnet_pack((w1, w2, w3, w4), "pointresnet_fused", lib.sonet_pointresnet_pack_size, lib.sonet_pointresnet_pack)
+
+
+def _chk_pointresnet(x, name, wstream, size_fn, affine):
+    """The operands of a fused first PointNet: the weight stream of ``size_fn()`` bytes, the f32 points and the folded 832 x 2 affine."""
+    _chk_member(wstream, "wstream", torch.uint8, (size_fn(),))
+    _chk(x, name, torch.float32, 3)
+    _chk(affine, "affine", torch.float32, 2)
+    if tuple(affine.shape) != (832, 2):
+        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
 
 
 def pointresnet_fused(x, wstream, affine, want_p16=False):
     """x B x Cin0 x L f32 -> B x 384 x L f32 (whole first PointNet, eval BN folded into ``affine`` 832 x 2).
     want_p16: -> (y, P16 planes of y), written by the same launch (the operand format of ``pointmlp_h3p``)."""
-    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_pack_size(),))
-    _chk(x, "x", torch.float32, 3)
-    _chk(affine, "affine", torch.float32, 2)
-    if tuple(affine.shape) != (832, 2):
-        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
+    _chk_pointresnet(x, "x", wstream, _lib.load().sonet_pointresnet_pack_size, affine)
     dev = _same_device(x, wstream, affine)
     B, Cin0, L = x.shape
     only = want_p16 == "only"                   # -> (None, planes): y is never written in f32 (P16.float() decodes the planes)
@@ -2106,13 +1993,11 @@ def pointresnet_fused(x, wstream, affine, want_p16=False):
     if B * L == 0:
         return (y, yp) if want_p16 else y
     _range_arm("pointresnet_fused_L%d" % L)
-    with _lib.on_device(dev), _timed("pointresnet_fused%s_L%d" % ("_p16only" if only else "_p16" if want_p16 else "", L)):
-        if want_p16:
-            check(_lib.load().sonet_pointresnet_fused_p16_f32(ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), ptr(yp.data), B, L, stream_ptr()),
-                  "sonet_pointresnet_fused_p16_f32")
-        else:
-            check(_lib.load().sonet_pointresnet_fused_f32(ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), B, L, stream_ptr()),
-                  "sonet_pointresnet_fused_f32")
+    name = "pointresnet_fused%s_L%d" % ("_p16only" if only else "_p16" if want_p16 else "", L)
+    if want_p16:
+        _launch(dev, name, _lib.load().sonet_pointresnet_fused_p16_f32, ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), ptr(yp.data), B, L)
+    else:
+        _launch(dev, name, _lib.load().sonet_pointresnet_fused_f32, ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), B, L)
     return (y, yp) if want_p16 else y
 
 
@@ -2121,60 +2006,37 @@ def pointresnet_fused_pool(sg, wstream, affine, M, want_p16=False):
     -> B x 384 x M f32.  want_p16: -> (that, ``P16`` 1 x 384 x Lm): the same map pre-split on the flat column axis of the node-level stage."""
     x_sorted = sg["x_aug_sorted"]
     _chk_sort_group(sg, M)
-    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_pack_size(),))
-    _chk(x_sorted, "x_sorted", torch.float32, 3)
-    _chk(affine, "affine", torch.float32, 2)
-    if tuple(affine.shape) != (832, 2):
-        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
+    _chk_pointresnet(x_sorted, "x_sorted", wstream, _lib.load().sonet_pointresnet_pack_size, affine)
     dev = _same_device(x_sorted, wstream, affine, sg["ids_sorted"], sg["pos0"], sg["node_off"], sg["count"])
     B, Cin0, L = x_sorted.shape
     lib = _lib.load()
-    ws = torch.empty((lib.sonet_pointresnet_pool_ws_size(B, L, int(M)),), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.sonet_pointresnet_pool_ws_size, dev, B, L, int(M))
     out = torch.empty((B, 384, int(M)), dtype=torch.float32, device=dev)
     outp = p16_flat(384, node_stage_columns(B, int(M)), B * int(M), dev) if want_p16 else None
     _range_arm("pointresnet_fused_pool_L%d" % L)
-    with _lib.on_device(dev), _timed("pointresnet_fused_pool_L%d" % L):
-        if want_p16:
-            check(lib.sonet_pointresnet_fused_pool_p16_f32(ptr(x_sorted), Cin0, ptr(wstream), ptr(affine), ptr(sg["ids_sorted"]), ptr(sg["pos0"]),
-                                                           ptr(sg["node_off"]), ptr(sg["count"]), ptr(ws), ptr(out), ptr(outp.data), B, L, int(M),
-                                                           stream_ptr()), "sonet_pointresnet_fused_pool_p16_f32")
-        else:
-            check(lib.sonet_pointresnet_fused_pool_f32(ptr(x_sorted), Cin0, ptr(wstream), ptr(affine), ptr(sg["ids_sorted"]), ptr(sg["pos0"]),
-                                                       ptr(sg["node_off"]), ptr(sg["count"]), ptr(ws), ptr(out), B, L, int(M), stream_ptr()),
-                  "sonet_pointresnet_fused_pool_f32")
+    args = (ptr(x_sorted), Cin0, ptr(wstream), ptr(affine), ptr(sg["ids_sorted"]), ptr(sg["pos0"]), ptr(sg["node_off"]), ptr(sg["count"]), ptr(ws), ptr(out))
+    if want_p16:
+        _launch(dev, "pointresnet_fused_pool_L%d" % L, lib.sonet_pointresnet_fused_pool_p16_f32, *args, ptr(outp.data), B, L, int(M))
+    else:
+        _launch(dev, "pointresnet_fused_pool_L%d" % L, lib.sonet_pointresnet_fused_pool_f32, *args, B, L, int(M))
     return (out, outp) if want_p16 else out
 
 
 def pointresnet_bf16_pack(w1, w2, w3, w4):
     """Weight stream of the fused bf16 first PointNet (``sonet_pointresnet_bf16_pack``)."""
-    for i, w in enumerate((w1, w2, w3, w4)):
-        _chk(w, "w%d" % (i + 1), torch.float32, 2)
-    if (w1.shape[0], tuple(w2.shape), tuple(w3.shape), tuple(w4.shape)) != (64, (128, 64), (256, 128), (384, 320)) or w1.shape[1] > 16:
-        raise SonetHipError("pointresnet_bf16 supports Cin0<=16 -> 64 -> 128 -> 256 -> [320] -> 384 only")
-    dev = _same_device(w1, w2, w3, w4)
     lib = _lib.load()
-    ws = torch.empty((lib.sonet_pointresnet_bf16_pack_size(),), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        check(lib.sonet_pointresnet_bf16_pack(ptr(w1), ptr(w2), ptr(w3), ptr(w4), w1.shape[1], ptr(ws), stream_ptr()),
-              "sonet_pointresnet_bf16_pack")
-    return ws
+    return _pointresnet_pack((w1, w2, w3, w4), "pointresnet_bf16", lib.sonet_pointresnet_bf16_pack_size, lib.sonet_pointresnet_bf16_pack)
 
 
 def pointresnet_bf16(x, wstream, affine):
     """x B x Cin0 x L f32 -> B x 384 x L bfloat16: whole first PointNet in bf16 (eval BN folded into ``affine`` 832 x 2)."""
-    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_bf16_pack_size(),))
-    _chk(x, "x", torch.float32, 3)
-    _chk(affine, "affine", torch.float32, 2)
-    if tuple(affine.shape) != (832, 2):
-        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
+    _chk_pointresnet(x, "x", wstream, _lib.load().sonet_pointresnet_bf16_pack_size, affine)
     dev = _same_device(x, wstream, affine)
     B, Cin0, L = x.shape
     y = torch.empty((B, 384, L), dtype=torch.bfloat16, device=dev)
     if y.numel() == 0:
         return y
-    with _lib.on_device(dev), _timed("pointresnet_bf16_L%d" % L):
-        check(_lib.load().sonet_pointresnet_bf16(ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), B, L, stream_ptr()),
-              "sonet_pointresnet_bf16")
+    _launch(dev, "pointresnet_bf16_L%d" % L, _lib.load().sonet_pointresnet_bf16, ptr(x), Cin0, ptr(wstream), ptr(affine), ptr(y), B, L)
     return y
 
 
@@ -2183,20 +2045,14 @@ def pointresnet_bf16_pool(sg, wstream, affine, M):
     -> B x 384 x M f32 holding bf16-representable values (the maxima of the bf16 features the store variant writes)."""
     x_sorted = sg["x_aug_sorted"]
     _chk_sort_group(sg, M)
-    _chk_member(wstream, "wstream", torch.uint8, (_lib.load().sonet_pointresnet_bf16_pack_size(),))
-    _chk(x_sorted, "x_sorted", torch.float32, 3)
-    _chk(affine, "affine", torch.float32, 2)
-    if tuple(affine.shape) != (832, 2):
-        raise SonetHipError("affine must be 832 x 2 (scale, shift)")
+    _chk_pointresnet(x_sorted, "x_sorted", wstream, _lib.load().sonet_pointresnet_bf16_pack_size, affine)
     dev = _same_device(x_sorted, wstream, affine, sg["ids_sorted"], sg["pos0"], sg["node_off"], sg["count"])
     B, Cin0, L = x_sorted.shape
     lib = _lib.load()
-    ws = torch.empty((lib.sonet_pointresnet_bf16_pool_ws_size(B, L, int(M)),), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.sonet_pointresnet_bf16_pool_ws_size, dev, B, L, int(M))
     out = torch.empty((B, 384, int(M)), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("pointresnet_bf16_pool_L%d" % L):
-        check(lib.sonet_pointresnet_bf16_pool(ptr(x_sorted), Cin0, ptr(wstream), ptr(affine), ptr(sg["ids_sorted"]), ptr(sg["pos0"]),
-                                              ptr(sg["node_off"]), ptr(sg["count"]), ptr(ws), ptr(out), B, L, int(M), stream_ptr()),
-              "sonet_pointresnet_bf16_pool")
+    _launch(dev, "pointresnet_bf16_pool_L%d" % L, lib.sonet_pointresnet_bf16_pool, ptr(x_sorted), Cin0, ptr(wstream), ptr(affine), ptr(sg["ids_sorted"]),
+            ptr(sg["pos0"]), ptr(sg["node_off"]), ptr(sg["count"]), ptr(ws), ptr(out), B, L, int(M))
     return out
 
 
@@ -2212,12 +2068,9 @@ def channel_stats(y):
     mean = torch.empty((C,), dtype=torch.float32, device=dev)
     var = torch.empty((C,), dtype=torch.float32, device=dev)
     lib = _lib.load()
-    fn = lib.sonet_channel_stats_f32 if y.dtype == torch.float32 else lib.sonet_channel_stats_bf16
-    try:
-        with _lib.on_device(dev), _timed("channel_stats" if y.dtype == torch.float32 else "channel_stats_bf16"):
-            check(fn(ptr(y), B, C, L, ptr(ws), ptr(mean), ptr(var), stream_ptr()), "sonet_channel_stats")
-    finally:
-        _rider_done()
+    fn = _by_dtype(lib, "sonet_channel_stats", y)
+    _launch(dev, "channel_stats" if y.dtype == torch.float32 else "channel_stats_bf16", fn, ptr(y), B, C, L, ptr(ws), ptr(mean), ptr(var),
+            what="sonet_channel_stats")
     return mean, var
 
 
@@ -2226,9 +2079,7 @@ def channel_affine_act_(y, scale, shift, relu):
     B, C, L = y.shape
     _chk_cvec(C, scale=scale, shift=shift)
     dev = _same_device(y, scale, shift)
-    with _lib.on_device(dev), _timed("channel_affine_act"):
-        check(_lib.load().sonet_channel_affine_act_f32(ptr(y), ptr(scale), ptr(shift), int(bool(relu)), B, C, L, stream_ptr()),
-              "sonet_channel_affine_act_f32")
+    _launch(dev, "channel_affine_act", _lib.load().sonet_channel_affine_act_f32, ptr(y), ptr(scale), ptr(shift), int(bool(relu)), B, C, L)
     return y
 
 
@@ -2241,9 +2092,9 @@ def channel_affine_act(x, scale, shift, relu):
     dev = _same_device(x, scale, shift)
     y = torch.empty_like(x)
     lib = _lib.load()
-    fn = lib.sonet_channel_affine_act_out_f32 if x.dtype == torch.float32 else lib.sonet_channel_affine_act_out_bf16
-    with _lib.on_device(dev), _timed("channel_affine_act" if x.dtype == torch.float32 else "channel_affine_act_bf16"):
-        check(fn(ptr(x), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, C, L, stream_ptr()), "sonet_channel_affine_act_out")
+    fn = _by_dtype(lib, "sonet_channel_affine_act_out", x)
+    _launch(dev, "channel_affine_act" if x.dtype == torch.float32 else "channel_affine_act_bf16", fn, ptr(x), ptr(scale), ptr(shift), int(bool(relu)), ptr(y),
+            B, C, L, what="sonet_channel_affine_act_out")
     return y
 
 
@@ -2256,8 +2107,7 @@ def chunk_mean(h, k):
         raise SonetHipError("chunk_mean: k in {1, 2, 3} and a length divisible by k")
     dev = _same_device(h)
     out = torch.empty((B, C, L // k), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("chunk_mean"):
-        check(_lib.load().sonet_chunk_mean_f32(ptr(h), ptr(out), B * C, L // k, int(k), stream_ptr()), "sonet_chunk_mean_f32")
+    _launch(dev, "chunk_mean", _lib.load().sonet_chunk_mean_f32, ptr(h), ptr(out), B * C, L // k, int(k))
     return out
 
 
@@ -2311,9 +2161,8 @@ def bn_fwd_coeffs(mean, var, gamma, beta, eps):
     _chk_cvec(C, mean=mean, var=var, gamma=gamma, beta=beta)
     dev = _same_device(mean, var, gamma, beta)
     out = torch.empty((3, C), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        check(_lib.load().sonet_bn_fwd_coeffs_f32(ptr(mean), ptr(var), ptr(gamma.detach().contiguous()), ptr(beta.detach().contiguous()),
-                                                  float(eps), C, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()), "sonet_bn_fwd_coeffs_f32")
+    _launch(dev, None, _lib.load().sonet_bn_fwd_coeffs_f32, ptr(mean), ptr(var), ptr(gamma.detach().contiguous()), ptr(beta.detach().contiguous()), float(eps),
+            C, ptr(out[0]), ptr(out[1]), ptr(out[2]))
     return out[0], out[1], out[2]
 
 
@@ -2327,10 +2176,8 @@ def bn_bwd_coeffs(sums, mean, invstd, gamma, n):
         raise SonetHipError("sums must hold 2 C = %d elements, got %d" % (2 * C, sums.numel()))
     dev = _same_device(sums, mean, invstd, gamma)
     out = torch.empty((5, C), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        check(_lib.load().sonet_bn_bwd_coeffs_f32(ptr(sums), ptr(mean), ptr(invstd), ptr(gamma.detach().contiguous()), float(n), C,
-                                                  ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]), stream_ptr()),
-              "sonet_bn_bwd_coeffs_f32")
+    _launch(dev, None, _lib.load().sonet_bn_bwd_coeffs_f32, ptr(sums), ptr(mean), ptr(invstd), ptr(gamma.detach().contiguous()), float(n), C, ptr(out[0]),
+            ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]))
     return out[0], out[1], out[2], out[3], out[4]
 
 
@@ -2346,9 +2193,9 @@ def pointwise_bwd_stats(gy, raw, scale, shift, relu, want_sums=False):
     dev = _same_device(gy, raw, scale, shift)
     sums = torch.empty((2 * C,), dtype=torch.float64, device=dev)
     lib = _lib.load()
-    fn = lib.sonet_pointwise_bwd_stats_f32 if gy.dtype == torch.float32 else lib.sonet_pointwise_bwd_stats_bf16
-    with _lib.on_device(dev), _timed("pointwise_bwd_stats" if gy.dtype == torch.float32 else "pointwise_bwd_stats_bf16"):
-        check(fn(ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), B, C, L, ptr(sums), stream_ptr()), "sonet_pointwise_bwd_stats")
+    fn = _by_dtype(lib, "sonet_pointwise_bwd_stats", gy)
+    _launch(dev, "pointwise_bwd_stats" if gy.dtype == torch.float32 else "pointwise_bwd_stats_bf16", fn, ptr(gy), ptr(raw), ptr(scale), ptr(shift),
+            int(bool(relu)), B, C, L, ptr(sums), what="sonet_pointwise_bwd_stats")
     if want_sums:
         return sums
     return sums[:C], sums[C:]
@@ -2366,10 +2213,9 @@ def pointwise_bwd_apply(gy, raw, scale, shift, relu, a, b, c0):
     dev = _same_device(gy, raw, scale, shift, a, b, c0)
     out = torch.empty_like(gy)
     lib = _lib.load()
-    fn = lib.sonet_pointwise_bwd_apply_f32 if gy.dtype == torch.float32 else lib.sonet_pointwise_bwd_apply_bf16
-    with _lib.on_device(dev), _timed("pointwise_bwd_apply" if gy.dtype == torch.float32 else "pointwise_bwd_apply_bf16"):
-        check(fn(ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), ptr(a), ptr(b), ptr(c0), ptr(out), B, C, L, stream_ptr()),
-              "sonet_pointwise_bwd_apply")
+    fn = _by_dtype(lib, "sonet_pointwise_bwd_apply", gy)
+    _launch(dev, "pointwise_bwd_apply" if gy.dtype == torch.float32 else "pointwise_bwd_apply_bf16", fn, ptr(gy), ptr(raw), ptr(scale), ptr(shift),
+            int(bool(relu)), ptr(a), ptr(b), ptr(c0), ptr(out), B, C, L, what="sonet_pointwise_bwd_apply")
     return out
 
 
@@ -2402,16 +2248,14 @@ def pointwise_bwd_apply_nodesum(gy, raw, scale, shift, relu, a, b, c0, ids, M):
     lib = _lib.load()
     g_raw = torch.empty_like(gy)
     gz = torch.empty((B, C, M), dtype=torch.float32, device=dev)
-    ws = torch.empty((lib.sonet_pointwise_bwd_apply_nodesum_ws_size(B, M, L),), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev), _timed("pointwise_bwd_apply_nodesum"):
-        check(lib.sonet_pointwise_bwd_apply_nodesum_f32(ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), ptr(a), ptr(b), ptr(c0),
-                                                        ptr(ids), M, ptr(g_raw), ptr(gz), ptr(ws), B, C, L, stream_ptr()),
-              "sonet_pointwise_bwd_apply_nodesum_f32")
+    ws = _ws(lib.sonet_pointwise_bwd_apply_nodesum_ws_size, dev, B, M, L)
+    _launch(dev, "pointwise_bwd_apply_nodesum", lib.sonet_pointwise_bwd_apply_nodesum_f32, ptr(gy), ptr(raw), ptr(scale), ptr(shift), int(bool(relu)), ptr(a),
+            ptr(b), ptr(c0), ptr(ids), M, ptr(g_raw), ptr(gz), ptr(ws), B, C, L)
     return g_raw, gz
 
 
-P16_ONLY = _os.environ.get("SONET_P16_ONLY", "1") != "0"        # segmenter: the fused first PointNet writes only the P16 planes of first_pn_out
-POOLED_DGRAD_MFMA = _os.environ.get("SONET_POOLED_DGRAD_MFMA", "1") != "0"        # bf16 outputs: the dense-tile product on the matrix cores (sonet_pooled_dgrad_mfma_bf16) when the shape allows
+P16_ONLY = _flag("P16_ONLY")        # segmenter: the fused first PointNet writes only the P16 planes of first_pn_out
+POOLED_DGRAD_MFMA = _flag("POOLED_DGRAD_MFMA")        # bf16 outputs: the dense-tile product on the matrix cores (sonet_pooled_dgrad_mfma_bf16) when the shape allows
 
 
 def pooled_dgrad_mfma_ok(C, C1, C2, L):
@@ -2423,7 +2267,7 @@ def pooled_dgrad_mfma_ok(C, C1, C2, L):
 # the BatchNorm-backward sums of the layer that produced x2 can ride on the store of the launch (sonet_pooled_dgrad_tail_f32) instead of being two
 # scatter_add launches and a statistics pass over (gy, raw) of that layer.  OFF: measured slower -- 1.24 ms against 1.00 ms for the three
 # launches apart (the store phase reads raw in 128-byte pieces from five workgroups per CU; docs/findings.md R5.14); kept as a tested record.
-POOLED_DGRAD_TAIL = _os.environ.get("SONET_POOLED_DGRAD_TAIL", "0") != "0"
+POOLED_DGRAD_TAIL = _flag("POOLED_DGRAD_TAIL", "0")
 
 
 def pooled_dgrad_tail_ok(C1, C2, out_dtype):
@@ -2442,7 +2286,7 @@ def pooled_dgrad(g_pooled, pos_i32, weight2d, C1, C2, L, out_dtype=torch.float32
     dev = _same_device(g_pooled, pos_i32, weight2d)
     B, C, M = g_pooled.shape
     lib = _lib.load()
-    ws = torch.empty((lib.sonet_pooled_dgrad_ws_size(B, C, M, int(L)),), dtype=torch.uint8, device=dev)
+    ws = _ws(lib.sonet_pooled_dgrad_ws_size, dev, B, C, M, int(L))
     gx1 = torch.empty((B, C1, int(L)), dtype=out_dtype, device=dev)
     gx2 = torch.empty((B, C2, int(L)), dtype=out_dtype, device=dev) if C2 else None
     if col0 is not None or pos0 is not None or below is not None:
@@ -2469,24 +2313,21 @@ def pooled_dgrad(g_pooled, pos_i32, weight2d, C1, C2, L, out_dtype=torch.float32
             if C2 == 0 or tuple(raw.shape) != (B, C2, int(L)) or sc.numel() != C2 or sh.numel() != C2:
                 raise SonetHipError("pooled_dgrad: below = (raw B x C2 x L, sc, sh, relu) with C2 coefficients")
             _same_device(g_pooled, raw, sc, sh)
-            tws = torch.empty((lib.sonet_pooled_dgrad_tail_ws_size(B, C2, int(L)),), dtype=torch.uint8, device=dev)
+            tws = _ws(lib.sonet_pooled_dgrad_tail_ws_size, dev, B, C2, int(L))
             sums = torch.empty((2 * C2,), dtype=torch.float64, device=dev)
-        with _lib.on_device(dev), _timed("pooled_dgrad_tail%s" % ("_sums" if below is not None else "")):
-            check(lib.sonet_pooled_dgrad_tail_f32(ptr(g_pooled), ptr(pos_i32), ptr(weight2d), B, C, M, C1, C2, int(L), ptr(ws), ptr(gx1), ptr(gx2),
-                                                  ptr(col0), ptr(pos0), ptr(raw), ptr(sc), ptr(sh), int(bool(relu)), ptr(tws), ptr(sums), stream_ptr()),
-                  "sonet_pooled_dgrad_tail_f32")
+        _launch(dev, "pooled_dgrad_tail%s" % ("_sums" if below is not None else ""), lib.sonet_pooled_dgrad_tail_f32, ptr(g_pooled), ptr(pos_i32),
+                ptr(weight2d), B, C, M, C1, C2, int(L), ptr(ws), ptr(gx1), ptr(gx2), ptr(col0), ptr(pos0), ptr(raw), ptr(sc), ptr(sh), int(bool(relu)),
+                ptr(tws), ptr(sums))
         return (gx1, gx2, sums) if below is not None else (gx1, gx2)
     if wt_pack is not None and out_dtype == torch.bfloat16 and pooled_dgrad_mfma_ok(C, C1, C2, int(L)):
         if wt_pack.dtype != torch.int16 or wt_pack.numel() != lib.sonet_pointmlp_bf16_pack_size(C, (C1 + C2 + 31) // 32 * 32) // 2:
             raise SonetHipError("pooled_dgrad: wt_pack is not the bf16 pack of W^T")
-        with _lib.on_device(dev), _timed("pooled_dgrad_mfma"):
-            check(lib.sonet_pooled_dgrad_mfma_bf16(ptr(g_pooled), ptr(pos_i32), ptr(wt_pack), B, C, M, C1, C2, int(L), ptr(ws), ptr(gx1), ptr(gx2),
-                                                   stream_ptr()), "sonet_pooled_dgrad_mfma_bf16")
+        _launch(dev, "pooled_dgrad_mfma", lib.sonet_pooled_dgrad_mfma_bf16, ptr(g_pooled), ptr(pos_i32), ptr(wt_pack), B, C, M, C1, C2, int(L), ptr(ws),
+                ptr(gx1), ptr(gx2))
         return gx1, gx2
     fn = lib.sonet_pooled_dgrad_f32 if out_dtype == torch.float32 else lib.sonet_pooled_dgrad_obf16
-    with _lib.on_device(dev), _timed("pooled_dgrad"):
-        check(fn(ptr(g_pooled), ptr(pos_i32), ptr(weight2d), B, C, M, C1, C2, int(L), ptr(ws), ptr(gx1), ptr(gx2), stream_ptr()),
-              "sonet_pooled_dgrad")
+    _launch(dev, "pooled_dgrad", fn, ptr(g_pooled), ptr(pos_i32), ptr(weight2d), B, C, M, C1, C2, int(L), ptr(ws), ptr(gx1), ptr(gx2),
+            what="sonet_pooled_dgrad")
     return gx1, gx2
 
 
@@ -2503,22 +2344,14 @@ def pooled_wgrad(g_pooled_t, pos_i32_t, x, xaff=None):
     part = torch.empty((B, C, Ci), dtype=torch.float32, device=dev)
     lib = _lib.load()
     if xaff is not None:
-        xs, xh, xr = xaff
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise SonetHipError("pooled_wgrad: float32 or bfloat16 rows")
-        _chk(xs, "xaff scale", torch.float32, 1)
-        _chk(xh, "xaff shift", torch.float32, 1)
-        if xs.numel() != Ci or xh.numel() != Ci:
-            raise SonetHipError("pooled_wgrad: xaff needs Ci = %d coefficients" % Ci)
-        _same_device(x, xs, xh)
         fnx = lib.sonet_pooled_wgrad_xaff_f32 if x.dtype == torch.float32 else lib.sonet_pooled_wgrad_xaff_xbf16
-        with _lib.on_device(dev), _timed("pooled_wgrad_xaff"):
-            check(fnx(ptr(g_pooled_t), ptr(pos_i32_t), ptr(x), B, C, M, Ci, L, ptr(part), ptr(xs), ptr(xh), int(bool(xr)), stream_ptr()),
-                  "sonet_pooled_wgrad_xaff")
+        _launch(dev, "pooled_wgrad_xaff", fnx, ptr(g_pooled_t), ptr(pos_i32_t), ptr(x), B, C, M, Ci, L, ptr(part),
+                *_xaff3(xaff, Ci, "pooled_wgrad: xaff needs Ci", x), what="sonet_pooled_wgrad_xaff")
         return part.sum(0)
     fn = lib.sonet_pooled_wgrad_f32 if x.dtype == torch.float32 else lib.sonet_pooled_wgrad_xbf16
-    with _lib.on_device(dev), _timed("pooled_wgrad"):
-        check(fn(ptr(g_pooled_t), ptr(pos_i32_t), ptr(x), B, C, M, Ci, L, ptr(part), stream_ptr()), "sonet_pooled_wgrad")
+    _launch(dev, "pooled_wgrad", fn, ptr(g_pooled_t), ptr(pos_i32_t), ptr(x), B, C, M, Ci, L, ptr(part), what="sonet_pooled_wgrad")
     return part.sum(0)
 
 
@@ -2535,13 +2368,12 @@ def linear_act(x, weight, scale, shift, relu):
         raise SonetHipError("linear_act: scale / shift must hold Cout = %d float32 elements" % Cout)
     x, weight = _aligned16(x), _aligned16(weight)                 # (16-byte loads when Cin % 4 == 0; the C entry refuses misaligned ones)
     y = torch.empty((B, Cout), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("linear_act_%dx%d" % (Cin, Cout)):
-        check(_lib.load().sonet_linear_act_f32(ptr(x), ptr(weight), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cin, Cout, stream_ptr()),
-              "sonet_linear_act_f32")
+    _launch(dev, "linear_act_%dx%d" % (Cin, Cout), _lib.load().sonet_linear_act_f32, ptr(x), ptr(weight), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B,
+            Cin, Cout)
     return y
 
 
-FC_HEAD = _os.environ.get("SONET_FC_HEAD", "1") != "0"          # training: the heads' B x C layers on sonet_fc_* (one forward, two backward launches per layer)
+FC_HEAD = _flag("FC_HEAD")          # training: the heads' B x C layers on sonet_fc_* (one forward, two backward launches per layer)
 
 
 def fc_head_ok(x, weight):
@@ -2561,10 +2393,8 @@ def fc_bn_act_fwd(x, weight, bias, gamma, beta, running_mean, running_var, momen
     y = torch.empty((B, Cout), dtype=torch.float32, device=dev)
     xhat = torch.empty((B, Cout), dtype=torch.float32, device=dev) if gamma is not None else None
     invstd = torch.empty((Cout,), dtype=torch.float32, device=dev) if gamma is not None else None
-    with _lib.on_device(dev), _timed("fc_bn_act_fwd_%dx%d" % (Cin, Cout)):
-        check(_lib.load().sonet_fc_bn_act_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-                                                  float(momentum), float(eps), int(bool(relu)), B, Cin, Cout, ptr(y), ptr(xhat), ptr(invstd),
-                                                  stream_ptr()), "sonet_fc_bn_act_fwd_f32")
+    _launch(dev, "fc_bn_act_fwd_%dx%d" % (Cin, Cout), _lib.load().sonet_fc_bn_act_fwd_f32, ptr(x), ptr(weight), ptr(bias), ptr(gamma), ptr(beta),
+            ptr(running_mean), ptr(running_var), float(momentum), float(eps), int(bool(relu)), B, Cin, Cout, ptr(y), ptr(xhat), ptr(invstd))
     return y, xhat, invstd
 
 
@@ -2578,10 +2408,8 @@ def fc_bn_act_bwd(gy, y, xhat, invstd, gamma, x, relu, want_dw=True):
     dW = torch.empty((Cout, Cin), dtype=torch.float32, device=dev) if want_dw else None
     vec = torch.empty((3, Cout), dtype=torch.float32, device=dev)
     has_bn = gamma is not None
-    with _lib.on_device(dev), _timed("fc_bn_act_bwd_%dx%d" % (Cin, Cout)):
-        check(_lib.load().sonet_fc_bn_act_bwd_f32(ptr(gy), ptr(y), ptr(xhat), ptr(invstd), ptr(gamma), ptr(x), int(bool(relu)), B, Cin, Cout,
-                                                  ptr(dz), ptr(dW), ptr(vec[0]), ptr(vec[1]) if has_bn else None, ptr(vec[2]) if has_bn else None,
-                                                  stream_ptr()), "sonet_fc_bn_act_bwd_f32")
+    _launch(dev, "fc_bn_act_bwd_%dx%d" % (Cin, Cout), _lib.load().sonet_fc_bn_act_bwd_f32, ptr(gy), ptr(y), ptr(xhat), ptr(invstd), ptr(gamma), ptr(x),
+            int(bool(relu)), B, Cin, Cout, ptr(dz), ptr(dW), ptr(vec[0]), ptr(vec[1]) if has_bn else None, ptr(vec[2]) if has_bn else None)
     return dz, dW, vec[0], (vec[1] if has_bn else None), (vec[2] if has_bn else None)
 
 
@@ -2593,8 +2421,7 @@ def fc_dx(dz, weight):
     B, Cout = dz.shape
     Cin = weight.shape[1]
     dx = torch.empty((B, Cin), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("fc_dx_%dx%d" % (Cin, Cout)):
-        check(_lib.load().sonet_fc_dx_f32(ptr(dz), ptr(weight), B, Cin, Cout, ptr(dx), stream_ptr()), "sonet_fc_dx_f32")
+    _launch(dev, "fc_dx_%dx%d" % (Cin, Cout), _lib.load().sonet_fc_dx_f32, ptr(dz), ptr(weight), B, Cin, Cout, ptr(dx))
     return dx
 
 
@@ -2606,8 +2433,7 @@ def chamfer_nn(q, db):
     B, _, Nq = q.shape
     Nd = db.shape[2]
     nn = torch.empty((B, Nq), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("chamfer_nn"):
-        check(_lib.load().sonet_chamfer_nn_f32(ptr(q), ptr(db), ptr(nn), B, Nq, Nd, stream_ptr()), "sonet_chamfer_nn_f32")
+    _launch(dev, "chamfer_nn", _lib.load().sonet_chamfer_nn_f32, ptr(q), ptr(db), ptr(nn), B, Nq, Nd)
     return nn
 
 
@@ -2651,9 +2477,8 @@ def chamfer_terms(pred, gt, want_nn=True, want_elems=True):
         r.elem_fwd, r.elem_bwd = el[:B * M].view(B, M), el[B * M:].view(B, N)
     f64 = torch.empty((2 * B + lib.sonet_chamfer_loss_ws_size(B, M, N) // 8,), dtype=torch.float64, device=dev)
     r.sums = f64[:2 * B].view(B, 2)
-    with _lib.on_device(dev), _timed("chamfer_loss"):
-        check(lib.sonet_chamfer_loss_f32(ptr(pred), ptr(gt), ptr(r.nn_pg), ptr(r.nn_gp), ptr(r.elem_fwd), ptr(r.elem_bwd), ptr(r.sums),
-                                         ptr(f64[2 * B:]), B, M, N, stream_ptr()), "sonet_chamfer_loss_f32")
+    _launch(dev, "chamfer_loss", lib.sonet_chamfer_loss_f32, ptr(pred), ptr(gt), ptr(r.nn_pg), ptr(r.nn_gp), ptr(r.elem_fwd), ptr(r.elem_bwd), ptr(r.sums),
+            ptr(f64[2 * B:]), B, M, N)
     return r
 
 
@@ -2672,10 +2497,8 @@ def chamfer_grad(pred, gt, terms, gscale):
     _same_device(pred, terms.nn_pg, terms.nn_gp, terms.elem_fwd, terms.elem_bwd, gscale)
     dpred = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
     bad = torch.empty((1,), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("chamfer_grad"):
-        check(_lib.load().sonet_chamfer_grad_f32(ptr(pred), ptr(gt), ptr(terms.nn_pg), ptr(terms.nn_gp), ptr(terms.elem_fwd),
-                                                 ptr(terms.elem_bwd), ptr(gscale), ptr(dpred), ptr(bad), B, M, N, stream_ptr()),
-              "sonet_chamfer_grad_f32")
+    _launch(dev, "chamfer_grad", _lib.load().sonet_chamfer_grad_f32, ptr(pred), ptr(gt), ptr(terms.nn_pg), ptr(terms.nn_gp), ptr(terms.elem_fwd),
+            ptr(terms.elem_bwd), ptr(gscale), ptr(dpred), ptr(bad), B, M, N)
     return dpred, bad
 
 
@@ -2737,9 +2560,8 @@ def upconv3x3_pack(weight4d):
         raise SonetHipError("upconv3x3_pack: Cout = %d is not a multiple of %d" % (Cout, UPCONV_COUT_BLOCK))
     dev = _same_device(weight4d)
     lib = _lib.load()
-    with _lib.on_device(dev):
-        wp = torch.empty((lib.sonet_upconv3x3_pack_size(Cin, Cout) // 4,), dtype=torch.int32, device=dev)
-        check(lib.sonet_upconv3x3_pack_f32(ptr(weight4d), ptr(wp), Cin, Cout, stream_ptr()), "sonet_upconv3x3_pack_f32")
+    wp = _pack_empty(lib, "upconv", Cin, Cout, dev)
+    _launch(dev, None, lib.sonet_upconv3x3_pack_f32, ptr(weight4d), ptr(wp), Cin, Cout)
     return wp
 
 
@@ -2759,18 +2581,14 @@ def upconv3x3(x, wp, scale, shift, relu, Cout):
     _chk_cvec(Cout, scale=scale, shift=shift)
     dev = _same_device(x, wp, scale, shift)
     lib = _lib.load()
-    if wp.numel() * 4 != lib.sonet_upconv3x3_pack_size(Cin, Cout):
-        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
-                            % (wp.numel() * 4, lib.sonet_upconv3x3_pack_size(Cin, Cout), Cin, Cout))
+    _chk_pack(lib, wp, "upconv", Cin, Cout, "bytes")
     y = torch.empty((B, Cout, 2 * H, 2 * W), dtype=torch.float32, device=dev)
     name = "upconv3x3_%dx%d_%dx%d" % (Cin, Cout, H, W)
     slot = None
     if _range_active is not None:
         import ctypes
         slot = ctypes.c_void_p(_range_active._slot(name))
-    with _lib.on_device(dev), _timed(name):
-        check(lib.sonet_upconv3x3_f32(ptr(x), ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cin, Cout, H, W, slot,
-                                      stream_ptr()), "sonet_upconv3x3_f32")
+    _launch(dev, name, lib.sonet_upconv3x3_f32, ptr(x), ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(y), B, Cin, Cout, H, W, slot)
     return y
 
 
@@ -2785,9 +2603,8 @@ def upconv3x3_dgrad_pack(weight4d):
         raise SonetHipError("upconv3x3_dgrad_pack: Cout = %d is not a multiple of %d" % (Cout, UPCONV_COUT_BLOCK))
     dev = _same_device(weight4d)
     lib = _lib.load()
-    with _lib.on_device(dev):
-        wpt = torch.empty((lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout) // 4,), dtype=torch.int32, device=dev)
-        check(lib.sonet_upconv3x3_dgrad_pack_f32(ptr(weight4d), ptr(wpt), Cin, Cout, stream_ptr()), "sonet_upconv3x3_dgrad_pack_f32")
+    wpt = _pack_empty(lib, "upconv-dgrad", Cin, Cout, dev)
+    _launch(dev, None, lib.sonet_upconv3x3_dgrad_pack_f32, ptr(weight4d), ptr(wpt), Cin, Cout)
     return wpt
 
 
@@ -2807,14 +2624,11 @@ def upconv3x3_dgrad(g, wpt, Cin):
     _chk(wpt, "wpt", torch.int32, 1)
     dev = _same_device(g, wpt)
     lib = _lib.load()
-    if wpt.numel() * 4 != lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout):
-        raise SonetHipError("packed weight has %d bytes, expected %d for Cin=%d Cout=%d"
-                            % (wpt.numel() * 4, lib.sonet_upconv3x3_dgrad_pack_size(Cin, Cout), Cin, Cout))
+    _chk_pack(lib, wpt, "upconv-dgrad", Cin, Cout, "bytes")
     if g.data_ptr() % 8 or wpt.data_ptr() % 16:
         raise SonetHipError("upconv3x3_dgrad: g must be 8-byte and the pack 16-byte aligned")
     dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev), _timed("upconv3x3_dgrad_%dx%d_%dx%d" % (Cin, Cout, H, W)):
-        check(lib.sonet_upconv3x3_dgrad_f32(ptr(g), ptr(wpt), ptr(dx), B, Cin, Cout, H, W, stream_ptr()), "sonet_upconv3x3_dgrad_f32")
+    _launch(dev, "upconv3x3_dgrad_%dx%d_%dx%d" % (Cin, Cout, H, W), lib.sonet_upconv3x3_dgrad_f32, ptr(g), ptr(wpt), ptr(dx), B, Cin, Cout, H, W)
     return dx
 
 
@@ -2848,9 +2662,8 @@ def upconv3x3_wgrad(g, x):
     if g.data_ptr() % 8 or x.data_ptr() % 4:
         raise SonetHipError("upconv3x3_wgrad: g must be 8-byte and x 4-byte aligned")
     dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=dev)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev), _timed("upconv3x3_wgrad_%dx%d_%dx%d" % (Cin, Cout, H, W)):
-        check(lib.sonet_upconv3x3_wgrad_f32(ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cin, Cout, H, W, stream_ptr()), "sonet_upconv3x3_wgrad_f32")
+    ws = _ws(nbytes, dev)
+    _launch(dev, "upconv3x3_wgrad_%dx%d_%dx%d" % (Cin, Cout, H, W), lib.sonet_upconv3x3_wgrad_f32, ptr(g), ptr(x), ptr(dw), ptr(ws), B, Cin, Cout, H, W)
     return dw
 
 
@@ -2912,10 +2725,8 @@ def seg_metrics(score, seg, label, part_offsets=None, want_pred=False):
     f64 = torch.empty((2, B), dtype=torch.float64, device=dev)
     r.nll_sum, r.iou = f64[0], f64[1]
     ws = torch.empty((max(1, lib.sonet_seg_metrics_ws_size(B, C, N) // 8),), dtype=torch.float64, device=dev)
-    with _lib.on_device(dev), _timed("seg_metrics"):
-        check(lib.sonet_seg_metrics_f32(ptr(score), ptr(seg), ptr(label), ptr(table), n_cat, ptr(r.pred), ptr(r.correct), ptr(r.nll_sum),
-                                        ptr(r.inter), ptr(r.pred_cnt), ptr(r.gt_cnt), ptr(r.iou), ptr(r.bad), ptr(ws), B, C, N,
-                                        stream_ptr()), "sonet_seg_metrics_f32")
+    _launch(dev, "seg_metrics", lib.sonet_seg_metrics_f32, ptr(score), ptr(seg), ptr(label), ptr(table), n_cat, ptr(r.pred), ptr(r.correct), ptr(r.nll_sum),
+            ptr(r.inter), ptr(r.pred_cnt), ptr(r.gt_cnt), ptr(r.iou), ptr(r.bad), ptr(ws), B, C, N)
     return r
 
 
@@ -2991,10 +2802,8 @@ def retrieval_lists(feat, labels=None, ids=None, query=None, top=1000, n_label=N
     ints = torch.empty((Q + N + 1,), dtype=torch.int32, device=dev)
     r.count, r.labels, r.bad = ints[:Q], ints[Q:Q + N], ints[Q + N:]
     ws = torch.empty((lib.sonet_retrieval_ws_size(N, D, Q, top) // 4,), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("retrieval_lists"):
-        check(lib.sonet_retrieval_lists_f32(ptr(feat), ptr(labels), ptr(ids), ptr(query), n_label, top, ptr(r.nn_id), ptr(r.nn_dist),
-                                            ptr(r.nn_pos), ptr(r.count), ptr(r.labels), ptr(r.bad), ptr(ws), N, D, Q, stream_ptr()),
-              "sonet_retrieval_lists_f32")
+    _launch(dev, "retrieval_lists", lib.sonet_retrieval_lists_f32, ptr(feat), ptr(labels), ptr(ids), ptr(query), n_label, top, ptr(r.nn_id), ptr(r.nn_dist),
+            ptr(r.nn_pos), ptr(r.count), ptr(r.labels), ptr(r.bad), ptr(ws), N, D, Q)
     return r
 
 
@@ -3004,10 +2813,8 @@ def mfma_f16_sustained_rate(random_operands=True, iters=4000, device=None):
     import ctypes
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     tf, ghz = ctypes.c_double(0.0), ctypes.c_double(0.0)
-    with _lib.on_device(dev):
-        _lib.require_device(dev)
-        check(_lib.load().sonet_diag_mfma_f16_rate(1 if random_operands else 0, int(iters), ctypes.byref(tf), ctypes.byref(ghz), stream_ptr()),
-              "sonet_diag_mfma_f16_rate")
+    _lib.require_device(dev)
+    _launch(dev, None, _lib.load().sonet_diag_mfma_f16_rate, 1 if random_operands else 0, int(iters), ctypes.byref(tf), ctypes.byref(ghz))
     return tf.value, ghz.value
 
 
@@ -3024,9 +2831,7 @@ def knn_prepare(coord, knn_I, center_avg):
     center = torch.empty((B, 3, M), dtype=torch.float32, device=dev)
     dec = torch.empty((B, 3, K * M), dtype=torch.float32, device=dev)
     gidx = torch.empty((B, K * M), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev), _timed("knn_prepare"):
-        check(_lib.load().sonet_knn_prepare_f32(ptr(coord), ptr(knn_I), B, M, K, int(bool(center_avg)), ptr(center), ptr(dec), ptr(gidx),
-                                                stream_ptr()), "sonet_knn_prepare_f32")
+    _launch(dev, "knn_prepare", _lib.load().sonet_knn_prepare_f32, ptr(coord), ptr(knn_I), B, M, K, int(bool(center_avg)), ptr(center), ptr(dec), ptr(gidx))
     return center, dec, gidx
 
 
@@ -3043,8 +2848,7 @@ def planes_max(x, K):
     out = torch.empty((B, C, L // K), dtype=torch.float32, device=dev)
     if out.numel() == 0:
         return out
-    with _lib.on_device(dev), _timed("planes_max"):
-        check(_lib.load().sonet_planes_max_f32(ptr(x), ptr(out), B * C, K, L // K, stream_ptr()), "sonet_planes_max_f32")
+    _launch(dev, "planes_max", _lib.load().sonet_planes_max_f32, ptr(x), ptr(out), B * C, K, L // K)
     return out
 
 
@@ -3054,9 +2858,8 @@ def bn_running_update_(running_mean, running_var, mean, var, momentum, unbias):
         _chk(t, n, torch.float32, 1)
     _chk_cvec(running_mean.numel(), running_var=running_var, mean=mean, var=var)
     dev = _same_device(running_mean, running_var, mean, var)
-    with _lib.on_device(dev):
-        check(_lib.load().sonet_bn_running_update_f32(ptr(running_mean), ptr(running_var), ptr(mean), ptr(var), float(momentum), float(unbias),
-                                                      running_mean.numel(), stream_ptr()), "sonet_bn_running_update_f32")
+    _launch(dev, None, _lib.load().sonet_bn_running_update_f32, ptr(running_mean), ptr(running_var), ptr(mean), ptr(var), float(momentum), float(unbias),
+            running_mean.numel())
     # written through raw pointers: move the version counters as an in-place aten op would (caches keyed on versions must notice)
     torch.autograd.graph.increment_version(running_mean)
     torch.autograd.graph.increment_version(running_var)

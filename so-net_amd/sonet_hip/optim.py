@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import SonetHipError, check, ptr, stream_ptr
+from .ops import SonetHipError, _launch, ptr
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -132,9 +132,9 @@ class FusedAdam(torch.optim.Optimizer):
                 dev.copy_(plan["host"], non_blocking=True)
                 plan["event"] = torch.cuda.Event()
                 plan["event"].record()
-                check(lib.sonet_adam_multi_f32(ptr(dev), ptr(plan["dev_scal"][0]), ptr(plan["dev_scal"][1]), ptr(plan["chunk_tensor"]),
-                                               ptr(plan["chunk_off"]), ptr(plan["sizes"]), int(plan["chunk_tensor"].numel()),
-                                               float(b1), float(b2), float(1.0 - b1), float(1.0 - b2), float(eps), stream_ptr()), "sonet_adam_multi_f32")
+            _launch(dev.device, None, lib.sonet_adam_multi_f32, ptr(dev), ptr(plan["dev_scal"][0]), ptr(plan["dev_scal"][1]), ptr(plan["chunk_tensor"]),
+                    ptr(plan["chunk_off"]), ptr(plan["sizes"]), int(plan["chunk_tensor"].numel()), float(b1), float(b2), float(1.0 - b1), float(1.0 - b2),
+                    float(eps))
             # the kernel wrote through raw pointers: tell autograd and every cache keyed on ``_version`` (the packed weights of the layer
             # kernels, the h3 weight-range verdicts) that the parameters changed, as an in-place aten op would
             for p in updated:

@@ -4,8 +4,8 @@ SONET_HIP_LIB to point at the variants library (tools/_variants.py does that); t
 import torch
 
 from . import _lib
-from ._lib import SonetHipError, check, ptr, stream_ptr
-from .ops import _chk, _range_arm, _same_device, _timed
+from ._lib import SonetHipError, ptr
+from .ops import _chk, _chk_pack, _launch, _range_arm, _same_device, _ws
 
 
 def _need(name):
@@ -31,15 +31,13 @@ def pointmlp_kmax(x1, wp, scale, shift, relu, Cout, M):
         raise SonetHipError("pointmlp_kmax: L %% M == 0 and Cout %% 128 == 0")
     dev = _same_device(x1, wp, scale, shift)
     lib = _need("sonet_pointmlp_h3_kmax_f32")
-    if wp.numel() != lib.sonet_pointmlp_x3_pack_size(C1, Cout):
-        raise SonetHipError("packed weight does not match Cin=%d Cout=%d" % (C1, Cout))
+    _chk_pack(lib, wp, "h3", C1, Cout)
     out = torch.empty((B, Cout, int(M)), dtype=torch.float32, device=dev)
     keys = torch.empty((B, Cout, int(M)), dtype=torch.int32, device=dev)
     name = "pointmlph3_kmax_%dx%d_L%d" % (C1, Cout, L)
     _range_arm(name)
-    with torch.cuda.device(dev), _timed(name):
-        check(lib.sonet_pointmlp_h3_kmax_f32(ptr(x1), C1, None, 0, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(out), ptr(keys),
-                                             B, Cout, L, int(M), stream_ptr()), "sonet_pointmlp_h3_kmax_f32")
+    _launch(dev, name, lib.sonet_pointmlp_h3_kmax_f32, ptr(x1), C1, None, 0, ptr(wp), ptr(scale), ptr(shift), int(bool(relu)), ptr(out), ptr(keys),
+            B, Cout, L, int(M))
     return out
 
 
@@ -57,7 +55,6 @@ def chamfer_nn2(a, b):
     lib = _need("sonet_chamfer_nn2_f32")
     nn_ab = torch.empty((B, Na), dtype=torch.int32, device=dev)
     nn_ba = torch.empty((B, Nb), dtype=torch.int32, device=dev)
-    ws = torch.empty((lib.sonet_chamfer_nn2_ws_size(B, Na, Nb),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev), _timed("chamfer_nn2"):
-        check(lib.sonet_chamfer_nn2_f32(ptr(a), ptr(b), ptr(nn_ab), ptr(nn_ba), ptr(ws), B, Na, Nb, stream_ptr()), "sonet_chamfer_nn2_f32")
+    ws = _ws(lib.sonet_chamfer_nn2_ws_size, dev, B, Na, Nb)
+    _launch(dev, "chamfer_nn2", lib.sonet_chamfer_nn2_f32, ptr(a), ptr(b), ptr(nn_ab), ptr(nn_ba), ptr(ws), B, Na, Nb)
     return nn_ab, nn_ba
