@@ -5,19 +5,31 @@ Class names, constructor signatures, ``forward(x, epoch=None)`` signatures and `
 ``linear.*``) are those of the reference, so checkpoints and the unmodified
 heads (models/networks.py Classifier / Segmenter / Decoder*) load and run on top.
 
-What is different underneath: ``EquivariantLayer`` (Conv1d k=1 + BN + ReLU, models/layers.py:243-296)
-and ``MyConv2d`` with a 1x1 kernel (:169-211) execute as ONE fused gfx950 kernel
-(``sonet_pointmlp_f32``: exact-f32 MFMA GEMM with the bias / BatchNorm / ReLU epilogue) instead of
-three aten launches; ``PointResNet`` feeds its skip concat (:431) to that kernel as a second input
-panel instead of materialising it.  Training mode computes the batch statistics with
-``sonet_channel_stats_f32`` and normalises in place; gradients flow through a custom
-``autograd.Function``.  ``MyLinear`` / ``UpConv`` (classifier FCs, decoder convs) are outside the
-hot path and stay on PyTorch-ROCm ops.
+What is different underneath (every path is a gfx950 kernel of ``sonet_hip.ops``; a missing one is an error, not an aten fallback):
+
+* ``EquivariantLayer`` (Conv1d k=1 + BN + ReLU, models/layers.py:243-296) and ``MyConv2d`` with a 1x1 kernel (:169-211) are one fused
+  layer launch (``ops.pointmlp``: bias / BatchNorm / ReLU in the epilogue) in the arithmetic ``ops.POINTMLP_PRECISION`` selects (h3, x3,
+  bf16, f32).  In training ``_PointwiseFn`` adds the batch statistics (a pass of their own or the layer's epilogue), the normalise pass
+  and the backward launches; the weight gradient runs on a side stream.
+* ``PointResNet`` feeds its skip concat (:431) to the kernel as a second input panel; in eval it is ONE launch (``ops.pointresnet_fused``),
+  in training ``forward_pooled`` ends in ``_PooledLastLayerFn`` (last layer + per-node arg-max pool as one node), and where the
+  arithmetic has the form the hidden layers hand their RAW outputs on and every consumer normalises on load (``defer`` / ``xaff``).
+* ``KNNModule`` and ``PointNet.forward_cat`` launch the layer kernels themselves in eval (gathered operand loads, rotated packs).
+* ``MyLinear`` (classifier FCs) runs on ``ops.linear_act`` in eval and on the ``sonet_fc_*`` kernels in training (``_FcFn``); ``UpConv``
+  (decoder) on the folded up-convolution kernels in eval (``fused``) and in training (``fused_train`` / ``fused_wgrad``,
+  ``_UpConvTrainFn``).  Other norms, activations and shapes of these two -- outside the hot path -- stay on PyTorch-ROCm ops.
+* ``_NodewiseLayerFn`` is the segmenter's layer 1 in its split (per-point / per-node / per-cloud) form, forward and backward.
+
+The building blocks these share exist once: ``_per_version`` (packs and splits cached per weight version), ``_folded_affine`` (eval-mode
+scale / shift), ``_bn_run`` / ``_bn_ran`` (training BatchNorm around a node), ``_rider`` / ``_bn_bwd_head`` (inside the nodes),
+``_carry_fits``, ``_on_side`` / ``_close_pooled`` (weight gradient on the side stream), ``_plain_norm_act`` / ``_eval_norm_act`` and
+``_init_norm_act`` / ``_init_norm`` (constructors).
 
 There is no CPU path: calling a fused layer on CPU tensors raises (modules can still be
 constructed on CPU, e.g. to build or load a ``state_dict``).
 """
 import math
+import weakref
 
 import torch
 import torch.nn as nn
@@ -59,6 +71,95 @@ class _PlainAttrs:
             d[name] = value
         else:
             nn.Module.__setattr__(self, name, value)
+
+
+def _per_version(owner, slot, w, extra, build):
+    """``build()`` (under no_grad) cached in ``owner.__dict__[slot]`` per version, storage and device of the weight ``w`` plus ``extra``
+    (a tuple: whatever else the product depends on).  A hit is one tuple comparison; the instance ``__dict__`` is written directly
+    (``_PlainAttrs``: this runs per layer and step)."""
+    d = owner.__dict__
+    key = (w._version, w.data_ptr(), w.device) + extra
+    if d.get(slot + '_key') != key:
+        with torch.no_grad():
+            d[slot] = build()
+        d[slot + '_key'] = key
+    return d[slot]
+
+
+def _storage_dtype(wp):
+    """The pack decides the kernel and the kernel the storage type: a bf16 pack takes bfloat16 operands."""
+    return torch.bfloat16 if wp.dtype == torch.int16 else torch.float32
+
+
+def _plain_norm_act(m):
+    """No norm or BatchNorm, no activation or ReLU: what the kernels' epilogues hold."""
+    return m.normalization in (None, 'batch') and m.activation in (None, 'relu')
+
+
+def _eval_norm_act(m):
+    """``_plain_norm_act`` with the BatchNorm in eval mode: the layer is one launch with a folded (scale, shift)."""
+    return _plain_norm_act(m) and not (m.normalization == 'batch' and m.norm.training)
+
+
+def _init_norm_act(m, channels, batch_norm, instance_norm, momentum, bn_momentum_decay_step, bn_momentum_decay):
+    """``m.norm`` / ``m.act`` of a conv / linear block as the reference creates them (after the conv: the order of the modules and of
+    the random draws is the reference's)."""
+    if m.normalization == 'batch':
+        m.norm = batch_norm(channels, momentum=momentum, affine=True, momentum_decay_step=bn_momentum_decay_step,
+                            momentum_decay=bn_momentum_decay)
+    elif m.normalization == 'instance':
+        m.norm = instance_norm(channels, momentum=momentum, affine=True)
+    act = _make_act(m.activation)
+    if act is not None:
+        m.act = act
+
+
+def _init_norm(m):
+    if m.normalization in ('batch', 'instance'):
+        m.norm.weight.data.fill_(1)
+        m.norm.bias.data.zero_()
+
+
+def _folded_affine(m, weight, bias, shared_unit):
+    """(scale, shift) folding the bias (None: zero) and the eval-mode BatchNorm (running statistics) of ``m``, cached on it per version
+    of everything folded.  shared_unit: without a norm the scale is the shared ``ops.const_vec`` ones (``_PointwiseFn.backward``
+    recognises a unit scale by its ``data_ptr``); otherwise a tensor of the block's own."""
+    bn = m.norm if m.normalization == 'batch' else None
+    ts = [bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+    key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (weight.device, getattr(bn, 'stats_gen', 0))
+    if getattr(m, '_affine_key', None) != key:
+        with torch.no_grad():
+            b = bias.detach().float() if bias is not None else torch.zeros(weight.shape[0], dtype=torch.float32, device=weight.device)
+            if bn is None:
+                scale, shift = (_ops.const_vec(b.numel(), 1.0, b.device) if shared_unit else torch.ones_like(b)), b.clone()
+            else:
+                scale = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
+                shift = (b - bn.running_mean) * scale + bn.bias.detach()
+            m._affine = (scale.contiguous(), shift.contiguous())
+        m._affine_key = key
+        m._affine_gen = getattr(m, '_affine_gen', 0) + 1          # (id() of the tensors can be recycled: count instead)
+    return m._affine
+
+
+def _bn_run(bn, n, device):
+    """Training BatchNorm around a node, before it: (running_mean, running_var, momentum, unbias) when F.batch_norm's update of the
+    running statistics can ride on the node's statistics launch (``ops.bn_rider``: the buffers allow it), else None."""
+    m = bn.momentum
+    ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
+            and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == device)
+    return (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None
+
+
+def _bn_ran(bn, layer, rode, n, mean, var):
+    """... and after it: F.batch_norm's running-statistics update where it did not ride (``rode`` = what ``_bn_run`` gave), and the
+    folded eval affine of ``layer`` dropped by hand -- the kernel writes the buffers through raw pointers, their _version does not
+    move, and a later eval() would run on stale statistics.  (F.batch_norm does not touch num_batches_tracked; nor does the reference.)"""
+    m = bn.momentum
+    with torch.no_grad():
+        if rode is None and bn.running_mean is not None and m is not None:
+            bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
+            bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
+        layer._affine_key = None
 
 
 class _DecayingBatchNorm(_BatchNorm):
@@ -158,17 +259,58 @@ def _dgrad(g_raw, pack, acc=None):
         y = torch.cat([_dgrad(g_raw, (w, w_rows, w_rows))
                        for w, w_rows in zip(wpt, [min(_F32_DGRAD_ROWS, Cp - r) for r in range(0, Cp, _F32_DGRAD_ROWS)])], dim=1)
         return y if Cp == Ci else y[:, :Ci]
-    want = torch.bfloat16 if wpt.dtype == torch.int16 else torch.float32
+    want = _storage_dtype(wpt)
     if g_raw.dtype != want:
         g_raw = g_raw.to(want)
     y = _ops.pointmlp(g_raw, wpt, _ops.const_vec(Cp, 1.0, g_raw.device), _ops.const_vec(Cp, 0.0, g_raw.device), False, Cp, acc=acc)
     return y if Cp == Ci else y[:, :Ci]
 
 
+def _carry_fits(carried, dtype, B, C, L):
+    """A carried gradient (``_GradCarry``) the store of an input-gradient launch can add: its output's type and shape, contiguous."""
+    return carried.dtype == dtype and carried.is_contiguous() and tuple(carried.shape) == (B, C, L)
+
+
 def _dgrad_acc_ok(g_raw, pack, acc):
     wpt, Ci, Cp = pack
-    return (not isinstance(wpt, list) and wpt.dtype == torch.int16 and Cp == Ci and acc.dtype == torch.bfloat16 and acc.is_contiguous() and g_raw.shape[2] % 2 == 0
-            and tuple(acc.shape) == (g_raw.shape[0], Cp, g_raw.shape[2]))
+    return (not isinstance(wpt, list) and wpt.dtype == torch.int16 and Cp == Ci and g_raw.shape[2] % 2 == 0
+            and _carry_fits(acc, torch.bfloat16, g_raw.shape[0], Cp, g_raw.shape[2]))
+
+
+def _rider(gamma, beta, eps, bn_run):
+    """bn_run = (running_mean, running_var, momentum, unbias) or None (``_bn_run``) -> (invstd, sc, sh) tensors the statistics launch
+    that follows fills: it also writes the normalisation coefficients and updates the running statistics (``ops.bn_rider``: one launch
+    instead of three per layer and step)."""
+    rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
+    return _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+
+
+def _bn_bwd_head(gy, raw, sc, sh, relu, mean, invstd, gamma, sums=None):
+    """Head of a training BatchNorm (+ ReLU) layer's backward: the two per-channel sums over (gy, raw) -- unless the launch that produced
+    gy left them (``sums``, ``_bwd_sums_hint``) -- and from them (a, b, c0, g_gamma, g_beta); gy, raw: B x C x L."""
+    if sums is None:
+        sums = _ops.pointwise_bwd_stats(gy, raw, sc, sh, relu, want_sums=True)
+    return _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, float(raw.shape[0] * raw.shape[2]))
+
+
+def _xaff_tensors(xa):
+    return [t for t in xa if torch.is_tensor(t)] if xa is not None else []
+
+
+def _xaff_halves(xa):
+    """xaff = (s1, h1, relu1[, s2, h2, relu2]) or None -> x1's triple, x2's triple (None, None without xaff)."""
+    return (None, None) if xa is None else (xa[:3], xa[3:6])
+
+
+def _on_side(ss, make, *reads):
+    """``make()`` -- a weight gradient, independent of the input gradient beside it -- on the side stream ``ss`` (None: in line), which
+    reads the tensors ``reads``."""
+    if ss is None:
+        return make()
+    with ss:
+        g = ss.keep(make())
+    ss.reads(*reads)
+    return g
 
 
 def _wgrad(g_raw, x, xaff=None):
@@ -235,7 +377,6 @@ def _bwd_sums_hint(gy, raw, relu):
 
 def _leaf_of(weight2d):
     """The parameter behind a layer's weight2d view (a weak reference: autograd contexts must not keep modules alive)."""
-    import weakref
     base = weight2d._base if weight2d._base is not None else weight2d
     try:
         return weakref.ref(base)
@@ -256,7 +397,6 @@ class _UseToken:
 def _register_use(wleaf):
     """Called by the forward of such a node (grad mode): remembers on the PARAMETER that one more node of a live graph will produce a
     gradient for it.  Returns the token the node keeps in its context."""
-    import weakref
     p = wleaf() if wleaf is not None else None
     if p is None:
         return None
@@ -370,15 +510,12 @@ class _PointwiseFn(torch.autograd.Function):
             ctx.save_for_backward(x1, x2 if x2 is not None else x1.new_empty(0), weight2d, scale, y if relu else x1.new_empty(0),
                                   ones, zeros)
         else:
-            # bn_run = (running_mean, running_var, momentum, unbias) or None: the statistics launch below also writes the normalisation
-            # coefficients and updates the running statistics (``ops.bn_rider``: one launch instead of three per layer and step)
             epi = _stats_epilogue_ok(x1, wp, Cout)
             if xaff is not None and not (epi and wp.dtype in (torch.int8, torch.int16)):
                 raise RuntimeError("_PointwiseFn: normalise-on-load needs the h3 or the bf16 layer with the statistics epilogue")
             if not epi:
                 raw = _ops.pointmlp(x1, wp, ones, bias, False, Cout, x2=x2)
-            rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
-            invstd, sc, sh = _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+            invstd, sc, sh = _rider(gamma, beta, eps, bn_run)
             if epi:
                 # batch statistics out of the layer kernel's epilogue (one pass over raw less; big tensors: the small node-level
                 # ones keep the second-generation kernel, which has no statistics epilogue)
@@ -427,12 +564,8 @@ class _PointwiseFn(torch.autograd.Function):
                 g_raw = _ops.pointwise_bwd_apply(gy, src, ones, zeros, ctx.relu, sc.contiguous(), zeros, zeros)
         else:
             sc, sh, raw, mean, invstd, gamma, zeros = saved[3:10]
-            n = float(raw.shape[0] * raw.shape[2])
             # (the launch that produced gy may have left this layer's sums on it: _bwd_sums_hint)
-            sums = _bwd_sums_hint(gy_in, raw, ctx.relu)
-            if sums is None:
-                sums = _ops.pointwise_bwd_stats(gy, raw, sc, sh, ctx.relu, want_sums=True)
-            a, b, c0, g_gamma, g_beta = _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, n)
+            a, b, c0, g_gamma, g_beta = _bn_bwd_head(gy, raw, sc, sh, ctx.relu, mean, invstd, gamma, _bwd_sums_hint(gy_in, raw, ctx.relu))
             g_bias = zeros.clone()                                        # a bias in front of BatchNorm has no gradient
             # f32-class, one input panel, an input gradient to compute: the BatchNorm / ReLU backward rides on the operand load of the
             # dgrad launch (which also writes g_raw for the weight gradient) instead of being a pass of its own over (gy, raw)
@@ -447,8 +580,7 @@ class _PointwiseFn(torch.autograd.Function):
                     # layer's gy, and its BatchNorm-backward sums come out of the epilogue (handed over on the tensor: _bwd_sums_hint)
                     below = (x1, xa_[0], xa_[1], xa_[2]) if (_ops.BWD_STATS_EPILOGUE and _ops.variants_only() and xa_ is not None and Cp == Ci and x1.dtype == torch.float32) else None
                     acc = None
-                    if (carried is not None and below is None and Cp == Ci and carried.dtype == torch.float32 and carried.is_contiguous()
-                            and tuple(carried.shape) == (gy.shape[0], Cp, gy.shape[2])):
+                    if carried is not None and below is None and Cp == Ci and _carry_fits(carried, torch.float32, gy.shape[0], Cp, gy.shape[2]):
                         acc, carried = carried, None
                     res = _ops.pointmlp_x3_bnb(gy, raw, wpt, _ops.const_vec(Cp, 1.0, dev), _ops.const_vec(Cp, 0.0, dev), a, b, c0, sc, sh, ctx.relu,
                                                Cp, want_g_raw=ctx.needs_input_grad[2], below=below, acc=acc)
@@ -467,8 +599,7 @@ class _PointwiseFn(torch.autograd.Function):
                     wpt, Ci, Cp = pk
                     dev = gy.device
                     acc = None
-                    if (carried is not None and carried.dtype == torch.bfloat16 and carried.is_contiguous()
-                            and tuple(carried.shape) == (gy.shape[0], Cp, gy.shape[2])):
+                    if carried is not None and _carry_fits(carried, torch.bfloat16, gy.shape[0], Cp, gy.shape[2]):
                         acc, carried = carried, None
                     fused_gx1, g_raw = _ops.pointmlp_bf16_bnb(gy, raw, wpt, _ops.const_vec(Cp, 1.0, dev), _ops.const_vec(Cp, 0.0, dev), a, b, c0, sc, sh,
                                                               ctx.relu, Cp, want_g_raw=ctx.needs_input_grad[2], acc=acc)
@@ -479,18 +610,13 @@ class _PointwiseFn(torch.autograd.Function):
         # the weight gradient (HBM-bound) and the input gradient (matrix cores) of a layer are independent: two streams
         ss = _ops.side_stream(g_raw.device) if (ctx.needs_input_grad[2] and (need1 or need2)) else None
         if ctx.needs_input_grad[2]:
-            xa = ctx.xaff
+            xa1, xa2 = _xaff_halves(ctx.xaff)
             def _gw():
-                parts = [_wgrad(g_raw, x1, None if xa is None else xa[:3])]
+                parts = [_wgrad(g_raw, x1, xa1)]
                 if ctx.has_x2:
-                    parts.append(_wgrad(g_raw, x2, None if xa is None else xa[3:6]))
+                    parts.append(_wgrad(g_raw, x2, xa2))
                 return torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]
-            if ss is not None:
-                with ss:
-                    g_w = ss.keep(_gw())
-                ss.reads(g_raw, x1, x2 if ctx.has_x2 else None, *([t for t in xa if torch.is_tensor(t)] if xa is not None else []))
-            else:
-                g_w = _gw()
+            g_w = _on_side(ss, _gw, g_raw, x1, x2 if ctx.has_x2 else None, *_xaff_tensors(ctx.xaff))
         g_x1 = g_x2 = None
         if fused_gx1 is not None:
             g_x1 = fused_gx1
@@ -545,8 +671,7 @@ class _NodewiseLayerFn(torch.autograd.Function):
         x_n = torch.cat((node_lead, node_maps), dim=1).contiguous()
         x_g = torch.cat((glob_lead, glob), dim=1)
         z = (_ops.pointmlp(x_n, wp_node, ones, zeros, False, Cout) + (x_g @ w_glob.t()).unsqueeze(2)).contiguous()
-        rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
-        invstd, sc, sh = _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+        invstd, sc, sh = _rider(gamma, beta, eps, bn_run)
         raw, mean, var = _ops.pointmlp_nodeadd_stats(x1, wp_point, bias.detach().contiguous(), Cout, z, ids, x2=x2)
         y = _ops.channel_affine_act(raw, sc, sh, relu)
         # (the first ten in the order of _PointwiseFn's 'batch' mode: x1, x2, weight2d, sc, sh, raw, mean, invstd, gamma, zeros)
@@ -563,9 +688,7 @@ class _NodewiseLayerFn(torch.autograd.Function):
         x1, x2, weight2d, sc, sh, raw, mean, invstd, gamma, zeros, x_n, x_g, ids = ctx.saved_tensors
         w_glob, wpt_x1, wpt_maps, cols = ctx.split[2:6]
         gy = gy.contiguous()
-        n = float(raw.shape[0] * raw.shape[2])
-        sums = _ops.pointwise_bwd_stats(gy, raw, sc, sh, ctx.relu, want_sums=True)
-        a, b, c0, g_gamma, g_beta = _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, n)
+        a, b, c0, g_gamma, g_beta = _bn_bwd_head(gy, raw, sc, sh, ctx.relu, mean, invstd, gamma)
         g_raw, gz = _ops.pointwise_bwd_apply_nodesum(gy, raw, sc, sh, ctx.relu, a, b, c0, ids, ctx.M)
         need = ctx.needs_input_grad
         gsum = gz.sum(dim=2)                                              # B x Cout: the per-cloud block saw every node's addend
@@ -593,6 +716,18 @@ class _NodewiseLayerFn(torch.autograd.Function):
             g_w[:, glob_cols[0]:glob_cols[1]] = g_wg[:, ctx.n_lead:]
         g_bias = zeros.clone() if need[7] else None                       # a bias in front of BatchNorm has no gradient
         return g_x1, None, None, g_maps, None, g_glob, g_w, g_bias, g_gamma, g_beta, None, None, None, None, None
+
+
+def _close_pooled(ctx, ss, g_x1):
+    """End of ``_PooledLastLayerFn.backward``: the side stream's launches are joined -- at the end of the pass when nothing reads the weight
+    gradient before (``_grad_slot_empty``) -- and x1's gradient goes to the carry when x1's other consumer adds it to its own
+    (-> None), else it is returned."""
+    if ss is not None:
+        ss.join(defer=_grad_slot_empty(ctx.wleaf, ctx.use_token))
+    if ctx.carry is not None and g_x1 is not None:
+        ctx.carry.put(g_x1)
+        return None
+    return g_x1
 
 
 class _PooledLastLayerFn(torch.autograd.Function):
@@ -664,7 +799,7 @@ class _PooledLastLayerFn(torch.autograd.Function):
             return (None,) * 12
         sparse = g_y is None
         xa = ctx.xaff
-        xa1, xa2 = (None, None) if xa is None else (xa[:3], xa[3:6])
+        xa1, xa2 = _xaff_halves(xa)
         G = None
         ss = None
         if g_mm is not None:
@@ -689,14 +824,10 @@ class _PooledLastLayerFn(torch.autograd.Function):
                 # 24,576 entries per cloud instead of a dense GEMM over kN columns (the kernel's limits: C, M, two rows in LDS);
                 # on the side stream: the sparse dgrad below does not depend on it (0.66 + 0.83 ms in sequence otherwise)
                 ss = _ops.side_stream(x1.device) if ((ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and _ops.POOLED_SIDE_STREAM) else None
-                if ss is not None:
-                    with ss:
-                        g_t, gi_t = g_mm.transpose(1, 2).contiguous(), gi.transpose(1, 2).contiguous()
-                        g_w = ss.keep(torch.cat((_ops.pooled_wgrad(g_t, gi_t, x1, xa1), _ops.pooled_wgrad(g_t, gi_t, x2, xa2)), dim=1))
-                    ss.reads(g_mm, gi, x1, x2, *([t for t in xa if torch.is_tensor(t)] if xa is not None else []))
-                else:
+                def _gw():
                     g_t, gi_t = g_mm.transpose(1, 2).contiguous(), gi.transpose(1, 2).contiguous()     # B x M x C: coalesced entry loads
-                    g_w = torch.cat((_ops.pooled_wgrad(g_t, gi_t, x1, xa1), _ops.pooled_wgrad(g_t, gi_t, x2, xa2)), dim=1)
+                    return torch.cat((_ops.pooled_wgrad(g_t, gi_t, x1, xa1), _ops.pooled_wgrad(g_t, gi_t, x2, xa2)), dim=1)
+                g_w = _on_side(ss, _gw, g_mm, gi, x1, x2, *_xaff_tensors(xa))
             else:
                 if G is None:
                     G = torch.zeros((B, weight2d.shape[0], L), dtype=x1.dtype, device=x1.device)
@@ -730,12 +861,7 @@ class _PooledLastLayerFn(torch.autograd.Function):
                     g_x1, g_x2 = res[0], res[1]
                     if below is not None:
                         g_x2._sonet_bwd_sums = (res[2], x2.data_ptr(), g_x2._version, bool(xa[5]))
-                    if ss is not None:
-                        ss.join(defer=_grad_slot_empty(ctx.wleaf, ctx.use_token))
-                    if ctx.carry is not None and g_x1 is not None:
-                        ctx.carry.put(g_x1)
-                        g_x1 = None
-                    return g_x1, g_x2, g_w, g_bias, None, None, None, None, None, None, None, None
+                    return (_close_pooled(ctx, ss, g_x1), g_x2, g_w, g_bias) + (None,) * 8
                 g_x1, g_x2 = _ops.pooled_dgrad(g_mm.float(), torch.where(occ, gi, torch.full_like(gi, -1)), w, C1, C2, L, out_dtype=x1.dtype,
                                                wt_pack=wt_pack)
                 if ctx.pos0 is None:
@@ -751,12 +877,7 @@ class _PooledLastLayerFn(torch.autograd.Function):
                 for pk in packs:
                     outs.append(_dgrad(G, pk))
                 g_x1, g_x2 = outs
-        if ss is not None:
-            ss.join(defer=_grad_slot_empty(ctx.wleaf, ctx.use_token))
-        if ctx.carry is not None and g_x1 is not None:
-            ctx.carry.put(g_x1)
-            g_x1 = None
-        return g_x1, g_x2, g_w, g_bias, None, None, None, None, None, None, None, None
+        return (_close_pooled(ctx, ss, g_x1), g_x2, g_w, g_bias) + (None,) * 8
 
 
 class _FusedPointwise(_PlainAttrs, nn.Module):
@@ -820,75 +941,51 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
         if _ops.PACK_REGISTRY and mode != "f32" and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous():
             # one launch refreshes every stale pack of the step (forward and transposed, all layers): sonet_hip.ops.packs
             return _ops.packs.get(self._weight2d(), ("fwd", mode))
-        key = (w._version, w.data_ptr(), w.device, mode)
-        if getattr(self, '_wp_key', None) != key:
-            with torch.no_grad():
-                self._wp = _ops.pointmlp_pack(self._weight2d().detach().contiguous().float(), mode)
-            self._wp_key = key
-        return self._wp
+        return _per_version(self, '_wp', w, (mode,), lambda: _ops.pointmlp_pack(self._weight2d().detach().contiguous().float(), mode))
 
     def _packed_rotated(self, lead):
         """h3 (or bf16) pack of the weight with its first ``lead`` input channels moved behind the others: a caller that feeds
         cat(a, b) with a narrow ``a`` (3 coordinate rows) passes (b, a) as (x1, x2) instead, so that x1 is 16-aligned."""
         w = self.conv.weight
         mode = "bf16" if _ops.POINTMLP_PRECISION == "bf16" else "h3"
-        key = (w._version, w.data_ptr(), w.device, lead, mode)
-        if getattr(self, '_wpr_key', None) != key:
-            with torch.no_grad():
-                w2 = self._weight2d().detach().float()
-                self._wpr = _ops.pointmlp_pack(torch.cat((w2[:, lead:], w2[:, :lead]), dim=1).contiguous(), mode)
-            self._wpr_key = key
-        return self._wpr
+        def build():
+            w2 = self._weight2d().detach().float()
+            return _ops.pointmlp_pack(torch.cat((w2[:, lead:], w2[:, :lead]), dim=1).contiguous(), mode)
+        return _per_version(self, '_wpr', w, (lead, mode), build)
 
     def _packed_split(self, lead):
         """(h3 or bf16 pack of W[:, lead:], W[:, :lead] as a contiguous Cout x lead f32 matrix): the layer is linear, so a caller
         whose input is cat(a, gather(b)) applies the wide block to b ONCE per node and adds the narrow block per column."""
         w = self.conv.weight
         mode = "bf16" if _ops.POINTMLP_PRECISION == "bf16" else "h3"
-        key = (w._version, w.data_ptr(), w.device, lead, mode)
-        if getattr(self, '_wps_key', None) != key:
-            with torch.no_grad():
-                w2 = self._weight2d().detach().float()
-                self._wps = (_ops.pointmlp_pack(w2[:, lead:].contiguous(), mode), w2[:, :lead].contiguous())
-            self._wps_key = key
-        return self._wps
+        def build():
+            w2 = self._weight2d().detach().float()
+            return _ops.pointmlp_pack(w2[:, lead:].contiguous(), mode), w2[:, :lead].contiguous()
+        return _per_version(self, '_wps', w, (lead, mode), build)
 
     def _direct_ok(self, x):
         """Eval-mode, no-grad, h3 / bf16: the caller may launch the kernel itself with this layer's pack and folded affine."""
         return (_ops.GATHER_NODE_STAGE and _ops.POINTMLP_PRECISION in ("h3", "bf16") and not torch.is_grad_enabled() and x.is_cuda
                 and (_ops.POINTMLP_PRECISION != "h3" or self._h3_ok())
                 and x.dtype in (torch.float32, torch.bfloat16) and self._fusable() and self.conv.out_channels % 32 == 0
-                and self.normalization in (None, 'batch') and not (self.normalization == 'batch' and self.norm.training)
-                and self.activation in (None, 'relu'))
+                and _eval_norm_act(self))
 
     def _packed_p16(self, make=None, tag=None):
         """h3p pack (third-generation layer, P16 operands) of this layer's weight -- or of ``make()``, a column selection of it the
         caller keeps apart under ``tag`` (the segmenter's per-point block of layer 1; built only when the weight has changed)."""
-        w = self.conv.weight
-        key = (w._version, w.data_ptr(), w.device, tag)
-        cache = self.__dict__.setdefault('_wp16', {})
-        if cache.get(tag, (None, None))[0] != key:
-            with torch.no_grad():
-                src = self._weight2d().detach() if make is None else make()
-                cache[tag] = (key, _ops.pointmlp_h3p_pack(src.contiguous().float()))
-        return cache[tag][1]
+        def build():
+            src = self._weight2d().detach() if make is None else make()
+            return _ops.pointmlp_h3p_pack(src.contiguous().float())
+        return _per_version(self, '_wp16' if tag is None else '_wp16_' + tag, self.conv.weight, (), build)
 
     def _lead_cols(self, lead):
         """W[:, :lead] as a contiguous Cout x lead f32 matrix (the coordinate channels of KNNModule's first layer), cached per weight version."""
-        w = self.conv.weight
-        key = (w._version, w.data_ptr(), w.device, lead)
-        if getattr(self, '_wlead_key', None) != key:
-            with torch.no_grad():
-                self._wlead = self._weight2d().detach()[:, :lead].float().contiguous()
-            self._wlead_key = key
-        return self._wlead
+        return _per_version(self, '_wlead', self.conv.weight, (lead,), lambda: self._weight2d().detach()[:, :lead].float().contiguous())
 
     def _p16_ok(self):
         """Eval-mode, no-grad, h3: this layer can run on pre-split (P16) operands and hand its output on in that form."""
         return (_ops.POINTMLP_PRECISION == "h3" and _ops.P16_CHAINS and not torch.is_grad_enabled() and self.conv.weight.is_cuda
-                and self._h3_ok() and self._fusable() and self.conv.out_channels % 32 == 0
-                and self.normalization in (None, 'batch') and not (self.normalization == 'batch' and self.norm.training)
-                and self.activation in (None, 'relu'))
+                and self._h3_ok() and self._fusable() and self.conv.out_channels % 32 == 0 and _eval_norm_act(self))
 
     def run_p16(self, x, x2=None, out="p16", **kw):
         """The layer on P16 operands (``sonet_hip.ops.P16``; f32 tensors are converted first): out "p16" | "f32" | "both".
@@ -907,21 +1004,7 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
 
     def _eval_affine(self):
         """(scale, shift) folding the conv bias and the eval-mode BatchNorm (running statistics)."""
-        bn = self.norm if self.normalization == 'batch' else None
-        ts = [self.conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (self.conv.weight.device, getattr(bn, 'stats_gen', 0))
-        if getattr(self, '_affine_key', None) != key:
-            with torch.no_grad():
-                b = self._bias().detach().float()
-                if bn is None:
-                    scale, shift = _ops.const_vec(b.numel(), 1.0, b.device), b.clone()      # the shared ones vector marks a unit scale
-                else:
-                    scale = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-                    shift = (b - bn.running_mean) * scale + bn.bias.detach()
-                self._affine = (scale.contiguous(), shift.contiguous())
-            self._affine_key = key
-            self._affine_gen = getattr(self, '_affine_gen', 0) + 1          # (id() of the tensors can be recycled: count instead)
-        return self._affine
+        return _folded_affine(self, self.conv.weight, self.conv.bias, True)
 
     def _run(self, x1, x2, epoch, xaff=None, defer=False, carry=None):
         """x1 (and optional x2): B x C x L contiguous f32 CUDA tensors -> B x Cout x L.
@@ -939,7 +1022,7 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
                                                   or self.conv.weight.requires_grad)
         fuse_act = relu_fused and (norm in (None, 'batch'))
         wp = self._packed(x1.shape[1], x2.shape[1] if x2 is not None else 0)
-        want = torch.bfloat16 if wp.dtype == torch.int16 else torch.float32     # the pack decides the kernel, the kernel the storage type
+        want = _storage_dtype(wp)
         if x1.dtype != want:
             x1 = x1.to(want)
         if x2 is not None and x2.dtype != want:
@@ -959,26 +1042,13 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
             xaff = None
         if train_bn:
             n = x1.shape[0] * x1.shape[2]
-            m = bn.momentum
-            # F.batch_norm's running-statistics update rides on the statistics launch of the forward (``ops.bn_rider``) when the buffers allow
-            ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
-                    and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x1.device)
+            rides = _bn_run(bn, n, x1.device)
             outs = _PointwiseFn.apply(x1, x2, self._weight2d(), self._bias(), bn.weight, bn.bias, wp, None, None,
-                                      fuse_act, 'batch', bn.eps, (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None,
-                                      xaff, bool(defer), carry)
+                                      fuse_act, 'batch', bn.eps, rides, xaff, bool(defer), carry)
             y, mean, var = outs[:3]
             if defer:
                 y = (y, outs[3], outs[4])
-            with torch.no_grad():                                       # F.batch_norm running-stat update
-                if ride:
-                    pass
-                elif bn.running_mean is not None and m is not None:
-                    bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
-                    bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
-                # the kernel writes the buffers through raw pointers: their _version does not move, so the folded eval
-                # affine (keyed on versions) must be dropped by hand -- or a later eval() would run on stale statistics
-                self._affine_key = None
-                # (F.batch_norm does not touch num_batches_tracked; the reference never increments it)
+            _bn_ran(bn, self, rides, n, mean, var)
         else:
             if norm in (None, 'batch'):
                 scale, shift = self._eval_affine()
@@ -991,6 +1061,14 @@ class _FusedPointwise(_PlainAttrs, nn.Module):
             else:
                 y = _ops.pointmlp(x1, wp, scale, shift, fuse_act, self.conv.out_channels, x2=x2)
         return y, fuse_act
+
+    def _finish(self, y, act_done):
+        """What the launch did not hold: another norm than BatchNorm, another activation than ReLU (aten, outside the hot path)."""
+        if self.normalization is not None and self.normalization != 'batch':
+            y = self.norm(y)
+        if self.activation is not None and not act_done:
+            y = self.act(y)
+        return y
 
     @staticmethod
     def _prep(x):
@@ -1011,14 +1089,7 @@ class EquivariantLayer(_FusedPointwise):
         self.activation = activation
         self.normalization = normalization
         self.conv = nn.Conv1d(num_in_channels, num_out_channels, kernel_size=1, stride=1, padding=0)
-        if normalization == 'batch':
-            self.norm = MyBatchNorm1d(num_out_channels, momentum=momentum, affine=True,
-                                      momentum_decay_step=bn_momentum_decay_step, momentum_decay=bn_momentum_decay)
-        elif normalization == 'instance':
-            self.norm = nn.InstanceNorm1d(num_out_channels, momentum=momentum, affine=True)
-        act = _make_act(activation)
-        if act is not None:
-            self.act = act
+        _init_norm_act(self, num_out_channels, MyBatchNorm1d, nn.InstanceNorm1d, momentum, bn_momentum_decay_step, bn_momentum_decay)
         self.weight_init()
 
     def weight_init(self):
@@ -1026,9 +1097,7 @@ class EquivariantLayer(_FusedPointwise):
         self.conv.weight.data.normal_(0, math.sqrt(2. / n))             # models/layers.py:271-275
         if self.conv.bias is not None:
             self.conv.bias.data.fill_(0)
-        if self.normalization in ('batch', 'instance'):
-            self.norm.weight.data.fill_(1)
-            self.norm.bias.data.zero_()
+        _init_norm(self)
 
     def forward(self, x, epoch=None, x_skip=None):
         """x: B x Cin x L.  ``x_skip`` (optional, B x C_skip x L, C_skip % 8 == 0) goes first in the channel
@@ -1037,11 +1106,7 @@ class EquivariantLayer(_FusedPointwise):
             y, act_done = self._run(self._prep(x_skip), self._prep(x), epoch)
         else:
             y, act_done = self._run(self._prep(x), None, epoch)
-        if self.normalization is not None and self.normalization != 'batch':
-            y = self.norm(y)
-        if self.activation is not None and not act_done:
-            y = self.act(y)
-        return y
+        return self._finish(y, act_done)
 
 
 class _FcFn(torch.autograd.Function):
@@ -1092,50 +1157,26 @@ class MyLinear(_PlainAttrs, nn.Module):
         self.activation = activation
         self.normalization = normalization
         self.linear = nn.Linear(in_features, out_features, bias=True)
-        if normalization == 'batch':
-            self.norm = MyBatchNorm1d(out_features, momentum=momentum, affine=True,
-                                      momentum_decay_step=bn_momentum_decay_step, momentum_decay=bn_momentum_decay)
-        elif normalization == 'instance':
-            self.norm = nn.InstanceNorm1d(out_features, momentum=momentum, affine=True)
-        act = _make_act(activation)
-        if act is not None:
-            self.act = act
+        _init_norm_act(self, out_features, MyBatchNorm1d, nn.InstanceNorm1d, momentum, bn_momentum_decay_step, bn_momentum_decay)
         self.weight_init()
 
     def weight_init(self):
         self.linear.weight.data.normal_(0, math.sqrt(2. / self.linear.in_features))
         if self.linear.bias is not None:
             self.linear.bias.data.fill_(0)
-        if self.normalization in ('batch', 'instance'):
-            self.norm.weight.data.fill_(1)
-            self.norm.bias.data.zero_()
+        _init_norm(self)
 
     def _eval_affine(self):
         """(scale, shift) folding the bias and the eval-mode BatchNorm1d into the matrix product."""
-        bn = self.norm if self.normalization == 'batch' else None
-        ts = [self.linear.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
-        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in ts) + (getattr(bn, 'stats_gen', 0),)
-        if getattr(self, '_affine_key', None) != key:
-            with torch.no_grad():
-                b = self.linear.bias.detach().float() if self.linear.bias is not None else torch.zeros(self.linear.out_features, device=self.linear.weight.device)
-                if bn is None:
-                    scale, shift = torch.ones_like(b), b.clone()
-                else:
-                    scale = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
-                    shift = (b - bn.running_mean) * scale + bn.bias.detach()
-                self._affine = (scale.contiguous(), shift.contiguous())
-            self._affine_key = key
-        return self._affine
+        return _folded_affine(self, self.linear.weight, self.linear.bias, False)
 
     def forward(self, x, epoch=None):
-        fast = (not torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
-                and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
-                and not (self.normalization == 'batch' and self.norm.training))
+        fast = not torch.is_grad_enabled() and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and _eval_norm_act(self)
         if fast:                                         # eval / no-grad: Linear + BN + ReLU as one kernel
             scale, shift = self._eval_affine()
             return _ops.linear_act(x.contiguous(), self.linear.weight.detach().contiguous(), scale, shift, self.activation == 'relu')
         bn = self.norm if self.normalization == 'batch' else None
-        if (torch.is_grad_enabled() and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
+        if (torch.is_grad_enabled() and _plain_norm_act(self)
                 and (bn is None or (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None))
                 and _ops.fc_head_ok(x, self.linear.weight) and (bn is None or x.shape[0] >= 2)):
             # training: Linear + BatchNorm1d (batch statistics) + ReLU in one launch, two for the backward
@@ -1160,14 +1201,7 @@ class MyConv2d(_FusedPointwise):
         self.activation = activation
         self.normalization = normalization
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=bias)
-        if normalization == 'batch':
-            self.norm = MyBatchNorm2d(out_channels, momentum=momentum, affine=True,
-                                      momentum_decay_step=bn_momentum_decay_step, momentum_decay=bn_momentum_decay)
-        elif normalization == 'instance':
-            self.norm = nn.InstanceNorm2d(out_channels, momentum=momentum, affine=True)
-        act = _make_act(activation)
-        if act is not None:
-            self.act = act
+        _init_norm_act(self, out_channels, MyBatchNorm2d, nn.InstanceNorm2d, momentum, bn_momentum_decay_step, bn_momentum_decay)
         self.weight_init()
 
     def weight_init(self):
@@ -1175,9 +1209,7 @@ class MyConv2d(_FusedPointwise):
         self.conv.weight.data.normal_(0, math.sqrt(2. / (ks[0] * ks[1] * self.conv.in_channels)))
         if self.conv.bias is not None:
             self.conv.bias.data.fill_(0)
-        if self.normalization in ('batch', 'instance'):
-            self.norm.weight.data.fill_(1)
-            self.norm.bias.data.zero_()
+        _init_norm(self)
 
     def forward(self, x, epoch=None):
         if self._fusable() and x.is_cuda:
@@ -1190,11 +1222,7 @@ class MyConv2d(_FusedPointwise):
             y, act_done = self.conv(x), False
             if self.normalization == 'batch':
                 y = self.norm(y, epoch)
-        if self.normalization is not None and self.normalization != 'batch':
-            y = self.norm(y)
-        if self.activation is not None and not act_done:
-            y = self.act(y)
-        return y
+        return self._finish(y, act_done)
 
 
 class _UpConvTrainFn(torch.autograd.Function):
@@ -1215,8 +1243,7 @@ class _UpConvTrainFn(torch.autograd.Function):
         ctx.relu, ctx.bn, ctx.fused_wgrad = bool(relu), gamma is not None, bool(fused_wgrad)
         if ctx.bn:
             raw = _ops.upconv3x3(x, wp, ones, b_, False, Cout)
-            rm, rv, mom, unb = bn_run if bn_run is not None else (None, None, 0.0, 1.0)
-            invstd, sc, sh = _ops.bn_rider(gamma, beta, eps, rm, rv, mom, unb)
+            invstd, sc, sh = _rider(gamma, beta, eps, bn_run)
             raw3 = raw.view(B, Cout, 4 * H * W)
             mean, var = _ops.channel_stats(raw3)
             y = _ops.channel_affine_act(raw3, sc, sh, relu).view(B, Cout, 2 * H, 2 * W)
@@ -1246,8 +1273,7 @@ class _UpConvTrainFn(torch.autograd.Function):
         if ctx.bn:
             sc, sh, raw, mean, invstd, gamma = saved[3:9]
             raw3 = raw.view(B, Cout, 4 * H * W)
-            sums = _ops.pointwise_bwd_stats(gy3, raw3, sc, sh, ctx.relu, want_sums=True)
-            a, b, c0, g_gamma, g_beta = _ops.bn_bwd_coeffs(sums, mean, invstd, gamma, float(B * 4 * H * W))
+            a, b, c0, g_gamma, g_beta = _bn_bwd_head(gy3, raw3, sc, sh, ctx.relu, mean, invstd, gamma)
             g_raw3 = _ops.pointwise_bwd_apply(gy3, raw3, sc, sh, ctx.relu, a, b, c0)
         elif ctx.relu:
             y3 = saved[3].view(B, Cout, 4 * H * W)                           # mask source: y > 0 <=> pre-activation > 0
@@ -1313,37 +1339,26 @@ class UpConv(nn.Module):
     def _fused_ok(self, x):
         conv = self.conv.conv
         return (self.fused and not self.training and _ops.POINTMLP_PRECISION == "h3" and x.dim() == 4 and x.is_cuda
-                and x.dtype == torch.float32 and not x.requires_grad and _ops.is_inference(x)
-                and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
+                and x.dtype == torch.float32 and not x.requires_grad and _ops.is_inference(x) and _plain_norm_act(self)
                 and conv.weight.is_cuda and conv.weight.dtype == torch.float32
                 and _ops.upconv3x3_supported(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]))
 
     def _packed_upconv(self):
         """The up-convolution pack of the 3x3 weight, rebuilt when the weight's version counter (or storage) has moved."""
         w = self.conv.conv.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if getattr(self, '_wup_key', None) != key:
-            with torch.no_grad():
-                self._wup = _ops.upconv3x3_pack(w.detach().contiguous())
-            self._wup_key = key
-        return self._wup
+        return _per_version(self, '_wup', w, (), lambda: _ops.upconv3x3_pack(w.detach().contiguous()))
 
     def _fused_train_ok(self, x):
         conv = self.conv.conv
         return (self.fused_train and self.training and _ops.POINTMLP_PRECISION == "h3" and x.dim() == 4 and x.is_cuda
-                and x.dtype == torch.float32 and self.normalization in (None, 'batch') and self.activation in (None, 'relu')
+                and x.dtype == torch.float32 and _plain_norm_act(self)
                 and conv.weight.is_cuda and conv.weight.dtype == torch.float32
                 and _ops.upconv3x3_supported(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]))
 
     def _packed_upconv_dgrad(self):
         """The input gradient's pack of the 3x3 weight (transposed folded weights), cached like ``_packed_upconv``."""
         w = self.conv.conv.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if getattr(self, '_wupt_key', None) != key:
-            with torch.no_grad():
-                self._wupt = _ops.upconv3x3_dgrad_pack(w.detach().contiguous())
-            self._wupt_key = key
-        return self._wupt
+        return _per_version(self, '_wupt', w, (), lambda: _ops.upconv3x3_dgrad_pack(w.detach().contiguous()))
 
     def _forward_train(self, x):
         conv, relu = self.conv, self.activation == 'relu'
@@ -1354,17 +1369,10 @@ class UpConv(nn.Module):
             return _UpConvTrainFn.apply(x, w, conv._bias(), None, None, self._packed_upconv(), wpt, relu, 0.0, None, bool(self.fused_wgrad))
         bn = conv.norm
         n = x.shape[0] * 4 * x.shape[2] * x.shape[3]
-        m = bn.momentum
-        ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
-                and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device)
-        y, mean, var = _UpConvTrainFn.apply(x, w, conv._bias(), bn.weight, bn.bias, self._packed_upconv(), wpt, relu, bn.eps,
-                                            (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None,
+        rides = _bn_run(bn, n, x.device)
+        y, mean, var = _UpConvTrainFn.apply(x, w, conv._bias(), bn.weight, bn.bias, self._packed_upconv(), wpt, relu, bn.eps, rides,
                                             bool(self.fused_wgrad))
-        with torch.no_grad():
-            if not ride and bn.running_mean is not None and m is not None:
-                bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
-                bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
-            conv._affine_key = None                        # (the buffers moved through raw pointers: drop the folded eval affine)
+        _bn_ran(bn, conv, rides, n, mean, var)
         return y
 
     def forward(self, x):
@@ -1539,6 +1547,26 @@ class PointResNet(nn.Module):
             self._fused_akey = akey
         return self._fused_w, self._fused_aff
 
+    def _pooled_layout_ok(self):
+        """What ``_PooledLastLayerFn`` needs of the stack: hidden layers, a norm-free, activation-free fusable last layer, and a first
+        width the kernels take as a panel of its own."""
+        n = len(self.out_channels_list)
+        last = self.layers[n - 1]
+        return (n >= 3 and last.normalization is None and last.activation is None and last._fusable()
+                and self.out_channels_list[0] % 16 == 0)
+
+    def _hidden_train_ok(self, lay):
+        """A hidden layer that can hand its RAW output on: training-mode BatchNorm + ReLU on the fused kernel."""
+        return lay.normalization == 'batch' and lay.norm.training and lay.activation == 'relu' and lay._fusable()
+
+    def _hidden(self, x, epoch):
+        """The hidden layers as usual -> (first layer's output, last hidden layer's output): the two panels of the last layer."""
+        skip = self.layers[0](x, epoch)
+        t = skip
+        for l in range(1, len(self.out_channels_list) - 1):
+            t = self.layers[l](t, epoch)
+        return skip, t
+
     def pooled_sorted_ok(self, x, M):
         """Training, f32-class arithmetic, nobody reads first_pn_out: the hidden layers may run on NODE-SORTED columns and the last layer
         pool its own output (``sonet_pointmlp_h3_segpool_f32``).  Decided before any layer runs."""
@@ -1546,10 +1574,10 @@ class PointResNet(nn.Module):
         last = self.layers[n - 1]
         if not (_ops.POINTMLP_PRECISION == "h3" and _ops.POOLED_TRAIN_EPILOGUE and _ops.H3_SEGPOOL and x.is_cuda and x.dtype == torch.float32):
             return False
-        if n < 3 or last.normalization is not None or last.activation is not None or not last._fusable():
+        if not self._pooled_layout_ok():
             return False
         c0, ck = self.out_channels_list[0], self.out_channels_list[n - 2]
-        if c0 % 16 != 0 or last.conv.out_channels % 32 != 0 or not 0 < M <= 1024:
+        if last.conv.out_channels % 32 != 0 or not 0 < M <= 1024:
             return False
         # the pack the layer would pick: h3 (the weight side of the range guard may send it to x3: store + index_max then)
         return _ops.x3_supported(c0, ck, last.conv.out_channels) and last._h3_ok()
@@ -1562,7 +1590,7 @@ class PointResNet(nn.Module):
             return False
         for l in range(n - 1):
             lay = self.layers[l]
-            if not (lay.normalization == 'batch' and lay.norm.training and lay.activation == 'relu' and lay._fusable()):
+            if not self._hidden_train_ok(lay):
                 return False
             if l >= 1 and not (lay._h3_ok() and _ops.xaff_ok(lay.conv.in_channels, 0, lay.conv.out_channels)
                                and x.shape[0] * x.shape[2] * lay.conv.out_channels * 4 >= (32 << 20)):
@@ -1581,7 +1609,7 @@ class PointResNet(nn.Module):
         B, _, L = x.shape
         for l in range(n - 1):
             lay = self.layers[l]
-            if not (lay.normalization == 'batch' and lay.norm.training and lay.activation == 'relu' and lay._fusable()):
+            if not self._hidden_train_ok(lay):
                 return False
             if l >= 1 and not _ops.bf16_xaff_ok(B, lay.conv.in_channels, 0, lay.conv.out_channels, L):
                 return False
@@ -1597,13 +1625,12 @@ class PointResNet(nn.Module):
         first element is None -- the tensor is never written."""
         n = len(self.out_channels_list)
         last = self.layers[n - 1]
-        if n < 3 or last.normalization is not None or last.activation is not None or not last._fusable():
+        if not self._pooled_layout_ok():                                 # decided BEFORE any layer runs (training BN must not run twice)
             return None
-        if self.out_channels_list[0] % 16 != 0:                          # decided BEFORE any layer runs (training BN must not run twice)
-            return None
-        if pos0 is not None and self.norm_on_load_ok(x):
-            # the normalised activations of the hidden layers are never written: every consumer (next layer, weight gradients, the pooled
-            # last layer and its sparse weight gradient) normalises on load
+        # the normalised activations of the hidden layers are never written: every consumer (next layer, weight gradients, the pooled last
+        # layer and its sparse weight gradient) normalises on load -- f32-class on NODE-SORTED columns (pos0), bf16 in the original order
+        # when nobody reads first_pn_out (the pool is the last layer's epilogue, round 6)
+        if (self.norm_on_load_ok(x) if pos0 is not None else (not need_dense and self.bf16_norm_on_load_ok(x, M))):
             h, _ = self.layers[0]._run(_FusedPointwise._prep(x), None, epoch, defer=True)
             skip = h
             # the first layer's output feeds the second layer and the last one: the last layer's input gradient (computed first) is added
@@ -1612,32 +1639,16 @@ class PointResNet(nn.Module):
             for l in range(1, n - 1):
                 h, _ = self.layers[l]._run(h[0], None, epoch, xaff=(h[1], h[2], True), defer=True, carry=carry if l == 1 else None)
             wp = last._packed(skip[0].shape[1], h[0].shape[1])
-            if wp.dtype == torch.int8:
+            if (wp.dtype == torch.int8 if pos0 is not None
+                    else (wp.dtype == torch.int16 and _ops.pointmlp_bf16_pool_ok(skip[0], h[0], last.conv.out_channels, M))):
                 return _PooledLastLayerFn.apply(skip[0], h[0], last._weight2d(), last._bias(), wp, min_idx_i32, row_max, M, False, pos0,
                                                 (skip[1], skip[2], True, h[1], h[2], True), carry)
+            # (the weight side of the range guard changed the pack between the check and here: the activations are written out after all)
             skip, t = _Materialise.apply(skip[0], skip[1], skip[2], True), _Materialise.apply(h[0], h[1], h[2], True)
             return _PooledLastLayerFn.apply(skip.contiguous(), t.contiguous(), last._weight2d(), last._bias(), wp, min_idx_i32, row_max, M,
                                             bool(need_dense), pos0, None, carry)
-        elif pos0 is None and not need_dense and self.bf16_norm_on_load_ok(x, M):
-            # bf16: the same data flow in the original column order (round 6) -- the three normalise + ReLU passes over B x C x kN are gone
-            h, _ = self.layers[0]._run(_FusedPointwise._prep(x), None, epoch, defer=True)
-            skip = h
-            carry = _GradCarry() if (_ops.GRAD_CARRY and _ops._graph_task_id is not None and torch.is_grad_enabled() and skip[0].requires_grad) else None
-            for l in range(1, n - 1):
-                h, _ = self.layers[l]._run(h[0], None, epoch, xaff=(h[1], h[2], True), defer=True, carry=carry if l == 1 else None)
-            wp = last._packed(skip[0].shape[1], h[0].shape[1])
-            if wp.dtype == torch.int16 and _ops.pointmlp_bf16_pool_ok(skip[0], h[0], last.conv.out_channels, M):
-                return _PooledLastLayerFn.apply(skip[0], h[0], last._weight2d(), last._bias(), wp, min_idx_i32, row_max, M, False, None,
-                                                (skip[1], skip[2], True, h[1], h[2], True), carry)
-            skip, t = _Materialise.apply(skip[0], skip[1], skip[2], True), _Materialise.apply(h[0], h[1], h[2], True)
-            return _PooledLastLayerFn.apply(skip.contiguous(), t.contiguous(), last._weight2d(), last._bias(), wp, min_idx_i32, row_max, M,
-                                            bool(need_dense), None, None, carry)
-        else:
-            skip = self.layers[0](x, epoch)
-            t = skip
-            for l in range(1, n - 1):
-                t = self.layers[l](t, epoch)
-            wp = last._packed(skip.shape[1], t.shape[1])
+        skip, t = self._hidden(x, epoch)
+        wp = last._packed(skip.shape[1], t.shape[1])
         return _PooledLastLayerFn.apply(skip.contiguous(), t.contiguous(), last._weight2d(), last._bias(), wp, min_idx_i32, row_max, M, bool(need_dense), pos0)
 
     def forward(self, x, epoch=None):
@@ -1653,10 +1664,7 @@ class PointResNet(nn.Module):
                 return y                                   # (None when only the planes were written)
             return _ops.pointresnet_fused(_FusedPointwise._prep(x).float(), wstream, affine)
         n = len(self.out_channels_list)
-        skip = self.layers[0](x, epoch)
-        t = skip
-        for l in range(1, n - 1):
-            t = self.layers[l](t, epoch)
+        skip, t = self._hidden(x, epoch)
         if skip.shape[1] % 8 == 0:
             return self.layers[n - 1](t, epoch, x_skip=skip)              # fused concat (skip first)
         return self.layers[n - 1](torch.cat((skip, t), dim=1), epoch)

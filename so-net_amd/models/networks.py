@@ -30,7 +30,8 @@ import torch.nn as nn
 
 from sonet_hip import ops as _ops
 from util import som
-from .layers import EquivariantLayer, KNNModule, MyLinear, PointNet, PointResNet, _NodewiseLayerFn, _PlainAttrs  # noqa: F401
+from .layers import (EquivariantLayer, KNNModule, MyLinear, PointNet, PointResNet, _NodewiseLayerFn, _PlainAttrs,  # noqa: F401
+                     _bn_ran, _bn_run, _per_version, _storage_dtype)
 
 
 def _head_inference(fn):
@@ -541,20 +542,17 @@ class Segmenter(_PlainAttrs, nn.Module):
         return o
 
     def _layer1_split(self):
-        lyr = self.layer1
-        w = lyr.conv.weight
-        key = (w._version, w.data_ptr(), w.device, _ops.POINTMLP_PRECISION)
-        if getattr(self, "_l1_key", None) != key:
-            with torch.no_grad():
-                W = w.detach().reshape(w.shape[0], w.shape[1]).float()
-                blk = self._layer1_blocks()
-                cols = lambda names: torch.cat([W[:, blk[n][0]:blk[n][1]] for n in names], dim=1).contiguous()
-                mode = _ops.POINTMLP_PRECISION
-                self._l1_wp_point = _ops.pointmlp_pack(cols(["first", "x_dec", "x", "sn"]), mode)      # x1 = first_pn_out (384), x2 = small
-                self._l1_wp_node = _ops.pointmlp_pack(cols(["centers", "fm_first", "fm_knn", "fm_final"]), mode)
-                self._l1_w_glob = cols(["onehot", "feature"])
-            self._l1_key = key
-        return self._l1_wp_point, self._l1_wp_node, self._l1_w_glob
+        w = self.layer1.conv.weight
+        mode = _ops.POINTMLP_PRECISION
+
+        def build():
+            W = w.detach().reshape(w.shape[0], w.shape[1]).float()
+            blk = self._layer1_blocks()
+            cols = lambda names: torch.cat([W[:, blk[n][0]:blk[n][1]] for n in names], dim=1).contiguous()
+            return (_ops.pointmlp_pack(cols(["first", "x_dec", "x", "sn"]), mode),                   # x1 = first_pn_out (384), x2 = small
+                    _ops.pointmlp_pack(cols(["centers", "fm_first", "fm_knn", "fm_final"]), mode),
+                    cols(["onehot", "feature"]))
+        return _per_version(self, "_l1", w, (mode,), build)
 
     def forward_nodewise(self, x_decentered, x, sn, label, first_pn_out, som_node, masked_max, knn_feature_1, final_pn_out, feature,
                          min_idx_i32, first_pn_out_p16=None):
@@ -572,7 +570,7 @@ class Segmenter(_PlainAttrs, nn.Module):
         zg = torch.cat([onehot, feature.float()], dim=1) @ w_glob.t()               # B x Cout: per-cloud block
         # the pack decides the kernel and the kernel the storage type: a bf16 pack (precision "bf16") takes bfloat16 operands --
         # the node-level maps arrive as a mix of f32 (som_node, pooled maxima) and bf16 tensors there
-        sdt = torch.bfloat16 if wp_point.dtype == torch.int16 else torch.float32
+        sdt = _storage_dtype(wp_point)
         zn = _ops.pointmlp(torch.cat([t_.to(sdt) for t_ in node_in], dim=1).contiguous(), wp_node, ones, zeros, False, Cout)
         z = (zn.float() + zg.unsqueeze(2)).contiguous()
         x2 = torch.cat(small, dim=1).to(sdt).contiguous()
@@ -610,28 +608,25 @@ class Segmenter(_PlainAttrs, nn.Module):
         """Per weight version: (h3 pack of W_p, h3 pack of W_n, W_g, transposed x3 packs of W's ``first`` and node-map columns, the
         column ranges of every block in W)."""
         lyr = self.layer1
-        w = lyr.conv.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if getattr(self, "_l1t_key", None) != key:
-            with torch.no_grad():
-                W = lyr._weight2d().detach()
-                blk = self._layer1_blocks()
-                cols = lambda names: torch.cat([W[:, blk[n][0]:blk[n][1]] for n in names], dim=1).contiguous()
-                small = [n for n in ("x_dec", "x", "sn") if blk[n][1] > blk[n][0]]
-                maps = (blk["fm_first"][0], blk["fm_final"][1])               # fm_first | fm_knn | fm_final: adjacent in W
-                assert blk["fm_first"][1] == blk["fm_knn"][0] and blk["fm_knn"][1] == blk["fm_final"][0]
-                c_first, c_maps = blk["first"][1] - blk["first"][0], maps[1] - maps[0]
-                ranges = (blk["first"], tuple(blk[n] for n in small), blk["centers"], maps, blk["onehot"], blk["feature"])
-                covered = sum(hi - lo for lo, hi in (ranges[0],) + ranges[1] + ranges[2:])
-                assert covered == W.shape[1], (covered, W.shape[1])
-                self._l1t = (_ops.pointmlp_pack(cols(["first"] + small), "h3"),
-                             _ops.pointmlp_pack(cols(["centers", "fm_first", "fm_knn", "fm_final"]), "h3"),
-                             cols(["onehot", "feature"]),
-                             (_ops.pointmlp_pack_transposed(W, blk["first"][0], c_first, c_first, "x3"), c_first, c_first),
-                             (_ops.pointmlp_pack_transposed(W, maps[0], c_maps, c_maps, "x3"), c_maps, c_maps),
-                             ranges)
-            self._l1t_key = key
-        return self._l1t
+
+        def build():
+            W = lyr._weight2d().detach()
+            blk = self._layer1_blocks()
+            cols = lambda names: torch.cat([W[:, blk[n][0]:blk[n][1]] for n in names], dim=1).contiguous()
+            small = [n for n in ("x_dec", "x", "sn") if blk[n][1] > blk[n][0]]
+            maps = (blk["fm_first"][0], blk["fm_final"][1])               # fm_first | fm_knn | fm_final: adjacent in W
+            assert blk["fm_first"][1] == blk["fm_knn"][0] and blk["fm_knn"][1] == blk["fm_final"][0]
+            c_first, c_maps = blk["first"][1] - blk["first"][0], maps[1] - maps[0]
+            ranges = (blk["first"], tuple(blk[n] for n in small), blk["centers"], maps, blk["onehot"], blk["feature"])
+            covered = sum(hi - lo for lo, hi in (ranges[0],) + ranges[1] + ranges[2:])
+            assert covered == W.shape[1], (covered, W.shape[1])
+            return (_ops.pointmlp_pack(cols(["first"] + small), "h3"),
+                    _ops.pointmlp_pack(cols(["centers", "fm_first", "fm_knn", "fm_final"]), "h3"),
+                    cols(["onehot", "feature"]),
+                    (_ops.pointmlp_pack_transposed(W, blk["first"][0], c_first, c_first, "x3"), c_first, c_first),
+                    (_ops.pointmlp_pack_transposed(W, maps[0], c_maps, c_maps, "x3"), c_maps, c_maps),
+                    ranges)
+        return _per_version(self, "_l1t", lyr.conv.weight, (), build)
 
     def _nodewise_train_ok(self):
         """``opt.seg_nodewise_train`` and everything the split training path needs: autograd on, train mode, h3 arithmetic (the weight
@@ -655,18 +650,12 @@ class Segmenter(_PlainAttrs, nn.Module):
         onehot = torch.zeros(B, 16, dtype=torch.float32, device=x.device)
         onehot.scatter_(1, label.unsqueeze(1), 1)
         n = B * k * N
-        m = bn.momentum
-        ride = (bn.track_running_stats and m is not None and bn.running_mean is not None and bn.running_mean.is_contiguous()
-                and bn.running_var.is_contiguous() and bn.running_mean.dtype == torch.float32 and bn.running_mean.device == x.device)
+        rides = _bn_run(bn, n, x.device)
         h, mean, var = _NodewiseLayerFn.apply(lyr._prep(first_pn_out).float(), x2, som_node.detach().float(), maps.contiguous(), onehot,
                                               feature.float(), lyr._weight2d(), lyr._bias(), bn.weight, bn.bias, min_idx_i32.contiguous(),
                                               self._layer1_split_train(), lyr.activation == 'relu', bn.eps,
-                                              (bn.running_mean, bn.running_var, m, n / max(n - 1, 1)) if ride else None)
-        with torch.no_grad():                                           # F.batch_norm's running-statistics update (as _FusedPointwise._run)
-            if not ride and bn.running_mean is not None and m is not None:
-                bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
-                bn.running_var.mul_(1 - m).add_(var * (n / max(n - 1, 1)), alpha=m)
-            lyr._affine_key = None
+                                              rides)
+        _bn_ran(bn, lyr, rides, n, mean, var)
         return self._tail(self.layer3(self.layer2(h)), k)
 
     def _tail(self, h, k):
