@@ -69,6 +69,9 @@ __device__ __forceinline__ i32x4_t raw_buffer_sgpr(const void *base, unsigned by
 // ---- f32 / bf16 storage by overload (uint16_t = bfloat16 bits): values widened on the load, arithmetic in f32 ----------------------
 __device__ __forceinline__ float ld_f32(const float *p, long long i) { return p[i]; }
 __device__ __forceinline__ float ld_f32(const uint16_t *p, long long i) { return __uint_as_float((unsigned)p[i] << 16); }
+// the two bf16 halves of a dword (two consecutive elements, the lower address in the low half)
+__device__ __forceinline__ float bf_lo(unsigned d) { return __uint_as_float(d << 16); }
+__device__ __forceinline__ float bf_hi(unsigned d) { return __uint_as_float(d & 0xFFFF0000u); }
 // ... and ONE rounding on the store: round to nearest even
 __device__ __forceinline__ void st_rne(float *p, long long i, float v) { p[i] = v; }
 __device__ __forceinline__ void st_rne(uint16_t *p, long long i, float v) { p[i] = (uint16_t)(cvt_pk_bf16(v, v) & 0xFFFFu); }
@@ -76,6 +79,28 @@ __device__ __forceinline__ void st_rne(uint16_t *p, long long i, float v) { p[i]
 __device__ __forceinline__ void st4_rne(float *o, const float (&v)[4]) { *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]); }
 __device__ __forceinline__ void st4_rne(uint16_t *o, const float (&v)[4]) {
     *reinterpret_cast<uint2 *>(o) = make_uint2(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]));
+}
+
+// ---- BatchNorm / ReLU per element: the ONE copy of the arithmetic of the training step's element-wise passes -----------------------
+// (bn_passes.hip, and wherever a layer kernel applies the same pass on its operand load or in its epilogue).  The forward's ReLU and
+// the backward's mask must agree at the edge: both hang on the SAME fma, `v < 0 ? 0 : v` keeps -0.0 and NaN, `!(v > 0)` masks +0, -0.0
+// and NaN (tests/test_gpu_bn_passes.py: test_relu_mask_agrees_between_forward_and_backward_at_its_edge).
+// y = act(x * sc + sh): one fma, then ReLU as a compare-and-select (not fmaxf: that would turn a NaN into 0)
+__device__ __forceinline__ float affine_act(float x, float sc, float sh, int relu) {
+    float v = __fmaf_rn(x, sc, sh);
+    if (relu) v = (v < 0.f) ? 0.f : v;
+    return v;
+}
+// gy * mask, mask = the forward's pre-activation is > 0 (recomputed from raw with the forward's own fma; without ReLU: 1).  g is
+// overwritten by value and returned, as every site spelled it before there was one copy: a `relu && ... ? 0.f : g` select compiles
+// to other code in some of the kernels.
+__device__ __forceinline__ float relu_masked(float g, float r, float sc, float sh, int relu) {
+    if (relu && !(__fmaf_rn(r, sc, sh) > 0.f)) g = 0.f;
+    return g;
+}
+// g_raw = a * (gy * mask) + b * raw + c0: two fmas, the inner one first (tests/bn_passes_ref.py emulates exactly these two roundings)
+__device__ __forceinline__ float bn_bwd_apply(float g, float r, float sc, float sh, int relu, float a, float b, float c0) {
+    return __fmaf_rn(a, relu_masked(g, r, sc, sh, relu), __fmaf_rn(b, r, c0));
 }
 
 // ---- bf16 normalise-on-load: a packed bf16 pair through act(raw * s + h) ---------------------------------------------

@@ -12,6 +12,9 @@
 //             W tile [4][64] go through LDS, the batch statistics of a channel are a wave reduction, running statistics updated in place
 //   backward  (1) same grid: ReLU mask, BatchNorm backward (two wave reductions), dz written, the four rows of dW = dz^T x (a thread per
 //             input channel, dz broadcast from LDS), bias / gamma / beta gradients;  (2) dx = dz W: workgroup = 64 input channels x 16 rows.
+//
+// Below them the two head kernels of EVAL mode: linear_act (sonet_linear_act_f32: Linear + folded BatchNorm + ReLU of a B x C feature, one
+// launch per layer) and chunk_mean (sonet_chunk_mean_f32: the segmenter head's mean over the k copies of a point).
 #include "common.hpp"
 
 namespace {
@@ -312,3 +315,191 @@ extern "C" int sonet_fc_dx_f32(const float *dz, const float *W, int B, int Cin, 
 }
 
 extern "C" int sonet_fc_max_rows(void) { return FC_MAXB; }
+
+// ---- small-batch fully connected layer (classifier / decoder heads in eval mode) --------------------------------------
+// y[b][o] = act((sum_k x[b][k] * W[o][k]) * scale[o] + shift[o]),  x [B][Cin], W [Cout][Cin] (nn.Linear layout), exact f32
+// fma chains.  MyLinear (models/layers.py:123-166) on a B x C feature: three of these (1024 -> 512 -> 256 -> 40)
+// replace ~12 aten launches (GEMM + bias, batch-norm transform, clamp).
+namespace {
+// The layer is a latency problem (67 MFLOP at B = 64, three of them in a row): the work is cut into many small workgroups and
+// every memory request of a thread is in flight before its first fma.  One workgroup = FC_ROWS = 16 rows x FC_OC = 8 outputs;
+// thread (row, ks) owns every 16th float4 of its row (the 16 ks lanes of a row read 256 consecutive bytes), its 8 weight rows
+// sit in LDS in the order the lanes walk k (ws[k % 4][k / 4][8]: the 16 lanes of an LDS read touch consecutive 32-byte slots);
+// the 16 k slices of a row meet in LDS and are summed in a fixed order.  1024 -> 512 at B = 64: 256 workgroups.
+// (Round 1: 64 rows x 2-4 outputs per workgroup, every lane reading its own row -- 64 cache lines per load instruction -- and
+// each workgroup pulling all of x: 22 us.  A version that staged x through LDS in chunks, 64 workgroups: 29-34 us, one wave per
+// SIMD waiting for each chunk.)
+constexpr int FC_ROWS = 16, FC_OC = 8, FC_KS = 16, FC_MAXJ = 16;   // FC_MAXJ float4 per thread and pass: 1024 columns
+template <bool MULTI /*Cin > 1024: more than one pass*/>
+__global__ __launch_bounds__(256) void linear_act_kernel(const float *__restrict__ x, const float *__restrict__ W,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift, int relu,
+                                                          float *__restrict__ y, int B, int Cin, int Cout, int nj /*float4 per thread*/)
+{
+    extern __shared__ __attribute__((aligned(16))) float fc_lds[];   // ws[4][K4][8] | part[16][16][8]
+    const int K4 = nj * FC_KS;                                    // padded Cin / 4
+    float *ws = fc_lds;
+    float *part = ws + (size_t)4 * K4 * FC_OC;
+    const int ks = threadIdx.x & 15, rr = threadIdx.x >> 4;
+    const int o0 = blockIdx.x * FC_OC, row = blockIdx.y * FC_ROWS + rr;
+    const bool vec = (Cin & 3) == 0;
+    // x first: the requests travel while the weights are staged.  A pass covers FC_MAXJ float4 per thread = 1024 columns; wider layers
+    // (Cin up to 4096: the weights of all passes sit in LDS) run the pass loop again with the accumulators kept.
+    float4 xv[FC_MAXJ];
+    auto fetch = [&](int j0) {
+#pragma unroll
+        for (int j = 0; j < FC_MAXJ; ++j) {
+            xv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int k = ((j0 + j) * FC_KS + ks) * 4;
+            if (j0 + j < nj && row < B && k < Cin) {
+                const float *src = x + (size_t)row * Cin + k;
+                if (vec) xv[j] = *reinterpret_cast<const float4 *>(src);
+                else {
+                    xv[j].x = src[0];
+                    if (k + 1 < Cin) xv[j].y = src[1];
+                    if (k + 2 < Cin) xv[j].z = src[2];
+                    if (k + 3 < Cin) xv[j].w = src[3];
+                }
+            }
+        }
+    };
+    fetch(0);
+    // weights: float4 along k, eight requests per thread in flight at a time; zero past Cin / Cout
+    for (int i0 = 0; i0 < FC_OC * K4; i0 += 8 * 256) {
+        float4 wv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 256 + (int)threadIdx.x, q = i / K4, k = (i - q * K4) * 4;
+            wv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < FC_OC * K4 && o0 + q < Cout && k < Cin) {
+                const float *src = W + (size_t)(o0 + q) * Cin + k;
+                if (vec) wv[u] = *reinterpret_cast<const float4 *>(src);
+                else {
+                    wv[u].x = src[0];
+                    if (k + 1 < Cin) wv[u].y = src[1];
+                    if (k + 2 < Cin) wv[u].z = src[2];
+                    if (k + 3 < Cin) wv[u].w = src[3];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * 256 + (int)threadIdx.x, q = i / K4, k4 = i - q * K4;
+            if (i < FC_OC * K4) {
+                ws[(0 * K4 + k4) * FC_OC + q] = wv[u].x;
+                ws[(1 * K4 + k4) * FC_OC + q] = wv[u].y;
+                ws[(2 * K4 + k4) * FC_OC + q] = wv[u].z;
+                ws[(3 * K4 + k4) * FC_OC + q] = wv[u].w;
+            }
+        }
+    }
+    __syncthreads();
+    float acc[FC_OC];
+#pragma unroll
+    for (int q = 0; q < FC_OC; ++q) acc[q] = 0.f;
+    for (int j0 = 0; j0 < (MULTI ? nj : 1); j0 += FC_MAXJ) {   // (single pass: straight-line code, measured 1.6 us faster on 1024 -> 512)
+        if (MULTI && j0 > 0) fetch(j0);
+#pragma unroll
+        for (int j = 0; j < FC_MAXJ; ++j) {
+            if (j0 + j < nj) {
+                const float xe[4] = {xv[j].x, xv[j].y, xv[j].z, xv[j].w};
+                const float4 *wp = reinterpret_cast<const float4 *>(ws + (size_t)((j0 + j) * FC_KS + ks) * FC_OC);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float4 w0 = wp[(size_t)e * K4 * 2], w1 = wp[(size_t)e * K4 * 2 + 1];
+                    acc[0] = __fmaf_rn(xe[e], w0.x, acc[0]); acc[1] = __fmaf_rn(xe[e], w0.y, acc[1]);
+                    acc[2] = __fmaf_rn(xe[e], w0.z, acc[2]); acc[3] = __fmaf_rn(xe[e], w0.w, acc[3]);
+                    acc[4] = __fmaf_rn(xe[e], w1.x, acc[4]); acc[5] = __fmaf_rn(xe[e], w1.y, acc[5]);
+                    acc[6] = __fmaf_rn(xe[e], w1.z, acc[6]); acc[7] = __fmaf_rn(xe[e], w1.w, acc[7]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < FC_OC; ++q) part[(rr * FC_KS + ks) * FC_OC + q] = acc[q];
+    __syncthreads();
+    if (threadIdx.x < FC_ROWS * FC_OC) {
+        const int r2 = threadIdx.x >> 3, q = threadIdx.x & 7;
+        const int o = o0 + q, row2 = blockIdx.y * FC_ROWS + r2;
+        if (o < Cout && row2 < B) {
+            float sum = 0.f;
+#pragma unroll
+            for (int t = 0; t < FC_KS; ++t) sum += part[(r2 * FC_KS + t) * FC_OC + q];
+            y[(size_t)row2 * Cout + o] = affine_act(sum, scale[o], shift[o], relu);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int sonet_linear_act_f32(const float *x, const float *W, const float *scale, const float *shift, int relu, float *y,
+                                    int B, int Cin, int Cout, sonet_stream_t stream)
+{
+    const char *what = "sonet_linear_act_f32";
+    SONET_REQUIRE(x && W && scale && shift && y, "%s: NULL pointer", what);
+    SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0, "%s: non-positive size", what);
+    // (the kernel reads x and W with 16-byte loads whenever Cin % 4 == 0: the rows then start on a 16-byte boundary iff the bases do)
+    SONET_REQUIRE((Cin & 3) != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) & 15) == 0,
+                  "%s: x and W must be 16-byte aligned when Cin %% 4 == 0 (misaligned)", what);
+    const int rows = sonet::ceil_div(B, FC_ROWS);
+    if (rows > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B=%d too large", what, B);
+    const int nj = sonet::ceil_div(Cin, 4 * FC_KS);
+    if (Cin > 4096) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cin=%d too large (max 4096: the workgroup's 8 weight rows sit in LDS)", what, Cin);
+    const size_t lds = ((size_t)4 * nj * FC_KS * FC_OC + FC_ROWS * FC_KS * FC_OC) * sizeof(float);
+    dim3 grid(sonet::ceil_div(Cout, FC_OC), rows), block(256);
+    hipStream_t st = sonet::as_stream(stream);
+    static bool raised = false;                                   // (dynamic LDS above 64 KiB has to be asked for: Cin > 1792)
+    if (lds > 64 * 1024 && !raised) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_act_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
+            return sonet::fail(SONET_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit", what);
+        raised = true;
+    }
+    if (nj > FC_MAXJ) hipLaunchKernelGGL(linear_act_kernel<true>, grid, block, lds, st, x, W, scale, shift, relu, y, B, Cin, Cout, nj);
+    else              hipLaunchKernelGGL(linear_act_kernel<false>, grid, block, lds, st, x, W, scale, shift, relu, y, B, Cin, Cout, nj);
+    return sonet::launched(what);
+}
+// ---- mean over the k copies of a point (segmenter head, models/networks.py:331-336) ----------------------------------------------
+// out[r][n] = c * ((h[r][n] + h[r][N + n]) + h[r][2 N + n]),  h [rows][k N], c = 1/3 (k = 3) or 0.5 (k = 2), k = 1: copy -- the
+// reference's own order of the adds and the single multiplication, so the result is bit-identical to the three aten launches it
+// replaces (split + add + add + mul: ~0.1 ms of the segmenter's 1.9 ms at 64 x 256 x 3 x 1024).
+namespace {
+__global__ __launch_bounds__(256) void chunk_mean_kernel(const float *__restrict__ h, float *__restrict__ out, long long rows, int N, int k, float c)
+{
+    const long long r = blockIdx.y;
+    const float *hr = h + r * (long long)k * N;
+    float *orow = out + r * N;
+    const bool vec = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    if (vec) {
+        const float4 *h4 = reinterpret_cast<const float4 *>(hr);
+        float4 *o4 = reinterpret_cast<float4 *>(orow);
+        const int N4 = N >> 2;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < N4; i += gridDim.x * 256) {
+            float4 s = h4[i];
+            for (int kk = 1; kk < k; ++kk) {
+                const float4 v = h4[(long long)kk * N4 + i];
+                s.x = __fadd_rn(s.x, v.x); s.y = __fadd_rn(s.y, v.y); s.z = __fadd_rn(s.z, v.z); s.w = __fadd_rn(s.w, v.w);
+            }
+            if (k > 1) { s.x = __fmul_rn(c, s.x); s.y = __fmul_rn(c, s.y); s.z = __fmul_rn(c, s.z); s.w = __fmul_rn(c, s.w); }
+            o4[i] = s;
+        }
+    } else {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+            float s = hr[i];
+            for (int kk = 1; kk < k; ++kk) s = __fadd_rn(s, hr[(long long)kk * N + i]);
+            orow[i] = k > 1 ? __fmul_rn(c, s) : s;
+        }
+    }
+}
+}  // namespace
+
+extern "C" int sonet_chunk_mean_f32(const float *h, float *out, long long rows, int N, int k, sonet_stream_t stream)
+{
+    const char *what = "sonet_chunk_mean_f32";
+    SONET_REQUIRE(h && out, "%s: NULL pointer", what);
+    SONET_REQUIRE(rows > 0 && N > 0 && k >= 1, "%s: bad size", what);
+    if (rows > 65535 * 32768ll || k > 3) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: rows=%lld k=%d", what, rows, k);
+    if (rows > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: more than 65535 rows", what);
+    const int gx = sonet::ceil_div(N, 1024) < 1 ? 1 : (sonet::ceil_div(N, 1024) > 8 ? 8 : sonet::ceil_div(N, 1024));
+    hipLaunchKernelGGL(chunk_mean_kernel, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, sonet::as_stream(stream), h, out, rows, N, k,
+                       k == 3 ? (float)(1.0 / 3.0) : 0.5f);
+    return sonet::launched(what);
+}

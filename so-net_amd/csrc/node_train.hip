@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void node_gather_bwd_kernel(const T *__restric
     gx[t] = s;
 }
 
-// The BatchNorm / ReLU backward of a layer (bwd_apply_kernel of pointwise_bwd.hip, operation for operation) and the per-node sums of what
+// The BatchNorm / ReLU backward of a layer (rowwise_kernel<1, float, false> of bn_passes.hip: bn_bwd_apply, operation for operation) and the per-node sums of what
 // it stores in ONE pass over (gy, raw): the gradient of a per-node addend (segmenter layer 1 in its node-wise form) is the sum of
 // g_raw over every node's columns, and a second launch would read the stored tensor again.  A workgroup owns ANS_ROWS channel rows of
 // one cloud and walks them in tiles of ANS_TILE columns: g_raw is computed, stored and kept in LDS; then one thread per (row, node)
@@ -220,9 +220,7 @@ __global__ __launch_bounds__(ANS_THREADS) void bwd_apply_nodesum_kernel(const fl
             } else {
                 for (int i = threadIdx.x; i < tlen; i += ANS_THREADS) {
                     const float rv = raw[base + i];
-                    float gv = gy[base + i];
-                    if (relu && !(__fmaf_rn(rv, sc[r], sh[r]) > 0.f)) gv = 0.f;
-                    const float ov = __fmaf_rn(a[r], gv, __fmaf_rn(bb[r], rv, c0[r]));
+                    const float ov = bn_bwd_apply(gy[base + i], rv, sc[r], sh[r], relu, a[r], bb[r], c0[r]);
                     out[base + i] = ov;
                     tile[r * ANS_TILE + i] = ov;
                 }

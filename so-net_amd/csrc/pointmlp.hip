@@ -188,8 +188,7 @@ __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_kernel(
                     const float sc = scale[o], sh = shift[o];
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
-                        float v = __fmaf_rn(acc[mt][nt][r], sc, sh);
-                        if (relu) v = (v < 0.f) ? 0.f : v;      // NaN propagates like aten's relu
+                        float v = affine_act(acc[mt][nt][r], sc, sh, relu);      // NaN propagates like aten's relu
                         if (pv[nt]) y[ybase[nt] + (long long)o * L] = v;
                     }
                 }
@@ -344,8 +343,7 @@ __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_wlds_kernel(
                 const int o = (ct0 + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (o < Cout) {
                     const float2 ss = affine[o - ct_begin * 32];
-                    float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                    if (relu) v = (v < 0.f) ? 0.f : v;
+                    float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                     if constexpr (ABL & 1) { asm volatile("" ::"v"(v)); continue; }
                     if (pv) y[ybase + (long long)o * L] = v;
                 }
@@ -498,84 +496,11 @@ __global__ __launch_bounds__(PM_THREADS) void pointmlp_f32_lean_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int orow = (r & 3) + 8 * (r >> 2);             // + 4h is folded into voy / aff
                     const float2 ss = aff[orow];
-                    float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                    if (relu) v = (v < 0.f) ? 0.f : v;
+                    float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy, so_tile + (unsigned)orow * rowB, 0);
                 }
             }
         }
-    }
-}
-
-// ---- training-mode BatchNorm support: per-channel statistics and the normalise + ReLU pass --------
-constexpr int ST_THREADS = 256;
-
-// grid (chunks, C): each workgroup reduces one chunk of one channel over (b, l); f64 partials are
-// combined with f64 atomics into stat_ws[2*C] = {sum[c], sumsq[c]}.
-__global__ __launch_bounds__(ST_THREADS) void channel_stats_kernel(const float *__restrict__ y, int B, int C, int L,
-                                                                    double *__restrict__ stat_ws)
-{
-    const int c = blockIdx.y;
-    const long long per_c = (long long)B * L;
-    const long long chunk = (per_c + gridDim.x - 1) / gridDim.x;
-    const long long beg = (long long)blockIdx.x * chunk, end = min(per_c, beg + chunk);
-    double s = 0.0, s2 = 0.0;
-    for (long long t = beg + threadIdx.x; t < end; t += ST_THREADS) {
-        const long long b = t / L;
-        const float v = y[(b * C + c) * (long long)L + (t - b * L)];
-        s += (double)v;
-        s2 += (double)v * (double)v;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_down(s, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-    }
-    __shared__ double red[2][ST_THREADS / 64];
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, a2 = 0.0;
-        for (int w = 0; w < ST_THREADS / 64; ++w) { a += red[0][w]; a2 += red[1][w]; }
-        unsafeAtomicAdd(&stat_ws[c], a);
-        unsafeAtomicAdd(&stat_ws[C + c], a2);
-    }
-}
-
-__global__ __launch_bounds__(256) void channel_stats_finalize_kernel(const double *__restrict__ stat_ws, int C, double inv_n,
-                                                                      float *__restrict__ mean, float *__restrict__ var, const sonet::BnRider rd)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const double m = stat_ws[c] * inv_n;
-    double v = stat_ws[C + c] * inv_n - m * m;
-    if (v < 0.0) v = 0.0;
-    mean[c] = (float)m;
-    var[c] = (float)v;
-    if (rd.gamma != nullptr) {                                  // (BatchNorm rider, common.hpp: coefficients + running update, operation for operation)
-        const float mf = (float)m, vf = (float)v;
-        const float is = 1.0f / __fsqrt_rn(vf + rd.eps);
-        const float s_ = rd.gamma[c] * is;
-        rd.invstd[c] = is;
-        rd.sc[c] = s_;
-        rd.sh[c] = rd.beta[c] - mf * s_;
-        if (rd.rmean != nullptr) {
-            const float mo = rd.momentum;
-            rd.rmean[c] = __fmaf_rn(mf, mo, __fmul_rn(rd.rmean[c], 1.0f - mo));
-            rd.rvar[c] = __fmaf_rn(__fmul_rn(vf, rd.unbias), mo, __fmul_rn(rd.rvar[c], 1.0f - mo));
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void channel_affine_act_kernel(float *__restrict__ y, const float *__restrict__ scale,
-                                                                  const float *__restrict__ shift, int relu, int C, int L,
-                                                                  long long total)
-{
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-        const int c = (int)((t / L) % C);
-        float v = __fmaf_rn(y[t], scale[c], shift[c]);
-        if (relu) v = (v < 0.f) ? 0.f : v;
-        y[t] = v;
     }
 }
 
@@ -682,39 +607,5 @@ extern "C" int sonet_pointmlp_f32(const float *x1, int C1, const float *x2, int 
 #undef PM_LAUNCH
 #undef PM_LAUNCH_V2
 #undef PM_ARGS
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_channel_stats_f32(const float *y, int B, int C, int L, double *stat_ws, float *mean,
-                                       float *var_biased, sonet_stream_t stream)
-{
-    const char *what = "sonet_channel_stats_f32";
-    SONET_REQUIRE(y && stat_ws && mean && var_biased, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0, "%s: non-positive size", what);
-    if (C > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: C=%d > 65535", what, C);
-    hipStream_t st = sonet::as_stream(stream);
-    if (hipMemsetAsync(stat_ws, 0, (size_t)2 * C * sizeof(double), st) != hipSuccess)
-        return sonet::fail(SONET_ERR_LAUNCH, "%s: hipMemsetAsync failed", what);
-    const long long per_c = (long long)B * L;
-    int chunks = (int)sonet::ceil_div64(per_c, 16384);
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    hipLaunchKernelGGL(channel_stats_kernel, dim3(chunks, C), dim3(ST_THREADS), 0, st, y, B, C, L, stat_ws);
-    hipLaunchKernelGGL(channel_stats_finalize_kernel, dim3(sonet::ceil_div(C, 256)), dim3(256), 0, st,
-                       stat_ws, C, 1.0 / (double)per_c, mean, var_biased, sonet::take_bn_rider());
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_channel_affine_act_f32(float *y, const float *scale, const float *shift, int relu,
-                                            int B, int C, int L, sonet_stream_t stream)
-{
-    const char *what = "sonet_channel_affine_act_f32";
-    SONET_REQUIRE(y && scale && shift, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0, "%s: non-positive size", what);
-    const long long total = (long long)B * C * L;
-    long long blocks = sonet::ceil_div64(total, 256);
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(channel_affine_act_kernel, dim3((unsigned)blocks), dim3(256), 0, sonet::as_stream(stream),
-                       y, scale, shift, relu, C, L, total);
     return sonet::launched(what);
 }

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const PackEntry *__rest
 // partials i, i + 256, ... in order, the 256 sums meet in a fixed tree (deterministic).  (Four channels per workgroup and 64 lanes per
 // channel took 40 us on the 7,500 partials of a point-level f32 layer.)  With a rider (common.hpp) the same thread goes on to the
 // normalisation coefficients and the running-statistics update -- the arithmetic of bn_fwd_coeffs_kernel / bn_running_update_kernel
-// (pointwise_bwd.hip), operation for operation.
+// (bn_passes.hip), operation for operation.
 __device__ __forceinline__ void bn_rider_apply(const sonet::BnRider &rd, int c, float mean, float var) {
     if (rd.gamma == nullptr) return;
     const float is = 1.0f / __fsqrt_rn(var + rd.eps);
@@ -569,8 +569,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
                         if ((r & 3) + 8 * (r >> 2) + 4 * h == sp_p0rel) {
-                            float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                            if (relu) v = (v < 0.f) ? 0.f : v;
+                            float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                             sp.v0[(size_t)b * Cout + (ct0 + mt) * 32 + j] = v;
                         }
                 }
@@ -592,8 +591,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {               // ascending point order, strict '>': the first of equal values stays
                         const int orow = (r & 3) + 8 * (r >> 2);
-                        float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                        if (relu) v = (v < 0.f) ? 0.f : v;
+                        float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                         const bool take = (unsigned)(trel + orow) < nrows && v > m;      // (a NaN fails the compare: it never wins)
                         m = take ? v : m;
                         p = take ? orow + 4 * h : p;
@@ -622,8 +620,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int orow = (r & 3) + 8 * (r >> 2);
                     const float2 ss = aff[orow];
-                    float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                    if (relu) v = (v < 0.f) ? 0.f : v;
+                    float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy_s, so_tile + (unsigned)orow * rowB, 0);
                     const int ch = (ct0 + mt) * 32 + orow + 4 * h;
                     // (requested here: 16 MT exposed round trips per lane.  Requested before the K loop -- 64 more registers, one workgroup
@@ -661,8 +658,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int orow = (r & 3) + 8 * (r >> 2);
                     const float2 ss = aff[orow];
-                    float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                    if (relu) v = (v < 0.f) ? 0.f : v;
+                    float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy_s, so_tile + (unsigned)orow * rowB, 0);
                     const float sv = pv ? v : 0.f;
                     const float s1 = row32_sum(sv), s2 = row32_sum(sv * sv);
@@ -685,8 +681,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                         const int orow = (r & 3) + 8 * (r >> 2);
                         const float2 ss = aff[orow];
                         const float zv = zok ? zb[(size_t)((ct0 + mt) * 32 + orow + 4 * h) * ZM] : 0.f;
-                        float v = __fmaf_rn(acc[mt][r], ss.x, __fmaf_rn(zv, ss.x * unscale, ss.y));
-                        if (relu) v = (v < 0.f) ? 0.f : v;
+                        float v = affine_act(acc[mt][r], ss.x, __fmaf_rn(zv, ss.x * unscale, ss.y), relu);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy_s, so_tile + (unsigned)orow * rowB, 0);
                         const float sv = pv ? v : 0.f;
                         const float s1 = row32_sum(sv), s2 = row32_sum(sv * sv);
@@ -722,8 +717,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                     float zv;
                     if constexpr (ZADD) zv = zreg[mt][r];
                     else zv = zok ? zb[(size_t)((ct0 + mt) * 32 + orow + 4 * h) * ZM] : 0.f;
-                    float v = __fmaf_rn(acc[mt][r], ss.x, __fmaf_rn(zv, ss.x * unscale, ss.y));
-                    if (relu) v = (v < 0.f) ? 0.f : v;
+                    float v = affine_act(acc[mt][r], ss.x, __fmaf_rn(zv, ss.x * unscale, ss.y), relu);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy, so_tile + (unsigned)orow * rowB, 0);
                 }
             }
@@ -753,8 +747,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                     for (int r = r0; r < r0 + 8; ++r) {
                         const int orow = (r & 3) + 8 * (r >> 2);
                         const float2 ss = aff[orow];
-                        float v = __fmaf_rn(acc[mt][r], ss.x, ss.y);
-                        if (relu) v = (v < 0.f) ? 0.f : v;
+                        float v = affine_act(acc[mt][r], ss.x, ss.y, relu);
                         if constexpr (BNB) { if (addy) v = v + ya[r - r0]; }
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voy, so_tile + (unsigned)orow * rowB, 0);
                     }
@@ -1012,8 +1005,7 @@ __global__ __launch_bounds__(X3_THREADS, NC == 1 ? 2 : 1) void pointmlp_h3r_kern
                     float v[NC], sv = 0.f, sq = 0.f;
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        v[c] = __fmaf_rn(acc[mt][c][r], ss.x, ss.y);
-                        if (relu) v[c] = (v[c] < 0.f) ? 0.f : v[c];
+                        v[c] = affine_act(acc[mt][c][r], ss.x, ss.y, relu);
                         const float vv = pv ? v[c] : 0.f;
                         sv = c == 0 ? vv : sv + vv;
                         sq = c == 0 ? vv * vv : sq + vv * vv;
@@ -1046,8 +1038,7 @@ __global__ __launch_bounds__(X3_THREADS, NC == 1 ? 2 : 1) void pointmlp_h3r_kern
                     for (int r = 0; r < 16; ++r) {
                         const int orow = (r & 3) + 8 * (r >> 2);
                         const float2 ss = aff[orow];
-                        float v = __fmaf_rn(acc[mt][0][r], ss.x, ss.y);
-                        if (relu) v = (v < 0.f) ? 0.f : v;
+                        float v = affine_act(acc[mt][0][r], ss.x, ss.y, relu);
                         const unsigned u = __float_as_uint(v);
                         atomicMax(kb + (size_t)((ct0 + mt) * 32 + orow + 4 * h) * KM, (u & 0x80000000u) ? ~u : (u | 0x80000000u));
                     }
@@ -1074,8 +1065,7 @@ __global__ __launch_bounds__(X3_THREADS, NC == 1 ? 2 : 1) void pointmlp_h3r_kern
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
                         const float zv = zok[c] ? zb[c][(size_t)((ct0 + mt) * 32 + orow + 4 * h) * ZM] : 0.f;
-                        v[c] = __fmaf_rn(acc[mt][c][r], ss.x, __fmaf_rn(zv, ss.x * 32.f, ss.y));
-                        if (relu) v[c] = (v[c] < 0.f) ? 0.f : v[c];
+                        v[c] = affine_act(acc[mt][c][r], ss.x, __fmaf_rn(zv, ss.x * 32.f, ss.y), relu);
                     }
                     store_row(v, voy, so_tile + (unsigned)orow * rowB);
                 }
@@ -1092,8 +1082,7 @@ __global__ __launch_bounds__(X3_THREADS, NC == 1 ? 2 : 1) void pointmlp_h3r_kern
                     float v[NC];
 #pragma unroll
                     for (int c = 0; c < NC; ++c) {
-                        v[c] = __fmaf_rn(acc[mt][c][r], ss.x, ss.y);
-                        if (relu) v[c] = (v[c] < 0.f) ? 0.f : v[c];
+                        v[c] = affine_act(acc[mt][c][r], ss.x, ss.y, relu);
                     }
                     store_row(v, voy, so_tile + (unsigned)orow * rowB);
                 }

@@ -1,772 +1,9 @@
-// pointwise_bwd.hip -- backward of act(BN(W x + b)) around the GEMMs (training, configs 2 / 5).
-//
-// Replaces the autograd graph the reference builds for models/layers.py:282-296 (conv1d -> F.batch_norm ->
-// relu): two passes over (gy, raw) instead of ~20 element-wise aten launches over B x C x L tensors.
-//   pass 1  per channel:  s1 = sum gy*mask,  s2 = sum gy*mask*raw      (f64 accumulation, as channel_stats)
-//   pass 2  g_raw = a[c] * (gy*mask) + b[c] * raw + c0[c]
-// with mask = (fma(raw, scale[c], shift[c]) > 0) when the layer has a ReLU (bit-identical to the forward's
-// affine), else 1.  The host turns (s1, s2) into (a, b, c0) -- for training BatchNorm
-//   a = gamma*invstd,  b = -a*invstd*sg/n,  c0 = -a*s1/n - b*mean,  sg = invstd*(s2 - mean*s1)
-// (the usual  gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) ), for a constant affine a = scale, b = c0 = 0.
-// The GEMMs themselves (dgrad = W^T g_raw on the pointmlp kernels, wgrad = g_raw x^T) are launched by the host.
+// pooled_bwd.hip -- backward of the pooled last layer of the first PointNet (training): the sparse input gradient (pooled_dgrad: scalar f32,
+// f32 with the tail layer's BatchNorm-backward sums, bf16 output, matrix-core bf16) and the weight gradient (pooled_wgrad) over the
+// arg-max positions of the per-node max-pool.
 #include "common.hpp"
 
 #include <hip/hip_runtime.h>
-
-namespace {
-
-constexpr int BW_THREADS = 256;
-
-__global__ __launch_bounds__(BW_THREADS) void bwd_stats_kernel(const float *__restrict__ gy, const float *__restrict__ raw,
-                                                                const float *__restrict__ scale, const float *__restrict__ shift,
-                                                                int relu, int B, int C, int L, double *__restrict__ ws)
-{
-    const int c = blockIdx.y;
-    const long long per_c = (long long)B * L;
-    const long long chunk = (per_c + gridDim.x - 1) / gridDim.x;
-    const long long beg = (long long)blockIdx.x * chunk, end = min(per_c, beg + chunk);
-    const float sc = scale[c], sh = shift[c];
-    double s1 = 0.0, s2 = 0.0;
-    for (long long t = beg + threadIdx.x; t < end; t += BW_THREADS) {
-        const long long b = t / L;
-        const long long o = (b * C + c) * (long long)L + (t - b * L);
-        const float r = raw[o];
-        float g = gy[o];
-        if (relu && !(__fmaf_rn(r, sc, sh) > 0.f)) g = 0.f;
-        s1 += (double)g;
-        s2 += (double)g * (double)r;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-    }
-    __shared__ double red[2][BW_THREADS / 64];
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, a2 = 0.0;
-        for (int w = 0; w < BW_THREADS / 64; ++w) { a += red[0][w]; a2 += red[1][w]; }
-        unsafeAtomicAdd(&ws[c], a);
-        unsafeAtomicAdd(&ws[C + c], a2);
-    }
-}
-
-__global__ __launch_bounds__(256) void bwd_ws_zero_kernel(double *ws, int n)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) ws[i] = 0.0;
-}
-
-// one workgroup row = one (b, c) row of L elements: coefficients are wave-uniform
-__global__ __launch_bounds__(256) void bwd_apply_kernel(const float *__restrict__ gy, const float *__restrict__ raw,
-                                                         const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                         const float *__restrict__ ca, const float *__restrict__ cb,
-                                                         const float *__restrict__ cc, float *__restrict__ out, int C, int L)
-{
-    const long long row = blockIdx.x;
-    const int c = (int)(row % C);
-    const float sc = scale[c], sh = shift[c], a = ca[c], b = cb[c], c0 = cc[c];
-    const float *g = gy + row * L, *r = raw + row * L;
-    float *o = out + row * L;
-    for (int t = blockIdx.y * 256 + threadIdx.x; t < L; t += gridDim.y * 256) {
-        const float rv = r[t];
-        float gv = g[t];
-        if (relu && !(__fmaf_rn(rv, sc, sh) > 0.f)) gv = 0.f;
-        o[t] = __fmaf_rn(a, gv, __fmaf_rn(b, rv, c0));
-    }
-}
-
-__global__ __launch_bounds__(256) void affine_act_out_kernel(const float *__restrict__ x, const float *__restrict__ scale,
-                                                              const float *__restrict__ shift, int relu, float *__restrict__ y,
-                                                              int C, int L)
-{
-    const long long row = blockIdx.x;
-    const int c = (int)(row % C);
-    const float sc = scale[c], sh = shift[c];
-    const float *xi = x + row * L;
-    float *yo = y + row * L;
-    for (int t = blockIdx.y * 256 + threadIdx.x; t < L; t += gridDim.y * 256) {
-        float v = __fmaf_rn(xi[t], sc, sh);
-        if (relu) v = (v < 0.f) ? 0.f : v;
-        yo[t] = v;
-    }
-}
-
-// y = act((t + z[b][c][ids[b][l]]) * scale[c] + shift[c]) in place: the per-node block of a layer whose input concatenates
-// per-point and per-node (broadcast back) channels is computed once per node and added here (segmenter layer 1,
-// models/networks.py:296-326).  One workgroup per (b, c) row; the row's M node values sit in LDS.
-__global__ __launch_bounds__(256) void node_add_affine_act_kernel(float *__restrict__ t, const float *__restrict__ z,
-                                                                   const int32_t *__restrict__ ids, const float *__restrict__ scale,
-                                                                   const float *__restrict__ shift, int relu, int C, int L, int M)
-{
-    extern __shared__ float zrow[];
-    const long long row = blockIdx.x;
-    const int c = (int)(row % C);
-    const long long b = row / C;
-    for (int m = threadIdx.x; m < M; m += 256) zrow[m] = z[row * M + m];
-    __syncthreads();
-    const float sc = scale[c], sh = shift[c];
-    float *tr = t + row * L;
-    const int32_t *id = ids + b * L;
-    for (int l = blockIdx.y * 256 + threadIdx.x; l < L; l += gridDim.y * 256) {
-        const int m = id[l];
-        float v = tr[l] + ((unsigned)m < (unsigned)M ? zrow[m] : 0.f);
-        v = __fmaf_rn(v, sc, sh);
-        if (relu) v = (v < 0.f) ? 0.f : v;
-        tr[l] = v;
-    }
-}
-
-// out[b][c][l] = act((z[b][c][gidx[b][l]] + sum_i wl[c][i] * lead[b][i][l]) * scale[c] + shift[c]):  a layer over GATHERED node
-// features plus a few per-column channels (KNNModule layer 1: 384 gathered + 3 de-centred coordinate channels over K * M
-// columns, models/layers.py:313-350) is linear in the features, so W_f . x is computed ONCE per node (z, M columns instead of
-// K * M: one ninth of the MFMAs at K = 9) and gathered here; the NL <= 4 lead channels are exact f32 fmas in channel order.
-// One workgroup per (cloud, 8 channels): gidx / lead are read once per 8 output rows, the 8 node rows sit in LDS.
-constexpr int NGL_CH = 8, NGL_THREADS = 128;
-// T: storage type of z and out (float, or uint16_t = bfloat16 bits: values widened, arithmetic in f32, one rounding on the store)
-template <typename T>
-__global__ __launch_bounds__(NGL_THREADS) void node_gather_lead_kernel(const T *__restrict__ z, const int32_t *__restrict__ gidx,
-                                                                        const float *__restrict__ lead, const float *__restrict__ wl,
-                                                                        const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                                        T *__restrict__ out, int C, int L, int M, int NL)
-{
-    extern __shared__ float zs[];                                 // [NGL_CH][M] | coef[NGL_CH][6] (w0..w3, scale, shift)
-    float *coef = zs + NGL_CH * M;
-    const int cb = blockIdx.x * NGL_CH;
-    const long long b = blockIdx.y;
-    const int nch = min(NGL_CH, C - cb);
-    for (int i = threadIdx.x; i < nch * M; i += NGL_THREADS) zs[i] = ld_f32(z, ((long long)b * C + cb) * M + i);
-    if (threadIdx.x < nch) {
-        const int c = cb + threadIdx.x;
-        for (int i = 0; i < 4; ++i) coef[threadIdx.x * 6 + i] = i < NL ? wl[c * NL + i] : 0.f;
-        coef[threadIdx.x * 6 + 4] = scale[c];
-        coef[threadIdx.x * 6 + 5] = shift[c];
-    }
-    __syncthreads();
-    const int32_t *g = gidx + b * L;
-    const float *ld = lead + b * (long long)NL * L;
-    T *ob = out + ((long long)b * C + cb) * L;
-    const int L4 = (L + 3) >> 2;
-    const bool vec = (L & 3) == 0;
-    // a thread owns a quad of columns: node ids and lead channels are read once and serve the 8 channel rows
-    for (int q = threadIdx.x; q < L4; q += NGL_THREADS) {
-        const int l = q * 4;
-        int m[4];
-        float d[4][4];
-        if (vec) {
-            const int4 mv = *reinterpret_cast<const int4 *>(g + l);
-            m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 dv = i < NL ? *reinterpret_cast<const float4 *>(ld + (long long)i * L + l) : make_float4(0.f, 0.f, 0.f, 0.f);
-                d[i][0] = dv.x; d[i][1] = dv.y; d[i][2] = dv.z; d[i][3] = dv.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int le = l + e < L ? l + e : L - 1;
-                m[e] = g[le];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) d[i][e] = i < NL ? ld[(long long)i * L + le] : 0.f;
-            }
-        }
-        for (int c = 0; c < nch; ++c) {
-            const float *cf = coef + c * 6;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float a = (unsigned)m[e] < (unsigned)M ? zs[c * M + m[e]] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a = __fmaf_rn(cf[i], d[i][e], a);      // (absent lead channels: + 0 * 0, exact)
-                a = __fmaf_rn(a, cf[4], cf[5]);
-                v[e] = (relu && a < 0.f) ? 0.f : a;
-            }
-            T *o = ob + (long long)c * L + l;
-            if (vec) st4_rne(o, v);
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (l + e < L) st_rne(o, e, v[e]);
-            }
-        }
-    }
-}
-
-// per-channel coefficient kernels (C threads): replace a dozen C-element aten launches per layer
-__global__ __launch_bounds__(256) void bn_fwd_coeffs_kernel(const float *__restrict__ mean, const float *__restrict__ var,
-                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                             float eps, int C, float *__restrict__ invstd,
-                                                             float *__restrict__ sc, float *__restrict__ sh)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const float is = 1.0f / __fsqrt_rn(var[c] + eps);          // torch.rsqrt(var + eps) to 1 ulp; only the product below is used
-    const float s = gamma[c] * is;
-    invstd[c] = is;
-    sc[c] = s;
-    sh[c] = beta[c] - mean[c] * s;
-}
-
-// F.batch_norm's running-statistics update (models/layers.py:60-70 via MyBatchNorm*): r = r*(1-m) + m*stat, the variance
-// entering unbiased (var * n/(n-1)).  One launch instead of four C-element aten launches per BatchNorm layer and step.
-__global__ __launch_bounds__(256) void bn_running_update_kernel(float *__restrict__ rmean, float *__restrict__ rvar,
-                                                                 const float *__restrict__ mean, const float *__restrict__ var,
-                                                                 float m, float unbias, int C)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    rmean[c] = __fmaf_rn(mean[c], m, __fmul_rn(rmean[c], 1.0f - m));
-    rvar[c] = __fmaf_rn(__fmul_rn(var[c], unbias), m, __fmul_rn(rvar[c], 1.0f - m));
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(const double *__restrict__ sums, const float *__restrict__ mean,
-                                                             const float *__restrict__ invstd, const float *__restrict__ gamma,
-                                                             double n, int C, float *__restrict__ a, float *__restrict__ b,
-                                                             float *__restrict__ c0, float *__restrict__ g_gamma,
-                                                             float *__restrict__ g_beta)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const double s1 = sums[c], s2 = sums[C + c], m = (double)mean[c], is = (double)invstd[c];
-    const double sg = is * (s2 - m * s1);                       // sum gy*mask*xhat
-    const double av = (double)gamma[c] * is;
-    const double bv = -av * is * sg / n;
-    a[c] = (float)av;
-    b[c] = (float)bv;
-    c0[c] = (float)(-av * s1 / n - bv * m);
-    g_gamma[c] = (float)sg;
-    g_beta[c] = (float)s1;
-}
-
-// ---- bf16 twins of the element-wise passes (BASELINE configs[1]: bf16 training): same arithmetic in f32 / f64 on values
-// widened from bf16, results rounded to nearest-even bf16.  Two elements (one dword) per lane when the rows are dword aligned.
-__device__ __forceinline__ float bf_lo(unsigned d) { return __uint_as_float(d << 16); }
-__device__ __forceinline__ float bf_hi(unsigned d) { return __uint_as_float(d & 0xFFFF0000u); }
-
-// grid (chunks, C) as bwd_stats_kernel / channel_stats_kernel; raw == nullptr: plain statistics of gy (sum, sum of squares)
-template <bool PAIR>
-__global__ __launch_bounds__(BW_THREADS) void bwd_stats_bf16_kernel(const uint16_t *__restrict__ gy, const uint16_t *__restrict__ raw,
-                                                                     const float *__restrict__ scale, const float *__restrict__ shift,
-                                                                     int relu, int B, int C, int L, double *__restrict__ ws)
-{
-    const int c = blockIdx.y;
-    constexpr int V = PAIR ? 2 : 1;
-    const int Lv = L / V;
-    const long long per_c = (long long)B * Lv;
-    const long long chunk = (per_c + gridDim.x - 1) / gridDim.x;
-    const long long beg = (long long)blockIdx.x * chunk, end = min(per_c, beg + chunk);
-    const float sc = raw ? scale[c] : 0.f, sh = raw ? shift[c] : 0.f;
-    double s1 = 0.0, s2 = 0.0;
-    for (long long t = beg + threadIdx.x; t < end; t += BW_THREADS) {
-        const long long b = t / Lv;
-        const long long o = (b * C + c) * (long long)L + (t - b * Lv) * V;
-        float g[V], r[V];
-        if constexpr (PAIR) {
-            const unsigned dg = *reinterpret_cast<const unsigned *>(gy + o);
-            g[0] = bf_lo(dg); g[1] = bf_hi(dg);
-            if (raw) { const unsigned dr = *reinterpret_cast<const unsigned *>(raw + o); r[0] = bf_lo(dr); r[1] = bf_hi(dr); }
-        } else {
-            g[0] = ld_f32(gy, o);
-            if (raw) r[0] = ld_f32(raw, o);
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            if (raw) {
-                float gv = g[v];
-                if (relu && !(__fmaf_rn(r[v], sc, sh) > 0.f)) gv = 0.f;
-                s1 += (double)gv;
-                s2 += (double)gv * (double)r[v];
-            } else {
-                s1 += (double)g[v];
-                s2 += (double)g[v] * (double)g[v];
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-    }
-    __shared__ double red[2][BW_THREADS / 64];
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, a2 = 0.0;
-        for (int w = 0; w < BW_THREADS / 64; ++w) { a += red[0][w]; a2 += red[1][w]; }
-        unsafeAtomicAdd(&ws[c], a);
-        unsafeAtomicAdd(&ws[C + c], a2);
-    }
-}
-
-// one workgroup row = one (b, c) row.  MODE 0: out = act(x * scale + shift) (forward normalise + ReLU);
-// MODE 1: out = a * (gy * mask) + b * raw + c0 with mask from (raw, scale, shift) (backward apply).
-template <int MODE, bool PAIR>
-__global__ __launch_bounds__(256) void rowwise_bf16_kernel(const uint16_t *__restrict__ gy, const uint16_t *__restrict__ raw,
-                                                            const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                            const float *__restrict__ ca, const float *__restrict__ cb,
-                                                            const float *__restrict__ cc, uint16_t *__restrict__ out, int C, int L)
-{
-    const long long row = blockIdx.x;
-    const int c = (int)(row % C);
-    const float sc = scale[c], sh = shift[c];
-    const float a = MODE == 1 ? ca[c] : 0.f, b = MODE == 1 ? cb[c] : 0.f, c0 = MODE == 1 ? cc[c] : 0.f;
-    const uint16_t *r = raw + row * L, *g = MODE == 1 ? gy + row * L : nullptr;
-    uint16_t *o = out + row * L;
-    auto f = [&](float rv, float gv) {
-        if constexpr (MODE == 0) {
-            float v = __fmaf_rn(rv, sc, sh);
-            if (relu) v = (v < 0.f) ? 0.f : v;
-            return v;
-        } else {
-            if (relu && !(__fmaf_rn(rv, sc, sh) > 0.f)) gv = 0.f;
-            return __fmaf_rn(a, gv, __fmaf_rn(b, rv, c0));
-        }
-    };
-    if constexpr (PAIR) {
-        const int Lv = L >> 1;
-        for (int t = blockIdx.y * 256 + threadIdx.x; t < Lv; t += gridDim.y * 256) {
-            const unsigned dr = reinterpret_cast<const unsigned *>(r)[t];
-            const unsigned dg = MODE == 1 ? reinterpret_cast<const unsigned *>(g)[t] : 0u;
-            reinterpret_cast<unsigned *>(o)[t] = cvt_pk_bf16(f(bf_lo(dr), bf_lo(dg)), f(bf_hi(dr), bf_hi(dg)));
-        }
-    } else {
-        for (int t = blockIdx.y * 256 + threadIdx.x; t < L; t += gridDim.y * 256)
-            o[t] = (uint16_t)(cvt_pk_bf16(f(ld_f32(r, t), MODE == 1 ? ld_f32(g, t) : 0.f), 0.f) & 0xFFFFu);
-    }
-}
-
-__global__ __launch_bounds__(256) void stats_finalize_kernel(const double *__restrict__ ws, int C, double inv_n,
-                                                             float *__restrict__ mean, float *__restrict__ var, const sonet::BnRider rd)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    const double m = ws[c] * inv_n;
-    double v = ws[C + c] * inv_n - m * m;
-    if (v < 0.0) v = 0.0;
-    mean[c] = (float)m;
-    var[c] = (float)v;
-    if (rd.gamma != nullptr) {                                  // (BatchNorm rider: bn_fwd_coeffs_kernel + bn_running_update_kernel below, operation for operation)
-        const float mf = (float)m, vf = (float)v;
-        const float is = 1.0f / __fsqrt_rn(vf + rd.eps);
-        const float s_ = rd.gamma[c] * is;
-        rd.invstd[c] = is;
-        rd.sc[c] = s_;
-        rd.sh[c] = rd.beta[c] - mf * s_;
-        if (rd.rmean != nullptr) {
-            const float mo = rd.momentum;
-            rd.rmean[c] = __fmaf_rn(mf, mo, __fmul_rn(rd.rmean[c], 1.0f - mo));
-            rd.rvar[c] = __fmaf_rn(__fmul_rn(vf, rd.unbias), mo, __fmul_rn(rd.rvar[c], 1.0f - mo));
-        }
-    }
-}
-
-}  // namespace
-
-
-namespace {
-// ---- 16 bytes per lane -------------------------------------------------------------------------------------------------------------
-// The element-wise passes of the training step (normalise + ReLU of the forward, the two passes of the BatchNorm / ReLU backward) are
-// pure streams over [B][C][L] tensors; with 4-byte accesses per lane they ran at 3.0-4.3 TB/s (and the statistics pass paid a 64-bit
-// division per element for its flat index).  Same arithmetic per element, 16 bytes per lane and access (4 f32 / 8 bf16), one (b, c) row
-// segment per workgroup: used whenever the rows are 16-byte aligned (L % 4 == 0 resp. L % 8 == 0); the scalar kernels above remain for the rest.
-__device__ __forceinline__ uint4 nt_load16(const uint4 *p) {
-    const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(p));
-    return make_uint4(v[0], v[1], v[2], v[3]);
-}
-template <bool BF> struct VecIO;
-template <> struct VecIO<false> {                              // f32: 4 elements per 16 bytes
-    static constexpr int N = 4;
-    static __device__ __forceinline__ void unpack(const uint4 &d, float (&v)[4]) {
-        v[0] = __uint_as_float(d.x); v[1] = __uint_as_float(d.y); v[2] = __uint_as_float(d.z); v[3] = __uint_as_float(d.w);
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[4]) {
-        return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-    }
-};
-template <> struct VecIO<true> {                               // bf16: 8 elements per 16 bytes
-    static constexpr int N = 8;
-    static __device__ __forceinline__ void unpack(const uint4 &d, float (&v)[8]) {
-        v[0] = bf_lo(d.x); v[1] = bf_hi(d.x); v[2] = bf_lo(d.y); v[3] = bf_hi(d.y);
-        v[4] = bf_lo(d.z); v[5] = bf_hi(d.z); v[6] = bf_lo(d.w); v[7] = bf_hi(d.w);
-    }
-    static __device__ __forceinline__ uint4 pack(const float (&v)[8]) {
-        return make_uint4(cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]), cvt_pk_bf16(v[4], v[5]), cvt_pk_bf16(v[6], v[7]));
-    }
-};
-
-// MODE 0: out = act(x * scale + shift); MODE 1: out = a * (gy * mask) + b * raw + c0 (as rowwise_bf16_kernel / bwd_apply_kernel).  grid (rows, ysplit)
-template <int MODE, bool BF>
-__global__ __launch_bounds__(256) void rowwise_vec_kernel(const uint4 *__restrict__ gy, const uint4 *__restrict__ raw,
-                                                           const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                           const float *__restrict__ ca, const float *__restrict__ cb,
-                                                           const float *__restrict__ cc, uint4 *__restrict__ out, int C, int Lv)
-{
-    constexpr int N = VecIO<BF>::N;
-    const long long row = blockIdx.x;
-    const int c = (int)(row % C);
-    const float sc = scale[c], sh = shift[c];
-    const float a = MODE == 1 ? ca[c] : 0.f, b = MODE == 1 ? cb[c] : 0.f, c0 = MODE == 1 ? cc[c] : 0.f;
-    const uint4 *r = raw + row * Lv, *g = MODE == 1 ? gy + row * Lv : nullptr;
-    uint4 *o = out + row * Lv;
-    for (int t = blockIdx.y * 256 + threadIdx.x; t < Lv; t += gridDim.y * 256) {
-        float rv[N], gv[N], ov[N];
-        VecIO<BF>::unpack(nt_load16(r + t), rv);
-        if constexpr (MODE == 1) VecIO<BF>::unpack(nt_load16(g + t), gv);
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-            if constexpr (MODE == 0) {
-                float v = __fmaf_rn(rv[e], sc, sh);
-                if (relu) v = (v < 0.f) ? 0.f : v;
-                ov[e] = v;
-            } else {
-                float gg = gv[e];
-                if (relu && !(__fmaf_rn(rv[e], sc, sh) > 0.f)) gg = 0.f;
-                ov[e] = __fmaf_rn(a, gg, __fmaf_rn(b, rv[e], c0));
-            }
-        }
-        o[t] = VecIO<BF>::pack(ov);
-    }
-}
-
-// per-channel (sum of gy * mask, sum of gy * mask * raw), or with raw == nullptr (sum of gy, sum of gy^2): grid (segments, C, B);
-// f64 accumulation per element as in the scalar kernels, one pair of f64 atomics per workgroup
-constexpr int SV_BG = 8;                       // clouds per workgroup of the statistics pass
-template <bool BF>
-__global__ __launch_bounds__(256) void stats_vec_kernel(const uint4 *__restrict__ gy, const uint4 *__restrict__ raw,
-                                                         const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                         int B, int bg /*clouds per workgroup*/, int C, int Lv, double *__restrict__ ws)
-{
-    constexpr int N = VecIO<BF>::N;
-    const int c = blockIdx.y;
-    const float sc = raw ? scale[c] : 0.f, sh = raw ? shift[c] : 0.f;
-    double s1 = 0.0, s2 = 0.0;
-    // a workgroup walks its segment of the channel's row in bg (= SV_BG on big launches) clouds: one wave reduction + one pair of f64 atomics per ~240 KB
-    // instead of per 30 KB (a workgroup per (segment, channel, cloud) ran at 3.0 TB/s on the bf16 step's tensors)
-    for (int bb = blockIdx.z * bg; bb < min(B, (int)(blockIdx.z + 1) * bg); ++bb) {
-    const long long row = (long long)bb * C + c;
-    const uint4 *g = gy + row * Lv, *r = raw ? raw + row * Lv : nullptr;
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < Lv; t += gridDim.x * 256) {
-        float gv[N], rv[N];
-        VecIO<BF>::unpack(nt_load16(g + t), gv);
-        if (raw) VecIO<BF>::unpack(nt_load16(r + t), rv);
-        // the N values of one access are summed in f32 (pairwise), then carried in f64: N x fewer f64 operations (they run at half the
-        // f32 rate and were what bounded the bf16 pass: 3.0 TB/s), error <= N 2^-24 of one access's partial
-        float p1[N], p2[N];
-#pragma unroll
-        for (int e = 0; e < N; ++e) {
-            if (raw) {
-                float gg = gv[e];
-                if (relu && !(__fmaf_rn(rv[e], sc, sh) > 0.f)) gg = 0.f;
-                p1[e] = gg;
-                p2[e] = gg * rv[e];
-            } else {
-                p1[e] = gv[e];
-                p2[e] = gv[e] * gv[e];
-            }
-        }
-#pragma unroll
-        for (int w = N / 2; w > 0; w >>= 1)
-#pragma unroll
-            for (int e = 0; e < w; ++e) { p1[e] += p1[e + w]; p2[e] += p2[e + w]; }
-        s1 += (double)p1[0];
-        s2 += (double)p2[0];
-    }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s1 += __shfl_down(s1, off, 64);
-        s2 += __shfl_down(s2, off, 64);
-    }
-    __shared__ double red[2][4];
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsafeAtomicAdd(&ws[c], (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
-        unsafeAtomicAdd(&ws[C + c], (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
-    }
-}
-
-static bool vec_ok(int L, int elem_bytes, const void *p0, const void *p1, const void *p2)
-{
-    return ((long long)L * elem_bytes) % 16 == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0;
-}
-template <int MODE, bool BF>
-static void launch_rowwise_vec(const void *gy, const void *raw, const float *scale, const float *shift, int relu, const float *a, const float *b,
-                               const float *c0, void *out, long long rows, int C, int L, hipStream_t st)
-{
-    const int Lv = (int)((long long)L * (BF ? 2 : 4) / 16);
-    int ys = sonet::ceil_div(Lv, 256 * 4);
-    ys = ys < 1 ? 1 : (ys > 16 ? 16 : ys);
-    hipLaunchKernelGGL((rowwise_vec_kernel<MODE, BF>), dim3((unsigned)rows, (unsigned)ys), dim3(256), 0, st, reinterpret_cast<const uint4 *>(gy),
-                       reinterpret_cast<const uint4 *>(raw), scale, shift, relu, a, b, c0, reinterpret_cast<uint4 *>(out), C, Lv);
-}
-template <bool BF>
-static void launch_stats_vec(const void *gy, const void *raw, const float *scale, const float *shift, int relu, int B, int C, int L, double *sums,
-                             hipStream_t st)
-{
-    const int Lv = (int)((long long)L * (BF ? 2 : 4) / 16);
-    int seg = sonet::ceil_div(Lv, 256 * 4);
-    seg = seg < 1 ? 1 : (seg > 8 ? 8 : seg);
-    // (small launches keep one cloud per workgroup: the grid must still fill the chip)
-    const int bg = (long long)seg * C * sonet::ceil_div(B, SV_BG) >= 2048 ? SV_BG : 1;
-    hipLaunchKernelGGL((stats_vec_kernel<BF>), dim3((unsigned)seg, (unsigned)C, (unsigned)sonet::ceil_div(B, bg)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(gy), reinterpret_cast<const uint4 *>(raw), scale, shift, relu, B, bg, C, Lv, sums);
-}
-}  // namespace
-
-static bool bf_pair_ok(int L, const void *p0, const void *p1, const void *p2)
-{
-    return (L % 2 == 0) && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 3) == 0;
-}
-
-// bf16 twins (raw bfloat16 bit patterns [B][C][L]); sums / coefficients stay f64 / f32 exactly as in the f32 entry points.
-// sonet_channel_stats_bf16: raw == NULL in the stats kernel -> (sum, sum of squares) -> mean, biased variance.
-extern "C" int sonet_pointwise_bwd_stats_bf16(const uint16_t *gy, const uint16_t *raw, const float *scale, const float *shift,
-                                              int relu, int B, int C, int L, double *sums, sonet_stream_t stream)
-{
-    const char *what = "sonet_pointwise_bwd_stats_bf16";
-    SONET_REQUIRE(gy && raw && scale && shift && sums, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0 && C <= 65535, "%s: bad size", what);
-    hipStream_t st = sonet::as_stream(stream);
-    hipLaunchKernelGGL(bwd_ws_zero_kernel, dim3(sonet::ceil_div(2 * C, 256)), dim3(256), 0, st, sums, 2 * C);
-    const long long per_c = (long long)B * L;
-    int chunks = (int)sonet::ceil_div64(per_c, 16384);
-    chunks = chunks < 1 ? 1 : (chunks > 64 ? 64 : chunks);
-    if (vec_ok(L, 2, gy, raw, nullptr) && B <= 65535) launch_stats_vec<true>(gy, raw, scale, shift, relu, B, C, L, sums, st);
-    else if (bf_pair_ok(L, gy, raw, nullptr)) hipLaunchKernelGGL(bwd_stats_bf16_kernel<true>, dim3(chunks, C), dim3(BW_THREADS), 0, st, gy, raw, scale, shift, relu, B, C, L, sums);
-    else hipLaunchKernelGGL(bwd_stats_bf16_kernel<false>, dim3(chunks, C), dim3(BW_THREADS), 0, st, gy, raw, scale, shift, relu, B, C, L, sums);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_channel_stats_bf16(const uint16_t *y, int B, int C, int L, double *sums, float *mean, float *var, sonet_stream_t stream)
-{
-    const char *what = "sonet_channel_stats_bf16";
-    SONET_REQUIRE(y && sums && mean && var, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0 && C <= 65535, "%s: bad size", what);
-    hipStream_t st = sonet::as_stream(stream);
-    hipLaunchKernelGGL(bwd_ws_zero_kernel, dim3(sonet::ceil_div(2 * C, 256)), dim3(256), 0, st, sums, 2 * C);
-    const long long per_c = (long long)B * L;
-    int chunks = (int)sonet::ceil_div64(per_c, 16384);
-    chunks = chunks < 1 ? 1 : (chunks > 64 ? 64 : chunks);
-    if (vec_ok(L, 2, y, nullptr, nullptr) && B <= 65535) launch_stats_vec<true>(y, nullptr, nullptr, nullptr, 0, B, C, L, sums, st);
-    else if (bf_pair_ok(L, y, nullptr, nullptr)) hipLaunchKernelGGL(bwd_stats_bf16_kernel<true>, dim3(chunks, C), dim3(BW_THREADS), 0, st, y, (const uint16_t *)nullptr, (const float *)nullptr, (const float *)nullptr, 0, B, C, L, sums);
-    else hipLaunchKernelGGL(bwd_stats_bf16_kernel<false>, dim3(chunks, C), dim3(BW_THREADS), 0, st, y, (const uint16_t *)nullptr, (const float *)nullptr, (const float *)nullptr, 0, B, C, L, sums);
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(sonet::ceil_div(C, 256)), dim3(256), 0, st, sums, C, 1.0 / ((double)B * L), mean, var, sonet::take_bn_rider());
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_pointwise_bwd_apply_bf16(const uint16_t *gy, const uint16_t *raw, const float *scale, const float *shift, int relu,
-                                              const float *a, const float *b, const float *c0, uint16_t *g_raw, int B, int C, int L,
-                                              sonet_stream_t stream)
-{
-    const char *what = "sonet_pointwise_bwd_apply_bf16";
-    SONET_REQUIRE(gy && raw && scale && shift && a && b && c0 && g_raw, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0, "%s: bad size", what);
-    const long long rows = (long long)B * C;
-    if (rows > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many rows", what);
-    int ysplit = sonet::ceil_div(L, 256 * 8);
-    ysplit = ysplit < 1 ? 1 : (ysplit > 16 ? 16 : ysplit);
-    dim3 grid((unsigned)rows, (unsigned)ysplit);
-    if (vec_ok(L, 2, gy, raw, g_raw)) launch_rowwise_vec<1, true>(gy, raw, scale, shift, relu, a, b, c0, g_raw, rows, C, L, sonet::as_stream(stream));
-    else if (bf_pair_ok(L, gy, raw, g_raw)) hipLaunchKernelGGL((rowwise_bf16_kernel<1, true>), grid, dim3(256), 0, sonet::as_stream(stream), gy, raw, scale, shift, relu, a, b, c0, g_raw, C, L);
-    else hipLaunchKernelGGL((rowwise_bf16_kernel<1, false>), grid, dim3(256), 0, sonet::as_stream(stream), gy, raw, scale, shift, relu, a, b, c0, g_raw, C, L);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_channel_affine_act_out_bf16(const uint16_t *x, const float *scale, const float *shift, int relu, uint16_t *y,
-                                                 int B, int C, int L, sonet_stream_t stream)
-{
-    const char *what = "sonet_channel_affine_act_out_bf16";
-    SONET_REQUIRE(x && scale && shift && y, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0, "%s: bad size", what);
-    const long long rows = (long long)B * C;
-    if (rows > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: too many rows", what);
-    int ysplit = sonet::ceil_div(L, 256 * 8);
-    ysplit = ysplit < 1 ? 1 : (ysplit > 16 ? 16 : ysplit);
-    dim3 grid((unsigned)rows, (unsigned)ysplit);
-    if (vec_ok(L, 2, x, y, nullptr)) launch_rowwise_vec<0, true>(nullptr, x, scale, shift, relu, nullptr, nullptr, nullptr, y, rows, C, L, sonet::as_stream(stream));
-    else if (bf_pair_ok(L, x, y, nullptr)) hipLaunchKernelGGL((rowwise_bf16_kernel<0, true>), grid, dim3(256), 0, sonet::as_stream(stream), (const uint16_t *)nullptr, x, scale, shift, relu, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, y, C, L);
-    else hipLaunchKernelGGL((rowwise_bf16_kernel<0, false>), grid, dim3(256), 0, sonet::as_stream(stream), (const uint16_t *)nullptr, x, scale, shift, relu, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, y, C, L);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_bn_fwd_coeffs_f32(const float *mean, const float *var, const float *gamma, const float *beta, float eps, int C,
-                                       float *invstd, float *scale, float *shift, sonet_stream_t stream)
-{
-    const char *what = "sonet_bn_fwd_coeffs_f32";
-    SONET_REQUIRE(mean && var && gamma && beta && invstd && scale && shift, "%s: NULL pointer", what);
-    SONET_REQUIRE(C > 0, "%s: bad size C=%d", what, C);
-    hipLaunchKernelGGL(bn_fwd_coeffs_kernel, dim3(sonet::ceil_div(C, 256)), dim3(256), 0, sonet::as_stream(stream),
-                       mean, var, gamma, beta, eps, C, invstd, scale, shift);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_bn_running_update_f32(float *running_mean, float *running_var, const float *mean, const float *var,
-                                          float momentum, float unbias, int C, sonet_stream_t stream)
-{
-    const char *what = "sonet_bn_running_update_f32";
-    SONET_REQUIRE(running_mean && running_var && mean && var, "%s: NULL pointer", what);
-    SONET_REQUIRE(C > 0, "%s: bad size C=%d", what, C);
-    hipLaunchKernelGGL(bn_running_update_kernel, dim3(sonet::ceil_div(C, 256)), dim3(256), 0, sonet::as_stream(stream),
-                       running_mean, running_var, mean, var, momentum, unbias, C);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_bn_bwd_coeffs_f32(const double *sums, const float *mean, const float *invstd, const float *gamma, double n, int C,
-                                       float *a, float *b, float *c0, float *g_gamma, float *g_beta, sonet_stream_t stream)
-{
-    const char *what = "sonet_bn_bwd_coeffs_f32";
-    SONET_REQUIRE(sums && mean && invstd && gamma && a && b && c0 && g_gamma && g_beta, "%s: NULL pointer", what);
-    SONET_REQUIRE(C > 0 && n > 0, "%s: bad size C=%d", what, C);
-    hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(sonet::ceil_div(C, 256)), dim3(256), 0, sonet::as_stream(stream),
-                       sums, mean, invstd, gamma, n, C, a, b, c0, g_gamma, g_beta);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_pointwise_bwd_stats_f32(const float *gy, const float *raw, const float *scale, const float *shift,
-                                             int relu, int B, int C, int L, double *sums, sonet_stream_t stream)
-{
-    const char *what = "sonet_pointwise_bwd_stats_f32";
-    SONET_REQUIRE(gy && raw && scale && shift && sums, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0 && C <= 65535, "%s: bad size B=%d C=%d L=%d", what, B, C, L);
-    hipStream_t st = sonet::as_stream(stream);
-    hipLaunchKernelGGL(bwd_ws_zero_kernel, dim3(sonet::ceil_div(2 * C, 256)), dim3(256), 0, st, sums, 2 * C);
-    const long long per_c = (long long)B * L;
-    int chunks = (int)sonet::ceil_div64(per_c, 16384);
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    if (vec_ok(L, 4, gy, raw, nullptr) && B <= 65535) launch_stats_vec<false>(gy, raw, scale, shift, relu, B, C, L, sums, st);
-    else hipLaunchKernelGGL(bwd_stats_kernel, dim3(chunks, C), dim3(BW_THREADS), 0, st, gy, raw, scale, shift, relu, B, C, L, sums);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_pointwise_bwd_apply_f32(const float *gy, const float *raw, const float *scale, const float *shift, int relu,
-                                             const float *a, const float *b, const float *c0, float *g_raw,
-                                             int B, int C, int L, sonet_stream_t stream)
-{
-    const char *what = "sonet_pointwise_bwd_apply_f32";
-    SONET_REQUIRE(gy && raw && scale && shift && a && b && c0 && g_raw, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0, "%s: bad size B=%d C=%d L=%d", what, B, C, L);
-    const long long rows = (long long)B * C;
-    SONET_REQUIRE(rows <= 2147483647LL, "%s: too many rows", what);
-    int gx = sonet::ceil_div(L, 256 * 8);
-    if (gx < 1) gx = 1;
-    if (vec_ok(L, 4, gy, raw, g_raw)) launch_rowwise_vec<1, false>(gy, raw, scale, shift, relu, a, b, c0, g_raw, rows, C, L, sonet::as_stream(stream));
-    else hipLaunchKernelGGL(bwd_apply_kernel, dim3((unsigned)rows, gx), dim3(256), 0, sonet::as_stream(stream),
-                            gy, raw, scale, shift, relu, a, b, c0, g_raw, C, L);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_channel_affine_act_out_f32(const float *x, const float *scale, const float *shift, int relu, float *y,
-                                                int B, int C, int L, sonet_stream_t stream)
-{
-    const char *what = "sonet_channel_affine_act_out_f32";
-    SONET_REQUIRE(x && scale && shift && y, "%s: NULL pointer", what);
-    const long long rows = (long long)B * C;
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0 && rows <= 2147483647LL, "%s: bad size B=%d C=%d L=%d", what, B, C, L);
-    int gx = sonet::ceil_div(L, 256 * 8);
-    if (gx < 1) gx = 1;
-    if (vec_ok(L, 4, x, y, nullptr)) launch_rowwise_vec<0, false>(nullptr, x, scale, shift, relu, nullptr, nullptr, nullptr, y, rows, C, L, sonet::as_stream(stream));
-    else hipLaunchKernelGGL(affine_act_out_kernel, dim3((unsigned)rows, gx), dim3(256), 0, sonet::as_stream(stream),
-                            x, scale, shift, relu, y, C, L);
-    return sonet::launched(what);
-}
-
-extern "C" int sonet_node_add_affine_act_f32(float *t, const float *z, const int32_t *min_idx_i32, const float *scale,
-                                             const float *shift, int relu, int B, int C, int L, int M, sonet_stream_t stream)
-{
-    const char *what = "sonet_node_add_affine_act_f32";
-    SONET_REQUIRE(t && z && min_idx_i32 && scale && shift, "%s: NULL pointer", what);
-    const long long rows = (long long)B * C;
-    SONET_REQUIRE(B > 0 && C > 0 && L > 0 && M > 0 && M <= 8192 && rows <= 2147483647LL, "%s: bad size B=%d C=%d L=%d M=%d", what, B, C, L, M);
-    int gy = sonet::ceil_div(L, 256 * 8);
-    if (gy < 1) gy = 1;
-    hipLaunchKernelGGL(node_add_affine_act_kernel, dim3((unsigned)rows, gy), dim3(256), (size_t)M * sizeof(float),
-                       sonet::as_stream(stream), t, z, min_idx_i32, scale, shift, relu, C, L, M);
-    return sonet::launched(what);
-}
-
-// node_gather_lead_kernel takes its quad path on L % 4 == 0 alone: 16-byte loads of gidx and lead, a 16-byte (f32) / 8-byte (bf16) store
-static bool ngl_aligned(int L, int NL, const void *gidx, const void *lead, const void *out, unsigned out_align)
-{
-    if ((L & 3) != 0) return true;
-    return (reinterpret_cast<uintptr_t>(gidx) & 15) == 0 && (NL == 0 || (reinterpret_cast<uintptr_t>(lead) & 15) == 0) &&
-           (reinterpret_cast<uintptr_t>(out) & (out_align - 1)) == 0;
-}
-
-extern "C" int sonet_node_gather_lead_affine_act_f32(const float *z, const int32_t *gidx, const float *lead, const float *wl,
-                                                     const float *scale, const float *shift, int relu, float *out,
-                                                     int B, int C, int L, int M, int NL, sonet_stream_t stream)
-{
-    const char *what = "sonet_node_gather_lead_affine_act_f32";
-    SONET_REQUIRE(z && gidx && scale && shift && out && (NL == 0 || (lead && wl)), "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && B <= 65535 && C > 0 && L > 0 && M > 0 && M <= 1024 && NL >= 0 && NL <= 4, "%s: bad size B=%d C=%d L=%d M=%d NL=%d", what, B, C, L, M, NL);
-    SONET_REQUIRE(ngl_aligned(L, NL, gidx, lead, out, 16), "%s: gidx, lead and out must be 16-byte aligned when L %% 4 == 0 (misaligned)", what);
-    hipLaunchKernelGGL(node_gather_lead_kernel<float>, dim3((unsigned)sonet::ceil_div(C, NGL_CH), (unsigned)B), dim3(NGL_THREADS), (size_t)NGL_CH * (M + 6) * sizeof(float),
-                       sonet::as_stream(stream), z, gidx, lead, wl, scale, shift, relu, out, C, L, M, NL);
-    return sonet::launched(what);
-}
-
-/* bf16 storage of z and out (bfloat16 bit patterns); lead, wl, scale, shift f32 */
-extern "C" int sonet_node_gather_lead_affine_act_bf16(const uint16_t *z, const int32_t *gidx, const float *lead, const float *wl,
-                                                      const float *scale, const float *shift, int relu, uint16_t *out,
-                                                      int B, int C, int L, int M, int NL, sonet_stream_t stream)
-{
-    const char *what = "sonet_node_gather_lead_affine_act_bf16";
-    SONET_REQUIRE(z && gidx && scale && shift && out && (NL == 0 || (lead && wl)), "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && B <= 65535 && C > 0 && L > 0 && M > 0 && M <= 1024 && NL >= 0 && NL <= 4, "%s: bad size B=%d C=%d L=%d M=%d NL=%d", what, B, C, L, M, NL);
-    SONET_REQUIRE(ngl_aligned(L, NL, gidx, lead, out, 8), "%s: gidx and lead must be 16-byte, out 8-byte aligned when L %% 4 == 0 (misaligned)", what);
-    hipLaunchKernelGGL(node_gather_lead_kernel<uint16_t>, dim3((unsigned)sonet::ceil_div(C, NGL_CH), (unsigned)B), dim3(NGL_THREADS), (size_t)NGL_CH * (M + 6) * sizeof(float),
-                       sonet::as_stream(stream), z, gidx, lead, wl, scale, shift, relu, out, C, L, M, NL);
-    return sonet::launched(what);
-}
-
-// ---- mean over the k copies of a point (segmenter head, models/networks.py:331-336) ----------------------------------------------
-// out[r][n] = c * ((h[r][n] + h[r][N + n]) + h[r][2 N + n]),  h [rows][k N], c = 1/3 (k = 3) or 0.5 (k = 2), k = 1: copy -- the
-// reference's own order of the adds and the single multiplication, so the result is bit-identical to the three aten launches it
-// replaces (split + add + add + mul: ~0.1 ms of the segmenter's 1.9 ms at 64 x 256 x 3 x 1024).
-namespace {
-__global__ __launch_bounds__(256) void chunk_mean_kernel(const float *__restrict__ h, float *__restrict__ out, long long rows, int N, int k, float c)
-{
-    const long long r = blockIdx.y;
-    const float *hr = h + r * (long long)k * N;
-    float *orow = out + r * N;
-    const bool vec = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (vec) {
-        const float4 *h4 = reinterpret_cast<const float4 *>(hr);
-        float4 *o4 = reinterpret_cast<float4 *>(orow);
-        const int N4 = N >> 2;
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < N4; i += gridDim.x * 256) {
-            float4 s = h4[i];
-            for (int kk = 1; kk < k; ++kk) {
-                const float4 v = h4[(long long)kk * N4 + i];
-                s.x = __fadd_rn(s.x, v.x); s.y = __fadd_rn(s.y, v.y); s.z = __fadd_rn(s.z, v.z); s.w = __fadd_rn(s.w, v.w);
-            }
-            if (k > 1) { s.x = __fmul_rn(c, s.x); s.y = __fmul_rn(c, s.y); s.z = __fmul_rn(c, s.z); s.w = __fmul_rn(c, s.w); }
-            o4[i] = s;
-        }
-    } else {
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
-            float s = hr[i];
-            for (int kk = 1; kk < k; ++kk) s = __fadd_rn(s, hr[(long long)kk * N + i]);
-            orow[i] = k > 1 ? __fmul_rn(c, s) : s;
-        }
-    }
-}
-}  // namespace
-
-extern "C" int sonet_chunk_mean_f32(const float *h, float *out, long long rows, int N, int k, sonet_stream_t stream)
-{
-    const char *what = "sonet_chunk_mean_f32";
-    SONET_REQUIRE(h && out, "%s: NULL pointer", what);
-    SONET_REQUIRE(rows > 0 && N > 0 && k >= 1, "%s: bad size", what);
-    if (rows > 65535 * 32768ll || k > 3) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: rows=%lld k=%d", what, rows, k);
-    if (rows > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: more than 65535 rows", what);
-    const int gx = sonet::ceil_div(N, 1024) < 1 ? 1 : (sonet::ceil_div(N, 1024) > 8 ? 8 : sonet::ceil_div(N, 1024));
-    hipLaunchKernelGGL(chunk_mean_kernel, dim3((unsigned)gx, (unsigned)rows), dim3(256), 0, sonet::as_stream(stream), h, out, rows, N, k,
-                       k == 3 ? (float)(1.0 / 3.0) : 0.5f);
-    return sonet::launched(what);
-}
 
 // ---- sparse dgrad of the pooled last layer ---------------------------------------------------
 // In the classifier / autoencoder the only consumer of first_pn_out = W4 . [x1; x2] + b is the per-node max-pool
@@ -1295,8 +532,7 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad5_kernel(const int3
                     else {
                         g2[((size_t)b * C2 + (ch - C1)) * L + l] = v[t];
                         if (tail.sraw) {
-                            float gm = v[t];
-                            if (tail.srelu && !(__fmaf_rn(rw[t], sc[t], sh[t]) > 0.f)) gm = 0.f;
+                            const float gm = relu_masked(v[t], rw[t], sc[t], sh[t], tail.srelu);
                             s1 = gm;
                             s2 = gm * rw[t];
                         }
@@ -1814,149 +1050,5 @@ extern "C" int sonet_pooled_dgrad_mfma_bf16(const float *g_pooled, const int32_t
     }
 #undef PM_LAUNCH1
 #undef PM_LAUNCH
-    return sonet::launched(what);
-}
-
-// ---- small-batch fully connected layer (classifier / decoder heads in eval mode) --------------------------------------
-// y[b][o] = act((sum_k x[b][k] * W[o][k]) * scale[o] + shift[o]),  x [B][Cin], W [Cout][Cin] (nn.Linear layout), exact f32
-// fma chains.  MyLinear (models/layers.py:123-166) on a B x C feature: three of these (1024 -> 512 -> 256 -> 40)
-// replace ~12 aten launches (GEMM + bias, batch-norm transform, clamp).
-namespace {
-// The layer is a latency problem (67 MFLOP at B = 64, three of them in a row): the work is cut into many small workgroups and
-// every memory request of a thread is in flight before its first fma.  One workgroup = FC_ROWS = 16 rows x FC_OC = 8 outputs;
-// thread (row, ks) owns every 16th float4 of its row (the 16 ks lanes of a row read 256 consecutive bytes), its 8 weight rows
-// sit in LDS in the order the lanes walk k (ws[k % 4][k / 4][8]: the 16 lanes of an LDS read touch consecutive 32-byte slots);
-// the 16 k slices of a row meet in LDS and are summed in a fixed order.  1024 -> 512 at B = 64: 256 workgroups.
-// (Round 1: 64 rows x 2-4 outputs per workgroup, every lane reading its own row -- 64 cache lines per load instruction -- and
-// each workgroup pulling all of x: 22 us.  A version that staged x through LDS in chunks, 64 workgroups: 29-34 us, one wave per
-// SIMD waiting for each chunk.)
-constexpr int FC_ROWS = 16, FC_OC = 8, FC_KS = 16, FC_MAXJ = 16;   // FC_MAXJ float4 per thread and pass: 1024 columns
-template <bool MULTI /*Cin > 1024: more than one pass*/>
-__global__ __launch_bounds__(256) void linear_act_kernel(const float *__restrict__ x, const float *__restrict__ W,
-                                                          const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                                                          float *__restrict__ y, int B, int Cin, int Cout, int nj /*float4 per thread*/)
-{
-    extern __shared__ __attribute__((aligned(16))) float fc_lds[];   // ws[4][K4][8] | part[16][16][8]
-    const int K4 = nj * FC_KS;                                    // padded Cin / 4
-    float *ws = fc_lds;
-    float *part = ws + (size_t)4 * K4 * FC_OC;
-    const int ks = threadIdx.x & 15, rr = threadIdx.x >> 4;
-    const int o0 = blockIdx.x * FC_OC, row = blockIdx.y * FC_ROWS + rr;
-    const bool vec = (Cin & 3) == 0;
-    // x first: the requests travel while the weights are staged.  A pass covers FC_MAXJ float4 per thread = 1024 columns; wider layers
-    // (Cin up to 4096: the weights of all passes sit in LDS) run the pass loop again with the accumulators kept.
-    float4 xv[FC_MAXJ];
-    auto fetch = [&](int j0) {
-#pragma unroll
-        for (int j = 0; j < FC_MAXJ; ++j) {
-            xv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            const int k = ((j0 + j) * FC_KS + ks) * 4;
-            if (j0 + j < nj && row < B && k < Cin) {
-                const float *src = x + (size_t)row * Cin + k;
-                if (vec) xv[j] = *reinterpret_cast<const float4 *>(src);
-                else {
-                    xv[j].x = src[0];
-                    if (k + 1 < Cin) xv[j].y = src[1];
-                    if (k + 2 < Cin) xv[j].z = src[2];
-                    if (k + 3 < Cin) xv[j].w = src[3];
-                }
-            }
-        }
-    };
-    fetch(0);
-    // weights: float4 along k, eight requests per thread in flight at a time; zero past Cin / Cout
-    for (int i0 = 0; i0 < FC_OC * K4; i0 += 8 * 256) {
-        float4 wv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * 256 + (int)threadIdx.x, q = i / K4, k = (i - q * K4) * 4;
-            wv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < FC_OC * K4 && o0 + q < Cout && k < Cin) {
-                const float *src = W + (size_t)(o0 + q) * Cin + k;
-                if (vec) wv[u] = *reinterpret_cast<const float4 *>(src);
-                else {
-                    wv[u].x = src[0];
-                    if (k + 1 < Cin) wv[u].y = src[1];
-                    if (k + 2 < Cin) wv[u].z = src[2];
-                    if (k + 3 < Cin) wv[u].w = src[3];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int i = i0 + u * 256 + (int)threadIdx.x, q = i / K4, k4 = i - q * K4;
-            if (i < FC_OC * K4) {
-                ws[(0 * K4 + k4) * FC_OC + q] = wv[u].x;
-                ws[(1 * K4 + k4) * FC_OC + q] = wv[u].y;
-                ws[(2 * K4 + k4) * FC_OC + q] = wv[u].z;
-                ws[(3 * K4 + k4) * FC_OC + q] = wv[u].w;
-            }
-        }
-    }
-    __syncthreads();
-    float acc[FC_OC];
-#pragma unroll
-    for (int q = 0; q < FC_OC; ++q) acc[q] = 0.f;
-    for (int j0 = 0; j0 < (MULTI ? nj : 1); j0 += FC_MAXJ) {   // (single pass: straight-line code, measured 1.6 us faster on 1024 -> 512)
-        if (MULTI && j0 > 0) fetch(j0);
-#pragma unroll
-        for (int j = 0; j < FC_MAXJ; ++j) {
-            if (j0 + j < nj) {
-                const float xe[4] = {xv[j].x, xv[j].y, xv[j].z, xv[j].w};
-                const float4 *wp = reinterpret_cast<const float4 *>(ws + (size_t)((j0 + j) * FC_KS + ks) * FC_OC);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float4 w0 = wp[(size_t)e * K4 * 2], w1 = wp[(size_t)e * K4 * 2 + 1];
-                    acc[0] = __fmaf_rn(xe[e], w0.x, acc[0]); acc[1] = __fmaf_rn(xe[e], w0.y, acc[1]);
-                    acc[2] = __fmaf_rn(xe[e], w0.z, acc[2]); acc[3] = __fmaf_rn(xe[e], w0.w, acc[3]);
-                    acc[4] = __fmaf_rn(xe[e], w1.x, acc[4]); acc[5] = __fmaf_rn(xe[e], w1.y, acc[5]);
-                    acc[6] = __fmaf_rn(xe[e], w1.z, acc[6]); acc[7] = __fmaf_rn(xe[e], w1.w, acc[7]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < FC_OC; ++q) part[(rr * FC_KS + ks) * FC_OC + q] = acc[q];
-    __syncthreads();
-    if (threadIdx.x < FC_ROWS * FC_OC) {
-        const int r2 = threadIdx.x >> 3, q = threadIdx.x & 7;
-        const int o = o0 + q, row2 = blockIdx.y * FC_ROWS + r2;
-        if (o < Cout && row2 < B) {
-            float sum = 0.f;
-#pragma unroll
-            for (int t = 0; t < FC_KS; ++t) sum += part[(r2 * FC_KS + t) * FC_OC + q];
-            float v = __fmaf_rn(sum, scale[o], shift[o]);
-            if (relu) v = (v < 0.f) ? 0.f : v;
-            y[(size_t)row2 * Cout + o] = v;
-        }
-    }
-}
-}  // namespace
-
-extern "C" int sonet_linear_act_f32(const float *x, const float *W, const float *scale, const float *shift, int relu, float *y,
-                                    int B, int Cin, int Cout, sonet_stream_t stream)
-{
-    const char *what = "sonet_linear_act_f32";
-    SONET_REQUIRE(x && W && scale && shift && y, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0, "%s: non-positive size", what);
-    // (the kernel reads x and W with 16-byte loads whenever Cin % 4 == 0: the rows then start on a 16-byte boundary iff the bases do)
-    SONET_REQUIRE((Cin & 3) != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) & 15) == 0,
-                  "%s: x and W must be 16-byte aligned when Cin %% 4 == 0 (misaligned)", what);
-    const int rows = sonet::ceil_div(B, FC_ROWS);
-    if (rows > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B=%d too large", what, B);
-    const int nj = sonet::ceil_div(Cin, 4 * FC_KS);
-    if (Cin > 4096) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cin=%d too large (max 4096: the workgroup's 8 weight rows sit in LDS)", what, Cin);
-    const size_t lds = ((size_t)4 * nj * FC_KS * FC_OC + FC_ROWS * FC_KS * FC_OC) * sizeof(float);
-    dim3 grid(sonet::ceil_div(Cout, FC_OC), rows), block(256);
-    hipStream_t st = sonet::as_stream(stream);
-    static bool raised = false;                                   // (dynamic LDS above 64 KiB has to be asked for: Cin > 1792)
-    if (lds > 64 * 1024 && !raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_act_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_act_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
-            return sonet::fail(SONET_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit", what);
-        raised = true;
-    }
-    if (nj > FC_MAXJ) hipLaunchKernelGGL(linear_act_kernel<true>, grid, block, lds, st, x, W, scale, shift, relu, y, B, Cin, Cout, nj);
-    else              hipLaunchKernelGGL(linear_act_kernel<false>, grid, block, lds, st, x, W, scale, shift, relu, y, B, Cin, Cout, nj);
     return sonet::launched(what);
 }

@@ -1,4 +1,4 @@
-"""Float64 restatement of the BatchNorm / ReLU passes (csrc/pointwise_bwd.hip, the statistics and affine kernels of csrc/pointmlp.hip) and
+"""Float64 restatement of the BatchNorm / ReLU passes (csrc/bn_passes.hip) and
 the seeded inputs of tests/test_gpu_bn_passes.py.  Plain numpy, no GPU, nothing from sonet_hip: tests/test_bn_passes_cpu.py pins this file
 to float64 autograd of F.batch_norm, the GPU tests pin the kernels to this file.
 
@@ -228,11 +228,11 @@ def _store(v, bf16):
     return round_bf16(v) if bf16 else v
 
 
-# Element-wise passes.  Dispatch (pointwise_bwd.hip): 16 bytes per lane when L * elem_bytes % 16 == 0 and every pointer is 16-byte aligned
+# Element-wise passes.  Dispatch (bn_passes.hip): 16 bytes per lane when L * elem_bytes % 16 == 0 and every pointer is 16-byte aligned
 # (rowwise_vec_kernel; gridDim.y = ceil(Lv / 1024), Lv = L / 4 resp. L / 8); bf16 otherwise: dword pairs when L is even and the pointers
-# 4-byte aligned (rowwise_bf16_kernel<., true>), else one element per lane (<., false>), gridDim.y = ceil(L / 2048); f32 otherwise:
-# bwd_apply_kernel / affine_act_out_kernel, gridDim.y = ceil(L / 2048).  channel_affine_act_ (in place, f32) is always the flat kernel of
-# pointmlp.hip.  A grid row strides by 256 * gridDim.y lanes.
+# 4-byte aligned (rowwise_kernel<., uint16_t, true>), else one element per lane (<., uint16_t, false>), gridDim.y = ceil(L / 2048); f32
+# otherwise: rowwise_kernel<., float, false>, gridDim.y = ceil(L / 2048).  channel_affine_act_ (in place, f32) is always the flat
+# channel_affine_act_kernel.  A grid row strides by 256 * gridDim.y lanes.
 def _elementwise_cases():
     cs = []
     for B, C in ((3, 5), (1, 1)):
@@ -303,9 +303,9 @@ def nan_inputs(case):
     return d
 
 
-# Statistics.  pointwise_bwd_stats f32: stats_vec_kernel<false> when L % 4 == 0 and aligned, else bwd_stats_kernel (chunks = ceil(B L / 16384)
-# of a flat (b, l) index per channel).  bf16 (and channel_stats bf16): stats_vec_kernel<true> when L % 8 == 0 and aligned, else
-# bwd_stats_bf16_kernel<true> (L even, 4-byte aligned; Lv = L / 2) or <false>.  channel_stats f32 is always channel_stats_kernel (scalar).
+# Statistics.  pointwise_bwd_stats f32: stats_vec_kernel<false> when L % 4 == 0 and aligned, else stats_scalar_kernel<float, false, .> (chunks =
+# ceil(B L / 16384) of a flat (b, l) index per channel).  bf16 (and channel_stats bf16): stats_vec_kernel<true> when L % 8 == 0 and aligned, else
+# stats_scalar_kernel<uint16_t, true, .> (L even, 4-byte aligned; Lv = L / 2) or <uint16_t, false, .>.  channel_stats f32 is always the scalar kernel.
 # stats_vec_kernel: seg = min(8, ceil(Lv / 1024)) segments per row; 8 clouds per workgroup once seg * C * ceil(B / 8) >= 2048.
 def _stats_cases():
     cs = []

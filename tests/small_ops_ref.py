@@ -1,5 +1,5 @@
 """Numpy restatements of the node-level gather, max, FC and Adam kernels (csrc/som.hip, csrc/node_train.hip, the node / FC kernels of
-csrc/pointwise_bwd.hip, csrc/optim.hip) and the seeded inputs of tests/test_gpu_small_ops.py.  Plain numpy, no torch, nothing from sonet_hip:
+csrc/bn_passes.hip, csrc/fc_head.hip, csrc/optim.hip) and the seeded inputs of tests/test_gpu_small_ops.py.  Plain numpy, no torch, nothing from sonet_hip:
 tests/test_small_ops_cpu.py pins this file to the reference's torch expressions on the CPU, the GPU tests pin the kernels to this file.
 
 Every restatement follows the kernel's documented expression in the kernel's own operation order, in the dtype of its inputs (float32: the

@@ -1,7 +1,13 @@
 """tests/bn_passes_ref.py -- the float64 restatement tests/test_gpu_bn_passes.py holds the BatchNorm / ReLU kernels to -- against float64
 autograd of F.batch_norm, and the properties of the seeded inputs the GPU tests rely on: no float64 result near a rounding midpoint (so
 that a float64 emulation of an fma may be compared bit for bit), bf16 inputs that hold bf16 values, and sum bounds that a single dropped
-element breaks at every shape."""
+element breaks at every shape.  And the one thing the GPU tests cannot see from Python -- which kernel a shape selects -- against the recorded
+dispatch of the entry points (tests/golden/launch, held to the tree by tests/test_launch_log_cpu.py)."""
+import lzma
+import os
+import re
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -182,3 +188,46 @@ def test_coefficient_inputs_cover_the_edges():
             assert d["var"][0] == 0 and d["mean"][C // 2] * np.sqrt(d["var"][C // 2] + R.EPS) ** -1 > 1000
         invstd, scale, shift = R.fwd_coeffs(d["mean"], d["var"], d["gamma"], d["beta"], R.EPS)
         assert np.isfinite(invstd).all() and (C == 1 or abs(invstd[0] - R.EPS ** -0.5) < 1e-9)
+
+
+# kernel (as the recording names it: a piece of the mangled name, template arguments included) -> flavour of ``Case.path``
+FLAVOUR = [("stats_vec_kernel", "vec"), ("rowwise_vec_kernel", "vec"),
+           ("bwd_stats_bf16_kernelILb1E", "pair"), ("rowwise_bf16_kernelILi0ELb1E", "pair"), ("rowwise_bf16_kernelILi1ELb1E", "pair"),
+           ("bwd_stats_bf16_kernelILb0E", "scalar"), ("rowwise_bf16_kernelILi0ELb0E", "scalar"), ("rowwise_bf16_kernelILi1ELb0E", "scalar"),
+           ("20channel_stats_kernel", "scalar"), ("16bwd_stats_kernel", "scalar"), ("16bwd_apply_kernel", "scalar"), ("21affine_act_out_kernel", "scalar")]
+# the ops of tests/test_gpu_bn_passes.py that run each list (channel_affine_act_ is one flat kernel whatever the shape: no flavour)
+RUNS = [(R.ELEMENTWISE, ("channel_affine_act_out", "pointwise_bwd_apply")),
+        (R.MASK_EDGE, ("channel_affine_act_out", "pointwise_bwd_apply", "pointwise_bwd_stats")),
+        (R.STATS, ("pointwise_bwd_stats", "channel_stats"))]
+
+
+def test_every_case_takes_the_kernel_its_path_names():
+    """``Case.path`` starts with the flavour (vec / pair / scalar) the dispatch rules give the shape; the launch recorder's line for the same
+    call -- entry point, dtype, B, C, L, every operand k elements into its allocation -- must name a kernel of that flavour.  A Case the
+    recorder's sweep does not hold fails, so the two cannot drift apart.  (channel_stats f32 has no 16-byte kernel: always scalar.)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import launch_log
+    with lzma.open(os.path.join(root, "tests", "golden", "launch", "product.txt.xz"), "rt") as f:
+        text = f.read()
+    recorded, group = {}, None                               # (group, case) -> the launches of the line
+    for line in launch_log.expand(text[text.index("== bn passes: kernels and refusal texts"):]):
+        if line.startswith("# "):
+            group = line[2:]
+        elif line.startswith("  ") and " | " in line:
+            head, launches = line[2:].split(" | ")
+            recorded[(group, head.rsplit(" ", 1)[0])] = launches.split()
+    checked = 0
+    for cases, ops in RUNS:
+        for case in cases:
+            for op in ops:
+                key = ("sonet_%s_%s k=%d" % (op, case.dt, case.k), "%dx%dx%d" % (case.B, case.C, case.L))
+                assert key in recorded, "the recorder's sweep (tools/launch_driver.cpp) does not hold %s %s" % key
+                flavours = [fl for item in recorded[key] for piece, fl in FLAVOUR if piece in item]
+                assert len(flavours) == 1, (key, recorded[key])
+                want = re.split(r"[ ,:]", case.path)[0]
+                if op == "channel_stats" and not case.bf16:
+                    want = "scalar"
+                assert flavours[0] == want, (key, case.path, recorded[key])
+                checked += 1
+    assert checked == 2 * len(R.ELEMENTWISE) + 3 * len(R.MASK_EDGE) + 2 * len(R.STATS)

@@ -3,7 +3,8 @@ tests/test_bn_passes_cpu.py, which also asserts what the bit-equality below rest
 
 These kernels are the reference side of the suite's bit-identity tests (normalise-on-load, BatchNorm-backward-on-load, the statistics
 epilogues, the BatchNorm rider of the training goldens); here they are the side under test.  The kernel a shape selects cannot be observed
-from Python: it follows from the dispatch rules of csrc/pointwise_bwd.hip, restated next to the shapes in bn_passes_ref.py (``Case.path``).
+from Python: it follows from the dispatch rules of csrc/bn_passes.hip, restated next to the shapes in bn_passes_ref.py (``Case.path``), and
+tests/test_bn_passes_cpu.py holds every ``Case.path`` to the kernel the launch recorder names for that call.
 
 Bounds (none measured): element-wise results bit-equal; sums within 1e-12 (scalar kernels: every term in f64) resp. (log2 N + 1) 2^-24
 (16-byte kernels: one product rounding + a pairwise f32 sum of N = 4 / 8 values) of the sum of the terms' magnitudes; mean / var through

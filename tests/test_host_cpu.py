@@ -378,7 +378,7 @@ def test_data_flow_knobs_default_to_what_was_measured_faster():
 
 
 def test_host_model_of_the_entry_balanced_sparse_input_gradient():
-    """The chunk logic of pooled_dgrad5_kernel (csrc/pointwise_bwd.hip) restated on the host for one channel: a round's sorted entries cut into
+    """The chunk logic of pooled_dgrad5_kernel (csrc/pooled_bwd.hip) restated on the host for one channel: a round's sorted entries cut into
     sixteen chunks of equal length (the first n % 16 one longer, so the non-empty chunks are the first ones); a chunk whose first column began
     in the chunk before starts it from zero and parks the partial sum; after the round the first parked chunk of a run on one column adds the
     run to the accumulator in chunk order; a column that continues from the previous ROUND resumes from the accumulator.  Integer-valued

@@ -1,5 +1,11 @@
 """tools/bench_bwd_passes.py -- the element-wise passes of the training step (BatchNorm / ReLU backward statistics and apply, forward
-statistics, normalise + ReLU) on B x C x 15000 tensors, bf16 and f32, against the HBM roofline (bytes read + written, once)."""
+statistics, normalise + ReLU) on B x C x L tensors, bf16 and f32, against the HBM roofline (bytes read + written, once).
+
+  --L N        row length (default 15000: the 16-byte kernels; 15001: the one-element kernels; 15002: bf16 pairs, f32 one element)
+  --offset K   every tensor K elements into its allocation (1: one element per lane in either dtype; 2: bf16 pairs)
+  --C a,b,...  channel counts (default 64,128,256)
+  --it N       timed calls per row (default 20)"""
+import argparse
 import os
 import sys
 
@@ -7,10 +13,24 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 from sonet_hip import ops  # noqa: E402
 
-DEV, B, L = "cuda:0", 64, 15000
+ap = argparse.ArgumentParser()
+ap.add_argument("--L", type=int, default=15000)
+ap.add_argument("--offset", type=int, default=0)
+ap.add_argument("--C", default="64,128,256")
+ap.add_argument("--it", type=int, default=20)
+args = ap.parse_args()
+DEV, B, L = "cuda:0", 64, args.L
 
 
-def t(fn, it=20):
+def view(x):
+    """x [B][C][L] on the device, args.offset elements into a flat allocation"""
+    flat = torch.empty(x.numel() + args.offset, dtype=x.dtype, device=DEV)
+    v = flat[args.offset:].view(x.shape)
+    v.copy_(x)
+    return v
+
+
+def t(fn, it=args.it):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -25,10 +45,10 @@ def t(fn, it=20):
 
 for dt in (torch.bfloat16, torch.float32):
     eb = 2 if dt == torch.bfloat16 else 4
-    for C in (64, 128, 256):
+    for C in [int(c) for c in args.C.split(",")]:
         g = torch.Generator().manual_seed(C)
-        gy = torch.randn(B, C, L, generator=g).to(dt).to(DEV)
-        raw = torch.randn(B, C, L, generator=g).to(dt).to(DEV)
+        gy = view(torch.randn(B, C, L, generator=g).to(dt))
+        raw = view(torch.randn(B, C, L, generator=g).to(dt))
         sc, sh = (torch.rand(C, generator=g) + 0.5).to(DEV), torch.randn(C, generator=g).to(DEV)
         a, b, c0 = torch.randn(C, generator=g).to(DEV), torch.randn(C, generator=g).to(DEV), torch.randn(C, generator=g).to(DEV)
         n = B * C * L

@@ -2,7 +2,8 @@
 // dereferenced on the host) against tools/launch_stub.cpp and prints one line per case:
 //   group \t case \t return code \t sonet_last_error() when refused \t the launches the stub recorded
 // group = entry point, optional features and channel pair; case = B x L and whatever else varies inside the group.
-// argv[1..]: group prefixes to run (none: all).  Built with -DSONET_VARIANTS for the variants library's extra entry points.
+// argv[1..]: group prefixes to run (none: all); "@bn": the family of the BatchNorm / ReLU passes (run_bn_* below) instead of the layer
+// launchers.  Built with -DSONET_VARIANTS for the variants library's extra entry points.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -39,7 +40,9 @@ std::string fmt(const char *f, ...)
 
 bool wanted(const std::string &group)
 {
-    if (g_argc <= 1) return true;
+    bool any = false;
+    for (int i = 1; i < g_argc; ++i) any = any || g_argv[i][0] != '@';
+    if (!any) return true;
     for (int i = 1; i < g_argc; ++i)
         if (group.compare(0, strlen(g_argv[i]), g_argv[i]) == 0) return true;
     return false;
@@ -342,12 +345,225 @@ void run_wgrad()
     one(R, "bf16_xaff null xs", [] { return sonet_wgrad_bf16_xaff(P<h>(1), P<h>(2), P(3), P<void>(4), 2, 64, 64, 64, nullptr, P(6), 1, ST); });
 }
 
+// ---- the BatchNorm / ReLU passes, their node-broadcast forms, the coefficient kernels, the eval-mode head kernels and the pooled sparse
+// gradient ("@bn" in argv: this family INSTEAD of the layer launchers above, so that either half of the recording stands on its own) ----
+struct Args {
+    int B = 3, C = 5, L = 8, M = 64, NL = 3;
+    int null = -1;                              // number of the pointer passed as NULL
+    int off[3] = {0, 0, 0};                     // element offsets of the [B][C][L] operands
+    template <typename T> T *t(int i, int slot) const { return null == i ? nullptr : P<T>(i + 1, off[slot] * (int)sizeof(T)); }
+    template <typename T = float> T *v(int i) const { return null == i ? nullptr : P<T>(i + 1); }
+};
+typedef uint16_t bh;
+struct Entry { const char *name; int (*call)(const Args &); int nptr; std::vector<const char *> tensors; };
+const Entry BCL[] = {
+    {"sonet_channel_stats_f32", [](const Args &a) { return sonet_channel_stats_f32(a.t<float>(0, 0), a.B, a.C, a.L, a.v<double>(1), a.v(2), a.v(3), ST); }, 4, {"y"}},
+    {"sonet_channel_stats_bf16", [](const Args &a) { return sonet_channel_stats_bf16(a.t<bh>(0, 0), a.B, a.C, a.L, a.v<double>(1), a.v(2), a.v(3), ST); }, 4, {"y"}},
+    {"sonet_channel_affine_act_f32", [](const Args &a) { return sonet_channel_affine_act_f32(a.t<float>(0, 0), a.v(1), a.v(2), 1, a.B, a.C, a.L, ST); }, 3, {"y"}},
+    {"sonet_channel_affine_act_out_f32", [](const Args &a) { return sonet_channel_affine_act_out_f32(a.t<float>(0, 0), a.v(1), a.v(2), 1, a.t<float>(3, 1), a.B, a.C, a.L, ST); }, 4, {"x", "y"}},
+    {"sonet_channel_affine_act_out_bf16", [](const Args &a) { return sonet_channel_affine_act_out_bf16(a.t<bh>(0, 0), a.v(1), a.v(2), 1, a.t<bh>(3, 1), a.B, a.C, a.L, ST); }, 4, {"x", "y"}},
+    {"sonet_pointwise_bwd_stats_f32", [](const Args &a) { return sonet_pointwise_bwd_stats_f32(a.t<float>(0, 0), a.t<float>(1, 1), a.v(2), a.v(3), 1, a.B, a.C, a.L, a.v<double>(4), ST); }, 5, {"gy", "raw"}},
+    {"sonet_pointwise_bwd_stats_bf16", [](const Args &a) { return sonet_pointwise_bwd_stats_bf16(a.t<bh>(0, 0), a.t<bh>(1, 1), a.v(2), a.v(3), 1, a.B, a.C, a.L, a.v<double>(4), ST); }, 5, {"gy", "raw"}},
+    {"sonet_pointwise_bwd_apply_f32", [](const Args &a) { return sonet_pointwise_bwd_apply_f32(a.t<float>(0, 0), a.t<float>(1, 1), a.v(2), a.v(3), 1, a.v(4), a.v(5), a.v(6), a.t<float>(7, 2), a.B, a.C, a.L, ST); }, 8, {"gy", "raw", "g_raw"}},
+    {"sonet_pointwise_bwd_apply_bf16", [](const Args &a) { return sonet_pointwise_bwd_apply_bf16(a.t<bh>(0, 0), a.t<bh>(1, 1), a.v(2), a.v(3), 1, a.v(4), a.v(5), a.v(6), a.t<bh>(7, 2), a.B, a.C, a.L, ST); }, 8, {"gy", "raw", "g_raw"}},
+    {"sonet_pointwise_bwd_apply_nodesum_f32", [](const Args &a) { return sonet_pointwise_bwd_apply_nodesum_f32(a.t<float>(0, 0), a.t<float>(1, 1), a.v(2), a.v(3), 1, a.v(4), a.v(5), a.v(6), a.v<int32_t>(7), a.M,
+                                                                                                         a.t<float>(8, 2), a.v(9), a.v<void>(10), a.B, a.C, a.L, ST); }, 11, {"gy", "raw", "g_raw"}},
+    {"sonet_node_add_affine_act_f32", [](const Args &a) { return sonet_node_add_affine_act_f32(a.t<float>(0, 0), a.v(1), a.v<int32_t>(2), a.v(3), a.v(4), 1, a.B, a.C, a.L, a.M, ST); }, 5, {"t"}},
+    {"sonet_node_gather_lead_affine_act_f32", [](const Args &a) { return sonet_node_gather_lead_affine_act_f32(a.v(0), a.t<int32_t>(1, 0), a.t<float>(2, 1), a.v(3), a.v(4), a.v(5), 1, a.t<float>(6, 2),
+                                                                                                         a.B, a.C, a.L, a.M, a.NL, ST); }, 7, {"gidx", "lead", "out"}},
+    {"sonet_node_gather_lead_affine_act_bf16", [](const Args &a) { return sonet_node_gather_lead_affine_act_bf16(a.v<bh>(0), a.t<int32_t>(1, 0), a.t<float>(2, 1), a.v(3), a.v(4), a.v(5), 1, a.t<bh>(6, 2),
+                                                                                                           a.B, a.C, a.L, a.M, a.NL, ST); }, 7, {"gidx", "lead", "out"}},
+};
+const int BN_BS[] = {1, 3, 9, 17, 64}, BN_CS[] = {1, 5, 1024};
+const int BN_LS[] = {1, 2, 6, 7, 8, 1023, 1028, 1030, 2049, 2051, 2056, 4100, 5462, 5463, 8200, 8202, 15000, 40000};
+// the statistics pass groups 8 clouds per workgroup once segments * C * ceil(B / 8) >= 2048: both sides, at one and at two segments per row
+const int BN_GROUPING[][3] = {{9, 1024, 8}, {9, 1023, 8}, {8, 1024, 8}, {16, 1024, 8}, {17, 683, 8}, {17, 682, 8}, {9, 512, 4100}, {9, 511, 4100}, {9, 512, 8200}, {9, 511, 8200}};
+
+void bcl_sizes(const Entry &e, const std::string &group, Args a)
+{
+    if (!wanted(group)) return;
+    for (int B : BN_BS) for (int C : BN_CS) for (int L : BN_LS) {
+        a.B = B; a.C = C; a.L = L;
+        report(group, fmt("%dx%dx%d", B, C, L), e.call(a));
+    }
+    for (const auto &g : BN_GROUPING) {
+        a.B = g[0]; a.C = g[1]; a.L = g[2];
+        report(group, fmt("%dx%dx%d", g[0], g[1], g[2]), e.call(a));
+    }
+}
+
+void run_bn_bcl()
+{
+    for (const Entry &e : BCL) {
+        const int nt = (int)e.tensors.size();
+        for (int k = 0; k <= 2; ++k) {                            // every [B][C][L] operand k elements into its allocation
+            Args a;
+            for (int i = 0; i < nt; ++i) a.off[i] = k;
+            bcl_sizes(e, fmt("%s k=%d", e.name, k), a);
+        }
+        for (int i = 0; nt > 1 && i < nt; ++i)                    // ... and one operand alone
+            for (int k = 1; k <= 2; ++k) {
+                Args a;
+                a.off[i] = k;
+                bcl_sizes(e, fmt("%s %s+%d", e.name, e.tensors[i], k), a);
+            }
+        const std::string R = fmt("%s refused", e.name);
+        if (!wanted(R)) continue;
+        for (int L : {8, 7}) {
+            for (int i = 0; i < e.nptr; ++i) { Args a; a.L = L; a.null = i; report(R, fmt("L=%d null pointer %d", L, i), e.call(a)); }
+            { Args a; a.L = L; a.B = 0; report(R, fmt("L=%d B=0", L), e.call(a)); }
+            { Args a; a.L = L; a.C = 0; report(R, fmt("L=%d C=0", L), e.call(a)); }
+            { Args a; a.B = 1; a.L = 0; report(R, fmt("L=0 after %d", L), e.call(a)); }
+            { Args a; a.L = L; a.M = 0; report(R, fmt("L=%d M=0", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 1; a.C = 65535; report(R, fmt("L=%d C=65535", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 1; a.C = 65536; report(R, fmt("L=%d C=65536", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 65535; a.C = 1; report(R, fmt("L=%d B=65535", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 65536; a.C = 1; report(R, fmt("L=%d B=65536", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 32768; a.C = 65535; report(R, fmt("L=%d B*C=2^31-32768", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 32768; a.C = 65536; report(R, fmt("L=%d B*C=2^31", L), e.call(a)); }
+            { Args a; a.L = L; a.B = 65536; a.C = 32768; report(R, fmt("L=%d B*C=2^31 B=65536", L), e.call(a)); }
+            for (int M : {1024, 1025, 8192, 8193}) { Args a; a.L = L; a.M = M; report(R, fmt("L=%d M=%d", L, M), e.call(a)); }
+            for (int NL : {-1, 0, 4, 5}) { Args a; a.L = L; a.NL = NL; report(R, fmt("L=%d NL=%d", L, NL), e.call(a)); }
+            { Args a; a.L = L; a.NL = 0; a.null = 2; report(R, fmt("L=%d NL=0 without lead", L), e.call(a)); }
+            { Args a; a.L = L; a.NL = 0; a.null = 2; a.off[1] = 1; report(R, fmt("L=%d NL=0 without lead misaligned", L), e.call(a)); }
+        }
+    }
+}
+
+void run_bn_coeffs()
+{
+    const int CS[] = {1, 5, 255, 256, 257, 1024, 65535, 65536, 1 << 24};
+    for (int C : CS) {
+        const std::string cs = fmt("C=%d", C);
+        one("sonet_bn_fwd_coeffs_f32", cs.c_str(), [=] { return sonet_bn_fwd_coeffs_f32(P(1), P(2), P(3), P(4), 1e-5f, C, P(5), P(6), P(7), ST); });
+        one("sonet_bn_running_update_f32", cs.c_str(), [=] { return sonet_bn_running_update_f32(P(1), P(2), P(3), P(4), 0.1f, 1.5f, C, ST); });
+        one("sonet_bn_bwd_coeffs_f32", cs.c_str(), [=] { return sonet_bn_bwd_coeffs_f32(P<double>(1), P(2), P(3), P(4), 24.0, C, P(5), P(6), P(7), P(8), P(9), ST); });
+    }
+    auto Q = [](int i, int null) { return i == null ? nullptr : P(i + 1); };
+    const char *R = "sonet_bn coefficients refused";
+    for (int n = 0; n < 7; ++n)
+        one(R, fmt("fwd_coeffs null pointer %d", n).c_str(), [=] { return sonet_bn_fwd_coeffs_f32(Q(0, n), Q(1, n), Q(2, n), Q(3, n), 1e-5f, 5, Q(4, n), Q(5, n), Q(6, n), ST); });
+    for (int n = 0; n < 4; ++n)
+        one(R, fmt("running_update null pointer %d", n).c_str(), [=] { return sonet_bn_running_update_f32(Q(0, n), Q(1, n), Q(2, n), Q(3, n), 0.1f, 1.5f, 5, ST); });
+    for (int n = 0; n < 9; ++n)
+        one(R, fmt("bwd_coeffs null pointer %d", n).c_str(), [=] { return sonet_bn_bwd_coeffs_f32(n == 0 ? nullptr : P<double>(1), Q(1, n), Q(2, n), Q(3, n), 24.0, 5, Q(4, n), Q(5, n), Q(6, n), Q(7, n), Q(8, n), ST); });
+    for (int C : {0, -1}) {
+        one(R, fmt("fwd_coeffs C=%d", C).c_str(), [=] { return sonet_bn_fwd_coeffs_f32(P(1), P(2), P(3), P(4), 1e-5f, C, P(5), P(6), P(7), ST); });
+        one(R, fmt("running_update C=%d", C).c_str(), [=] { return sonet_bn_running_update_f32(P(1), P(2), P(3), P(4), 0.1f, 1.5f, C, ST); });
+        one(R, fmt("bwd_coeffs C=%d", C).c_str(), [=] { return sonet_bn_bwd_coeffs_f32(P<double>(1), P(2), P(3), P(4), 24.0, C, P(5), P(6), P(7), P(8), P(9), ST); });
+    }
+    one(R, "bwd_coeffs n=0", [] { return sonet_bn_bwd_coeffs_f32(P<double>(1), P(2), P(3), P(4), 0.0, 5, P(5), P(6), P(7), P(8), P(9), ST); });
+}
+
+void run_bn_head()
+{
+    for (long long rows : {1ll, 9ll, 65535ll})
+        for (int N : {1, 7, 8, 1024, 1028, 8192, 8196, 9000})
+            for (int k : {1, 2, 3})
+                one("sonet_chunk_mean_f32", fmt("%lldx%d k=%d", rows, N, k).c_str(), [=] { return sonet_chunk_mean_f32(P(1), P(2), rows, N, k, ST); });
+    one("sonet_chunk_mean_f32", "9x8 misaligned h", [] { return sonet_chunk_mean_f32(P(1, 4), P(2), 9, 8, 3, ST); });
+    one("sonet_chunk_mean_f32", "9x8 misaligned out", [] { return sonet_chunk_mean_f32(P(1), P(2, 4), 9, 8, 3, ST); });
+    const char *R = "sonet_chunk_mean_f32 refused";
+    one(R, "null h", [] { return sonet_chunk_mean_f32(nullptr, P(2), 9, 8, 3, ST); });
+    one(R, "null out", [] { return sonet_chunk_mean_f32(P(1), nullptr, 9, 8, 3, ST); });
+    one(R, "rows=0", [] { return sonet_chunk_mean_f32(P(1), P(2), 0, 8, 3, ST); });
+    one(R, "N=0", [] { return sonet_chunk_mean_f32(P(1), P(2), 9, 0, 3, ST); });
+    one(R, "k=0", [] { return sonet_chunk_mean_f32(P(1), P(2), 9, 8, 0, ST); });
+    one(R, "k=4", [] { return sonet_chunk_mean_f32(P(1), P(2), 9, 8, 4, ST); });
+    one(R, "rows=65536", [] { return sonet_chunk_mean_f32(P(1), P(2), 65536, 8, 3, ST); });
+    one(R, "rows=65535*32768+1", [] { return sonet_chunk_mean_f32(P(1), P(2), 65535 * 32768ll + 1, 8, 3, ST); });
+
+    for (int B : {1, 3, 16, 17, 64, 128})
+        for (int Cin : {1, 5, 256, 1024, 1028, 1792, 1796, 4096})
+            for (int Cout : {1, 8, 40, 512})
+                one("sonet_linear_act_f32", fmt("%dx%d>%d", B, Cin, Cout).c_str(), [=] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), B, Cin, Cout, ST); });
+    one("sonet_linear_act_f32", "3x5>8 misaligned x", [] { return sonet_linear_act_f32(P(1, 4), P(2), P(3), P(4), 1, P(5), 3, 5, 8, ST); });
+    const char *RL = "sonet_linear_act_f32 refused";
+    auto Q = [](int i, int null) { return i == null ? nullptr : P(i + 1); };
+    for (int n = 0; n < 5; ++n)
+        one(RL, fmt("null pointer %d", n).c_str(), [=] { return sonet_linear_act_f32(Q(0, n), Q(1, n), Q(2, n), Q(3, n), 1, Q(4, n), 3, 8, 8, ST); });
+    one(RL, "B=0", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 0, 8, 8, ST); });
+    one(RL, "Cin=0", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 3, 0, 8, ST); });
+    one(RL, "Cout=0", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 3, 8, 0, ST); });
+    one(RL, "misaligned x", [] { return sonet_linear_act_f32(P(1, 4), P(2), P(3), P(4), 1, P(5), 3, 8, 8, ST); });
+    one(RL, "misaligned W", [] { return sonet_linear_act_f32(P(1), P(2, 8), P(3), P(4), 1, P(5), 3, 8, 8, ST); });
+    one(RL, "Cin=4097", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 3, 4097, 8, ST); });
+    one(RL, "Cin=4100", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 3, 4100, 8, ST); });
+    one(RL, "B=16*65535+1", [] { return sonet_linear_act_f32(P(1), P(2), P(3), P(4), 1, P(5), 16 * 65535 + 1, 8, 8, ST); });
+}
+
+struct Pooled { int C, M, C1, C2; };
+const Pooled POOLED[] = {{384, 64, 64, 256}, {384, 16, 320, 0}, {128, 64, 3, 64}, {384, 64, 128, 256}, {96, 9, 64, 0}, {385, 64, 64, 256}};
+
+void run_bn_pooled()
+{
+    for (const Pooled &p : POOLED) {
+        const std::string sh = fmt(" C=%d M=%d %d+%d", p.C, p.M, p.C1, p.C2);
+        const int Ci = p.C1 + p.C2;
+        for (int B : {1, 8, 64})
+            for (int L : {1, 31, 128, 1023, 1024, 2049, 5000, 15000, 40000}) {
+                const std::string cs = fmt("%dx%d", B, L);
+                one(("sonet_pooled_wgrad_f32" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_wgrad_f32(P(1), P<int32_t>(2), P(3), B, p.C, p.M, Ci, L, P(4), ST); });
+                one(("sonet_pooled_wgrad_xaff_f32" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_wgrad_xaff_f32(P(1), P<int32_t>(2), P(3), B, p.C, p.M, Ci, L, P(4), P(5), P(6), 1, ST); });
+                one(("sonet_pooled_wgrad_xbf16" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_wgrad_xbf16(P(1), P<int32_t>(2), P<bh>(3), B, p.C, p.M, Ci, L, P(4), ST); });
+                one(("sonet_pooled_wgrad_xaff_xbf16" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_wgrad_xaff_xbf16(P(1), P<int32_t>(2), P<bh>(3), B, p.C, p.M, Ci, L, P(4), P(5), P(6), 1, ST); });
+                one(("sonet_pooled_dgrad_f32" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_dgrad_f32(P(1), P<int32_t>(2), P(3), B, p.C, p.M, p.C1, p.C2, L, P<void>(4), P(5), p.C2 ? P(6) : nullptr, ST); });
+                one(("sonet_pooled_dgrad_obf16" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_dgrad_obf16(P(1), P<int32_t>(2), P(3), B, p.C, p.M, p.C1, p.C2, L, P<void>(4), P<bh>(5), p.C2 ? P<bh>(6) : nullptr, ST); });
+                one(("sonet_pooled_dgrad_mfma_bf16" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_dgrad_mfma_bf16(P(1), P<int32_t>(2), P<void>(3), B, p.C, p.M, p.C1, p.C2, L, P<void>(4), P<bh>(5), p.C2 ? P<bh>(6) : nullptr, ST); });
+#ifdef SONET_VARIANTS
+                one(("sonet_pooled_dgrad_tail_f32" + sh).c_str(), cs.c_str(), [&] { return sonet_pooled_dgrad_tail_f32(P(1), P<int32_t>(2), P(3), B, p.C, p.M, p.C1, p.C2, L, P<void>(4), P(5), p.C2 ? P(6) : nullptr,
+                                                                                                            P(7), P<int32_t>(8), p.C2 ? P(9) : nullptr, P(10), P(11), 1, p.C2 ? P<void>(12) : nullptr, p.C2 ? P<double>(13) : nullptr, ST); });
+#endif
+            }
+    }
+    const char *R = "sonet_pooled refused";
+    auto Q = [](int i, int null) { return i == null ? nullptr : P(i + 1); };
+    for (int n = 0; n < 6; ++n) {
+        one(R, fmt("wgrad_xaff_f32 null pointer %d", n).c_str(), [=] { return sonet_pooled_wgrad_xaff_f32(Q(0, n), (const int32_t *)Q(1, n), Q(2, n), 2, 384, 64, 320, 1024, Q(3, n), Q(4, n), Q(5, n), 1, ST); });
+        one(R, fmt("wgrad_xaff_xbf16 null pointer %d", n).c_str(), [=] { return sonet_pooled_wgrad_xaff_xbf16(Q(0, n), (const int32_t *)Q(1, n), (const bh *)Q(2, n), 2, 384, 64, 320, 1024, Q(3, n), Q(4, n), Q(5, n), 1, ST); });
+        one(R, fmt("dgrad_f32 null pointer %d", n).c_str(), [=] { return sonet_pooled_dgrad_f32(Q(0, n), (const int32_t *)Q(1, n), Q(2, n), 2, 384, 64, 64, 256, 1024, Q(3, n), Q(4, n), Q(5, n), ST); });
+        one(R, fmt("dgrad_mfma_bf16 null pointer %d", n).c_str(), [=] { return sonet_pooled_dgrad_mfma_bf16(Q(0, n), (const int32_t *)Q(1, n), Q(2, n), 2, 384, 64, 64, 256, 1024, Q(3, n), (bh *)Q(4, n), (bh *)Q(5, n), ST); });
+    }
+    for (int n = 0; n < 4; ++n) {
+        one(R, fmt("wgrad_f32 null pointer %d", n).c_str(), [=] { return sonet_pooled_wgrad_f32(Q(0, n), (const int32_t *)Q(1, n), Q(2, n), 2, 384, 64, 320, 1024, Q(3, n), ST); });
+        one(R, fmt("wgrad_xbf16 null pointer %d", n).c_str(), [=] { return sonet_pooled_wgrad_xbf16(Q(0, n), (const int32_t *)Q(1, n), (const bh *)Q(2, n), 2, 384, 64, 320, 1024, Q(3, n), ST); });
+    }
+    struct S { const char *cs; int B, C, M, C1, C2, L; };
+    const S sizes[] = {{"B=0", 0, 384, 64, 64, 256, 1024}, {"C=0", 2, 0, 64, 64, 256, 1024}, {"M=0", 2, 384, 0, 64, 256, 1024}, {"C1=0", 2, 384, 64, 0, 256, 1024},
+                       {"L=0", 2, 384, 64, 64, 256, 0}, {"B=65536", 65536, 384, 64, 64, 256, 1024}, {"M=65", 2, 384, 65, 64, 256, 1024}, {"C*M=2^20", 2, 16384, 64, 64, 256, 1024},
+                       {"L=300000", 2, 384, 64, 64, 256, 300000}, {"L=1023", 2, 384, 64, 64, 256, 1023}, {"C=8", 2, 8, 64, 64, 256, 1024}, {"C=400", 2, 400, 64, 64, 256, 1024},
+                       {"odd tiles", 2, 384, 64, 64, 224, 1024}, {"14 tiles", 2, 384, 64, 192, 256, 1024}};
+    for (const S &z : sizes) {
+        one(R, fmt("wgrad_f32 %s", z.cs).c_str(), [&] { return sonet_pooled_wgrad_f32(P(1), P<int32_t>(2), P(3), z.B, z.C, z.M, z.C1 + z.C2, z.L, P(4), ST); });
+        one(R, fmt("wgrad_xbf16 %s", z.cs).c_str(), [&] { return sonet_pooled_wgrad_xbf16(P(1), P<int32_t>(2), P<bh>(3), z.B, z.C, z.M, z.C1 + z.C2, z.L, P(4), ST); });
+        one(R, fmt("dgrad_f32 %s", z.cs).c_str(), [&] { return sonet_pooled_dgrad_f32(P(1), P<int32_t>(2), P(3), z.B, z.C, z.M, z.C1, z.C2, z.L, P<void>(4), P(5), P(6), ST); });
+        one(R, fmt("dgrad_obf16 %s", z.cs).c_str(), [&] { return sonet_pooled_dgrad_obf16(P(1), P<int32_t>(2), P(3), z.B, z.C, z.M, z.C1, z.C2, z.L, P<void>(4), P<bh>(5), P<bh>(6), ST); });
+        one(R, fmt("dgrad_mfma_bf16 %s", z.cs).c_str(), [&] { return sonet_pooled_dgrad_mfma_bf16(P(1), P<int32_t>(2), P<void>(3), z.B, z.C, z.M, z.C1, z.C2, z.L, P<void>(4), P<bh>(5), P<bh>(6), ST); });
+    }
+    one(R, "dgrad_f32 gx2 without C2", [] { return sonet_pooled_dgrad_f32(P(1), P<int32_t>(2), P(3), 2, 384, 64, 320, 0, 1024, P<void>(4), P(5), P(6), ST); });
+    one(R, "dgrad_f32 C2 without gx2", [] { return sonet_pooled_dgrad_f32(P(1), P<int32_t>(2), P(3), 2, 384, 64, 64, 256, 1024, P<void>(4), P(5), nullptr, ST); });
+    one(R, "dgrad_mfma_bf16 misaligned gx1", [] { return sonet_pooled_dgrad_mfma_bf16(P(1), P<int32_t>(2), P<void>(3), 2, 384, 64, 64, 256, 1024, P<void>(4), P<bh>(5, 2), P<bh>(6), ST); });
+#ifdef SONET_VARIANTS
+    one(R, "dgrad_tail col0 without pos0", [] { return sonet_pooled_dgrad_tail_f32(P(1), P<int32_t>(2), P(3), 2, 384, 64, 64, 256, 1024, P<void>(4), P(5), P(6), P(7), nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ST); });
+    one(R, "dgrad_tail sraw without sums", [] { return sonet_pooled_dgrad_tail_f32(P(1), P<int32_t>(2), P(3), 2, 384, 64, 64, 256, 1024, P<void>(4), P(5), P(6), nullptr, nullptr, P(9), P(10), P(11), 1, P<void>(12), nullptr, ST); });
+    one(R, "dgrad_tail C1 + C2 = 67", [] { return sonet_pooled_dgrad_tail_f32(P(1), P<int32_t>(2), P(3), 2, 128, 64, 3, 64, 1024, P<void>(4), P(5), P(6), P(7), P<int32_t>(8), nullptr, nullptr, nullptr, 0, nullptr, nullptr, ST); });
+#endif
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
     g_argc = argc;
     g_argv = argv;
+    for (int i = 1; i < argc; ++i)
+        if (strcmp(argv[i], "@bn") == 0) {
+            run_bn_bcl();
+            run_bn_coeffs();
+            run_bn_head();
+            run_bn_pooled();
+            return 0;
+        }
     run_pointmlp();
     run_x3();
     run_bf16();

@@ -1,4 +1,4 @@
-"""tools/launch_log.py TREE [--variants] [--full] [--summary] [--sanitize] -- what the layer launchers of a checkout launch, without a GPU.
+"""tools/launch_log.py TREE [--variants] [--bn] [--full] [--summary] [--sanitize] -- what the layer launchers of a checkout launch, without a GPU.
 
 Compiles every source of TREE's so-net_amd/csrc/Makefile SRCS host-only (the Makefile's FLAGS plus --cuda-host-only), links them with a
 recording stand-in for the HIP runtime (tools/launch_stub.cpp) and a driver with its own main (tools/launch_driver.cpp: the C ABI of
@@ -9,6 +9,8 @@ dropped; m = a hipMemsetAsync; E = index into the table of error texts; consecut
 
   == base                      every case, CU count 256, no knob
   == LAUNCH_LOG_CUS=...        the cases that differ from base with another CU count / a failing CU query
+  == bn passes: ...            with --bn (without it the output is what it was before this half existed, byte for byte): the same for the family of the BatchNorm / ReLU passes (the driver's "@bn" half: the element-wise passes, the
+                               coefficient kernels, the eval-mode head kernels, the pooled sparse gradient), behind K / E tables of its own
   --variants: the -DSONET_VARIANTS build.  base lists the cases that differ from the product build's; then one section per SONET_*
               knob setting (each value the code distinguishes and one it rejects) over the launchers that read it: per group of cases
               (entry point, features, channel pair) the number of cases that differ from base and a digest of the group's text --
@@ -67,6 +69,13 @@ KNOBS = [
     ('SONET_WGRAD_BF16_STREAM', ['0', '1'], ['sonet_wgrad_bf16']),
 ]
 # knobs whose launchers also ask for the CU count: the two together
+# the family of the BatchNorm / ReLU passes (the driver's "@bn" half): only the pooled input gradient reads knobs, nothing asks for the CU count
+BN_KNOBS = [
+    ('SONET_PD_ABL', ['1', '4'], ['sonet_pooled_dgrad']),
+    ('SONET_PD_ONE', ['1'], ['sonet_pooled_dgrad']),
+    ('SONET_PD_KERNEL', ['4', '5', '3'], ['sonet_pooled_dgrad']),
+    ('SONET_PM_CH', ['1', '2', '3'], ['sonet_pooled_dgrad_mfma']),
+]
 KNOBS_X_CUS = [('SONET_POINTMLP_NC', '2', X3), ('SONET_BF16_XREG', '2', ['sonet_pointmlp_bf16']), ('SONET_BF16_POOL2', '0', ['sonet_pointresnet_bf16']),
                ('SONET_FUSED_FREE_CUS', '8', ['sonet_pointresnet_fused']), ('SONET_FUSED_FREE_CUS', '-1', ['sonet_pointresnet_fused'])]
 
@@ -94,8 +103,49 @@ def build(tree, variants, sanitize, tmp):
     return exe
 
 
+def recorded_names():
+    """{kernel name: the name it is printed under}.  tests/golden/launch/renamed.txt holds "old new" per line for every kernel that was
+    renamed or merged after the fixtures were recorded (names only, nothing else goes through it).  A kernel of this tree is printed under
+    the FIRST old name the file lists for it, and so is every other old name that became the same kernel: the text of a tree that merged
+    two kernels then differs from the recording only where the recording tells the two apart, and `expand` below removes that."""
+    path = os.path.join(ROOT, 'tests', 'golden', 'launch', 'renamed.txt')
+    pairs = [l.split() for l in open(path).read().split('\n') if l.strip()] if os.path.exists(path) else []
+    first = {}
+    for old, new in pairs:
+        first.setdefault(new, old)
+    out = {new: old for new, old in first.items()}
+    out.update({old: first[new] for old, new in pairs})
+    return out
+
+
+def expand(text):
+    """A recording or an output as one line per case, kernel indices and error indices replaced by what they stand for (kernel names
+    through recorded_names()), the K / E tables dropped: what two texts must agree in when kernels were merged or renamed between them
+    -- every case, its return code and message, every launch with its kernel, grid, block and LDS size.  Digest lines stay as they are."""
+    names = recorded_names()
+    K, E, out = {}, {}, []
+    for line in text.rstrip('\n').split('\n'):
+        m = re.match(r'([KE])(\d+) (.*)$', line)
+        if m:
+            (K if m.group(1) == 'K' else E)[m.group(2)] = names.get(m.group(3), m.group(3)) if m.group(1) == 'K' else m.group(3)
+            continue
+        if line.startswith('== ') and 'kernels and refusal texts' in line:
+            K, E = {}, {}                                    # (the tables of the second half follow)
+            continue
+        m = re.match(r'  (.*) (-?\d+)( E\d+)?$', line.split(' | ')[0]) if line.startswith('  ') else None
+        if not m:
+            out.append(line)
+            continue
+        items = [K[t.split(':')[0]] + t[len(t.split(':')[0]):] if t != 'm' else t for t in line.split(' | ')[1].split()] if ' | ' in line else []
+        tail = m.group(2) + (' ' + E[m.group(3)[2:]] if m.group(3) else '') + (' | ' + ' '.join(items) if items else '')
+        out += ['  %s %s' % (c, tail) for c in m.group(1).split(',')]
+    return out
+
+
 def run(exe, env, prefixes=()):
     """{group: [(case, text)]} in the driver's order; text = 'rc [error] | launches' with kernel NAMES"""
+    back = recorded_names()                                  # (names are rewritten on OUTPUT: a recording made with renamed.txt in place already
+                                                             #  carries the merged names -- record a parent with the file moved aside)
     e = dict((k, v) for k, v in os.environ.items() if not k.startswith('SONET_') and k != 'LAUNCH_LOG_CUS')
     e.update(env)
     out = subprocess.run([exe] + list(prefixes), env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
@@ -106,7 +156,7 @@ def run(exe, env, prefixes=()):
         if not line:
             continue
         group, case, rc, err, launches = line.split('\t')
-        res.setdefault(group, []).append((case, (rc, err, launches.split())))
+        res.setdefault(group, []).append((case, (rc, err, [back.get(t, t) for t in launches.split()])))
     return res
 
 
@@ -200,7 +250,8 @@ def main():
         sections = []                                        # (title, run, reference run or None, digest only)
         base = run(exe, {})
         if variants:
-            sections.append(('base, where it differs from the product build', base, run(build(tree, False, sanitize, tmp), {}), False))
+            product = build(tree, False, sanitize, tmp)
+            sections.append(('base, where it differs from the product build', base, run(product, {}), False))
             for knob, values, prefixes in KNOBS:
                 for v in values:
                     sections.append(('%s=%s' % (knob, v), run(exe, {knob: v}, prefixes), base, not full))
@@ -211,11 +262,25 @@ def main():
             sections.append(('base', base, None, False))
             for cus in CUS:
                 sections.append(('LAUNCH_LOG_CUS=' + cus, run(exe, {'LAUNCH_LOG_CUS': cus}), base, False))
-    names = Names([s[1] for s in sections] + [s[2] for s in sections if s[2] is not None])
-    out = ['K%d %s' % (i, n) for i, n in enumerate(names.table)] + ['E%d %s' % (i, n) for i, n in enumerate(names.errors)]
-    for title, res, ref, digest in sections:
-        out.append('== ' + title)
-        out += digest_section(res, names, ref) if digest else full_section(res, names, ref)
+        # the second half (--bn): the family of the BatchNorm / ReLU passes, with tables of its own (appended to a recording that had none)
+        bn = run(exe, {}, ['@bn']) if '--bn' in flags else None
+        bn_sections = []
+        if bn is None:
+            pass
+        elif variants:
+            bn_sections.append(('bn passes: base, where it differs from the product build', bn, run(product, {}, ['@bn']), False))
+            for knob, values, prefixes in BN_KNOBS:
+                for v in values:
+                    bn_sections.append(('bn passes: %s=%s' % (knob, v), run(exe, {knob: v}, ['@bn'] + prefixes), bn, False))   # (always in full: a digest hangs on table indices)
+        else:
+            bn_sections.append(('bn passes: base', bn, None, False))
+    out = []
+    for head, secs in ((None, sections), ('bn passes: kernels and refusal texts', bn_sections))[:2 if bn_sections else 1]:
+        names = Names([s[1] for s in secs] + [s[2] for s in secs if s[2] is not None])
+        out += ([] if head is None else ['== ' + head]) + ['K%d %s' % (i, n) for i, n in enumerate(names.table)] + ['E%d %s' % (i, n) for i, n in enumerate(names.errors)]
+        for title, res, ref, digest in secs:
+            out.append('== ' + title)
+            out += digest_section(res, names, ref) if digest else full_section(res, names, ref)
     text = '\n'.join(out) + '\n'
     sys.stdout.write(summarise(text) if '--summary' in flags else text)
     return 0
