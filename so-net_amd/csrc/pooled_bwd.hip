@@ -1,6 +1,14 @@
-// pooled_bwd.hip -- backward of the pooled last layer of the first PointNet (training): the sparse input gradient (pooled_dgrad: scalar f32,
-// f32 with the tail layer's BatchNorm-backward sums, bf16 output, matrix-core bf16) and the weight gradient (pooled_wgrad) over the
-// arg-max positions of the per-node max-pool.
+// pooled_bwd.hip -- backward of the pooled last layer of the first PointNet (training) over the arg-max positions of the per-node max-pool.
+//   the blocks     pd_key / pd_key_col / pd_key_id (the sort key of an entry), pd_bounds (a tile's bucket boundaries), pd_entry (the staged
+//                  record of an entry), pd_chain4 (the fma chains of a column-owned four-channel thread), pd_out / pd_store_tile (the way out);
+//                  pooled_dgrad5_kernel and pooled_wgrad_kernel, the pair of every training step, keep their own spelling (docs/findings.md)
+//   the lists      pooled_bucket_kernel (entries into 32-column buckets), pooled_sort_kernel (each bucket by (column, entry id))
+//   sparse dgrad   pooled_dgrad_kernel (one channel per thread: any width), pooled_dgrad4_kernel (four channels, column-owned: variants build,
+//                  the bit-exact twin of the former), pooled_dgrad5_kernel (four channels, entry-balanced: the product's; <TAIL>: the
+//                  measured-slower riders on its store, variants build) with pd_sums_finalize_kernel
+//   dense tile     pooled_dgrad_mfma_kernel (bf16 output: the tile of the never-built gradient times W^T on the matrix cores)
+//   sparse wgrad   pooled_wgrad_kernel
+//   host           PdWs (the workspace), pd_check (what both dgrad launchers check first), the entry points
 #include "common.hpp"
 
 #include <hip/hip_runtime.h>
@@ -9,11 +17,11 @@
 // In the classifier / autoencoder the only consumer of first_pn_out = W4 . [x1; x2] + b is the per-node max-pool
 // (models/networks.py:180-185), so d loss / d first_pn_out has exactly M non-zeros per (b, c) row -- at the arg-max
 // positions.  Instead of scattering them into a dense B x 384 x kN tensor and running a dense W4^T GEMM over it
-// (234x more MACs than needed at N = 5000), the entries are bucketed by 64-column tile and every tile accumulates
+// (234x more MACs than needed at N = 5000), the entries are bucketed by 32-column quarter of a 128-column tile and every tile accumulates
 //     g_x[b][:, l] += g[b][c][m] * W4[c][:]      for its entries (c, m) -> l
-// in LDS, then writes its 320 x 64 block with coalesced stores (the [C][L] layout makes a direct scatter of the 320-vectors
-// uncoalesced in both directions).  Entries of a tile are sorted by (column, channel) before they are applied, so the
-// result does not depend on the order the bucket atomics happened to take.
+// in LDS, 40 input channels per workgroup, then writes its 40 x 128 block with coalesced stores (the [C][L] layout makes a direct scatter
+// of the 320-vectors uncoalesced in both directions).  The entries of a bucket are sorted by (column, entry id) before they are applied, so
+// the result does not depend on the order the bucket atomics happened to take.
 namespace {
 
 constexpr int PD_TL = 128;                     // columns per tile: 256-byte (bf16) / 512-byte (f32) row segments on the way out.  (Round 3: 32
@@ -23,6 +31,52 @@ constexpr int PD_CQ = 4;                       // thread groups per channel: gro
 constexpr int PD_SB = PD_TL / PD_CQ;           // ... = one 32-column bucket of the entry lists (~52 entries at the benchmark shape)
 constexpr int PD_WB = 16;                      // W rows requested before the first fma (64 -- a whole bucket in one round trip -- measured slower)
 constexpr int PD_SQ = 128;                     // entries per group sorted in LDS at a time (more: further rounds, still in global rank order)
+
+// The sort key of an entry: (column inside its bucket, entry id), distinct per entry; entry id = c * M + m, the consumer recovers the
+// channel as id / M.  The launchers refuse C * M >= PD_KEY_IDS.
+constexpr int PD_KEY_BITS = 20;
+constexpr long long PD_KEY_IDS = 1ll << PD_KEY_BITS;
+__device__ __forceinline__ uint32_t pd_key(int col, int id) { return ((uint32_t)col << PD_KEY_BITS) | (uint32_t)id; }
+__device__ __forceinline__ int pd_key_col(uint32_t key) { return (int)(key >> PD_KEY_BITS); }
+__device__ __forceinline__ int pd_key_id(uint32_t key) { return (int)(key & (uint32_t)(PD_KEY_IDS - 1)); }
+
+// bnd[0 .. N]: where the N consecutive buckets from sb0 on begin and end in cloud b's entry list (buckets past the last one are empty)
+template <int N>
+__device__ __forceinline__ void pd_bounds(const int32_t *__restrict__ tile_off, int b, int nbucket, int sb0, int (&bnd)[N + 1])
+{
+    const int32_t *to = tile_off + (size_t)b * (nbucket + 1);
+#pragma unroll
+    for (int t = 0; t <= N; ++t) bnd[t] = to[min(sb0 + t, nbucket)];
+}
+
+// channel ch of cloud b on its way out: its row of the first panel (C1 channels) or of the second (the other Cin - C1)
+template <typename TO>
+__device__ __forceinline__ TO *pd_out(TO *gx1, TO *gx2, int b, int ch, int C1, int Cin, int L)
+{
+    return ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L;
+}
+
+// The accumulators acc[PD_TL][ld] of tile `tile`, channels [ch0, ch0 + nch), to the output; one rounding for bf16.
+template <typename TO>
+__device__ __forceinline__ void pd_store_tile(const float *acc, int ld, int tile, int b, int ch0, int nch, int C1, int Cin, int L, TO *gx1, TO *gx2)
+{
+    const int tid = threadIdx.x, nth = blockDim.x, l0 = tile * PD_TL;
+    if (sizeof(TO) == 2 && (L & 1) == 0) {
+        // bf16 output, even L: two columns per thread, one 4-byte store -- 64 consecutive threads write the 256 bytes of a row segment
+        for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
+            const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
+            if (l0 + col >= L) continue;                        // (L even: col + 1 is inside too)
+            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
+            *reinterpret_cast<unsigned *>(pd_out(gx1, gx2, b, ch0 + r, C1, Cin, L) + l0 + col) = pk;
+        }
+        return;
+    }
+    for (int idx = tid; idx < nch * PD_TL; idx += nth) {        // coalesced: consecutive threads along the columns of one channel
+        const int r = idx / PD_TL, col = idx - r * PD_TL;
+        if (l0 + col >= L) continue;
+        st_rne(pd_out(gx1, gx2, b, ch0 + r, C1, Cin, L), l0 + col, acc[col * ld + r]);
+    }
+}
 
 constexpr int PB_Q = 4;                        // workgroups per cloud: each owns a quarter of the bucket range (one per cloud left 3/4 of the chip idle)
 __global__ __launch_bounds__(1024) void pooled_bucket_kernel(const int32_t *__restrict__ pos, const float *__restrict__ g,
@@ -91,8 +145,7 @@ __global__ __launch_bounds__(1024) void pooled_bucket_kernel(const int32_t *__re
         const int t = l / PD_SB;
         if (t < t0 || t >= t0 + nb) continue;
         const int p = base + off[t - t0] + atomicAdd(&cnt[t - t0], 1);
-        // sort key (column, entry id); entry id = c * M + m, the consumer recovers the channel as id / M
-        ent_key[(size_t)b * E + p] = ((uint32_t)(l - t * PD_SB) << 20) | (uint32_t)e;
+        ent_key[(size_t)b * E + p] = pd_key(l - t * PD_SB, e);
         ent_val[(size_t)b * E + p] = g[(size_t)b * E + e];
     }
 }
@@ -126,7 +179,7 @@ __global__ __launch_bounds__(64) void pooled_sort_kernel(const int32_t *__restri
     }
     if (lane < PD_SB) colcnt[lane] = 0;
     __syncthreads();
-    for (int e = lane; e < nq; e += 64) atomicAdd(&colcnt[kb[e] >> 20], 1);
+    for (int e = lane; e < nq; e += 64) atomicAdd(&colcnt[pd_key_col(kb[e])], 1);
     __syncthreads();
     if (lane < PD_SB) {
         int s0 = 0;
@@ -137,12 +190,12 @@ __global__ __launch_bounds__(64) void pooled_sort_kernel(const int32_t *__restri
     __syncthreads();
     for (int e = lane; e < nq; e += 64) {
         const uint32_t key = kb[e];
-        tmp[atomicAdd(&cursor[key >> 20], 1)] = key;
+        tmp[atomicAdd(&cursor[pd_key_col(key)], 1)] = key;
     }
     __syncthreads();
     for (int t = lane; t < nq; t += 64) {
         const uint32_t key = tmp[t];
-        const int col = (int)(key >> 20);
+        const int col = pd_key_col(key);
         const int s0 = segstart[col], s1 = s0 + colcnt[col];
         int rank = 0;
         for (int u = s0; u < s1; ++u) rank += tmp[u] < key;
@@ -152,7 +205,7 @@ __global__ __launch_bounds__(64) void pooled_sort_kernel(const int32_t *__restri
 
 template <typename TO>
 __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32_t *__restrict__ tile_off, const uint32_t *__restrict__ ent_key,
-                                                           const float *__restrict__ ent_val, const float *__restrict__ g_pooled /*[B][E]: the entries' values by id*/,
+                                                           const float *__restrict__ g_pooled /*[B][E]: the entries' values by id*/,
                                                            const float *__restrict__ W,
                                                            int E, int M, int Cin, int C1, int L, int nbucket,
                                                            TO *__restrict__ gx1, TO *__restrict__ gx2, int abl /*experiments (variants build): 1 no stores, 2 no accumulation, 4 no sort*/)
@@ -168,29 +221,27 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32
     __shared__ int nq_all[PD_CQ];
     const int ch0 = blockIdx.z * PD_CH, nch = min(PD_CH, Cin - ch0);        // this workgroup's input channels
     for (int t = tid; t < PD_TL * ld; t += nth) acc[t] = 0.f;
-    const int sb = tile * PD_CQ + q;                                        // this group's bucket (32 columns)
-    const int beg = sb < nbucket ? tile_off[(size_t)b * (nbucket + 1) + sb] : 0;
-    const int nq = sb < nbucket ? tile_off[(size_t)b * (nbucket + 1) + sb + 1] - beg : 0;
+    int bnd[2];                                                             // this group's bucket (32 columns)
+    pd_bounds<1>(tile_off, b, nbucket, tile * PD_CQ + q, bnd);
+    const int beg = bnd[0], nq = bnd[1] - beg;
     const uint32_t *kb = ent_key + (size_t)b * E + beg;
-    const float *vb = ent_val + (size_t)b * E + beg;
     const float *gb = g_pooled + (size_t)b * E;
     if (i == 0) nq_all[q] = nq;
     __syncthreads();
     int nmax = 0;
 #pragma unroll
     for (int t = 0; t < PD_CQ; ++t) nmax = max(nmax, nq_all[t]);
-    // The group's bucket arrives SORTED by (column, entry id) (pooled_sort_kernel below: once per bucket instead of once per (bucket,
+    // The group's bucket arrives SORTED by (column, entry id) (pooled_sort_kernel above: once per bucket instead of once per (bucket,
     // channel slab)), so the order of the fma chain of an accumulator is fixed whatever order the bucket atomics took; thread (i, q)
     // applies the group's entries to channel ch0 + i (no two threads touch the same accumulator).  Rounds of PD_SQ consecutive entries: a
     // column that continues in the next round resumes from the stored value.
-    (void)vb;
     for (int base = 0; base < nmax; base += PD_SQ) {
         const int n = min(PD_SQ, max(0, nq - base));
         __syncthreads();                                                    // the previous round's lists are consumed
         for (int t = i; t < n; t += PD_CH) {
             const uint32_t key = kb[base + t];
-            const int id = (int)(key & 0xFFFFFu);
-            keys[t] = (key >> 20) + (uint32_t)(q * PD_SB);                  // column inside the tile
+            const int id = pd_key_id(key);
+            keys[t] = (uint32_t)(pd_key_col(key) + q * PD_SB);              // column inside the tile
             vals[t] = gb[id];
             wrow[t] = (id / M) * Cin + ch0;                                 // (per entry, once: the division per (entry, thread) was half of the kernel in round 2)
         }
@@ -229,36 +280,62 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad_kernel(const int32
     }
     __syncthreads();
     if (abl & 1) return;
-    const int l0 = tile * PD_TL;
-    if (sizeof(TO) == 2 && (L & 1) == 0) {
-        // bf16 output, even L: two columns per thread, one 4-byte store -- 64 consecutive threads write the 256 bytes of a row segment
-        for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
-            const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
-            if (l0 + col >= L) continue;                        // (L even: col + 1 is inside too)
-            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
-            const int ch = ch0 + r;
-            TO *dst = ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L + l0 + col : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col;
-            *reinterpret_cast<unsigned *>(dst) = pk;
-        }
-        return;
-    }
-    for (int idx = tid; idx < nch * PD_TL; idx += nth) {        // coalesced: consecutive threads along the columns of one channel
-        const int r = idx / PD_TL, col = idx - r * PD_TL;
-        if (l0 + col >= L) continue;
-        const float v = acc[col * ld + r];
-        const int ch = ch0 + r;
-        if (ch < C1) st_rne(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
-        else st_rne(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
-    }
+    pd_store_tile(acc, ld, tile, b, ch0, nch, C1, Cin, L, gx1, gx2);
 }
 
-// Four channels per thread (Cin a multiple of 4).  The accumulate loop of the kernel above is bound by instruction issue, not by latency: per
+// The staged record of an entry, 16 bytes: (column inside the tile -- its bucket is quarter q --, value bits, offset of its W row for the
+// workgroup's channel slab, -)
+__device__ __forceinline__ uint4 pd_entry(uint32_t key, int q, const float *__restrict__ gb, int M, int Cin, int ch0)
+{
+    const int id = pd_key_id(key);
+    return make_uint4((unsigned)(pd_key_col(key) + q * PD_SB), __float_as_uint(gb[id]), (unsigned)((id / M) * Cin + ch0), 0u);
+}
+
+// The fma chains of a four-channel thread over its cnt > 0 staged entries ent[0 .. cnt), sorted by column: acc4 / W4 are the accumulator row
+// of column 0 and W, both at the thread's channel quad.  PD4_WB entries and their float4 of W are requested before the first fma; the chains
+// of a column run in registers and are written when the column changes (a column that continues from an earlier round resumes from the stored
+// value -- the accumulators start at zero).  The entry-balanced kernel spells the same loop with a cut column's sum parked in `head`: through
+// this helper (a PARK template argument) the pair it runs beside the weight gradient measured slower, docs/findings.md.
+constexpr int PD4_LD = PD_CH + 4;              // accumulator row pitch: 16-byte aligned groups of four channels
+constexpr int PD4_WB = 8;                      // entries (a W float4 each) requested before the first fma
+__device__ __forceinline__ void pd_chain4(const uint4 *ent, int cnt, const float *__restrict__ W4, float *acc4)
+{
+    constexpr int ld = PD4_LD;
+    int cur = (int)ent[0].x;
+    float4 sum = *reinterpret_cast<const float4 *>(acc4 + cur * ld);
+    for (int e0 = 0; e0 < cnt; e0 += PD4_WB) {
+        uint4 en[PD4_WB];
+        float4 wv[PD4_WB];
+#pragma unroll
+        for (int t = 0; t < PD4_WB; ++t) {
+            en[t] = ent[e0 + t < cnt ? e0 + t : cnt - 1];
+            wv[t] = *reinterpret_cast<const float4 *>(W4 + (size_t)en[t].z);
+        }
+#pragma unroll
+        for (int t = 0; t < PD4_WB; ++t) {
+            if (e0 + t < cnt) {
+                const int col = (int)en[t].x;
+                if (col != cur) {
+                    *reinterpret_cast<float4 *>(acc4 + cur * ld) = sum;
+                    cur = col;
+                    sum = *reinterpret_cast<const float4 *>(acc4 + cur * ld);
+                }
+                const float v = __uint_as_float(en[t].y);
+                sum.x = __fmaf_rn(v, wv[t].x, sum.x);
+                sum.y = __fmaf_rn(v, wv[t].y, sum.y);
+                sum.z = __fmaf_rn(v, wv[t].z, sum.z);
+                sum.w = __fmaf_rn(v, wv[t].w, sum.w);
+            }
+        }
+    }
+    *reinterpret_cast<float4 *>(acc4 + cur * ld) = sum;
+}
+
+// Four channels per thread (Cin a multiple of 4).  The accumulate loop of the one-channel kernel is bound by instruction issue, not by latency: per
 // (entry, channel) three LDS reads, an address, a global load, a compare and one fma.  Here thread (i4, q, s) owns channels 4 i4 .. 4 i4 + 3 of the
 // columns [8 s, 8 s + 8) of quarter q: the same per-entry overhead (one 16-byte LDS read, one 16-byte load of W) feeds four fmas, and the
 // sixteen sub-ranges of a tile (their entry counts differ less than the four quarters') share the wave's loop trips.  Same entries in the same
-// (column, entry id) order per accumulator: the same bits as the kernel above.
-constexpr int PD4_LD = PD_CH + 4;              // accumulator row pitch: 16-byte aligned groups of four channels
-constexpr int PD4_WB = 8;                      // entries (a W float4 each) requested before the first fma
+// (column, entry id) order per accumulator: the same bits as the one-channel kernel.
 #ifdef SONET_VARIANTS   // (the column-owned form: replaced by the entry-balanced kernel below, kept as the bit-exact twin of the one-channel kernel)
 template <typename TO>
 __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad4_kernel(const int32_t *__restrict__ tile_off, const uint32_t *__restrict__ skey,
@@ -277,9 +354,9 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad4_kernel(const int3
     uint4 *ent = ent_all + q * PD_SQ;
     const int ch0 = blockIdx.z * PD_CH, nch = min(PD_CH, Cin - ch0);
     for (int t = tid; t < PD_TL * ld; t += nth) acc[t] = 0.f;
-    const int sb = tile * PD_CQ + q;
-    const int beg = sb < nbucket ? tile_off[(size_t)b * (nbucket + 1) + sb] : 0;
-    const int nq = sb < nbucket ? tile_off[(size_t)b * (nbucket + 1) + sb + 1] - beg : 0;
+    int bnd[2];
+    pd_bounds<1>(tile_off, b, nbucket, tile * PD_CQ + q, bnd);
+    const int beg = bnd[0], nq = bnd[1] - beg;
     const uint32_t *kb = skey + (size_t)b * E + beg;
     const float *gb = g_pooled + (size_t)b * E;
     if (tq == 0) nq_all[q] = nq;
@@ -294,68 +371,17 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad4_kernel(const int3
         __syncthreads();
         for (int t = tq; t < n; t += PD_CH) {
             const uint32_t key = kb[base + t];
-            const int id = (int)(key & 0xFFFFFu), colq = (int)(key >> 20);
-            ent[t] = make_uint4((unsigned)(colq + q * PD_SB), __float_as_uint(gb[id]), (unsigned)((id / M) * Cin + ch0), 0u);
-            atomicAdd(&subcnt[q][colq >> 3], 1);
+            ent[t] = pd_entry(key, q, gb, M, Cin, ch0);
+            atomicAdd(&subcnt[q][pd_key_col(key) >> 3], 1);
         }
         __syncthreads();
         int lo = 0;
         for (int t = 0; t < sub; ++t) lo += subcnt[q][t];
         const int cnt = subcnt[q][sub];
-        if (4 * i4 < nch && cnt > 0) {
-            // (sorted by column: the chains of a column run in registers and are written when the column changes; a column that continues
-            //  from the previous round resumes from the stored value -- the accumulators start at zero)
-            int cur = (int)ent[lo].x;
-            float4 sum = *reinterpret_cast<const float4 *>(acc + cur * ld + 4 * i4);
-            for (int e0 = 0; e0 < cnt; e0 += PD4_WB) {
-                uint4 en[PD4_WB];
-                float4 wv[PD4_WB];
-#pragma unroll
-                for (int t = 0; t < PD4_WB; ++t) {
-                    en[t] = ent[lo + (e0 + t < cnt ? e0 + t : cnt - 1)];
-                    wv[t] = *reinterpret_cast<const float4 *>(W + (size_t)en[t].z + 4 * i4);
-                }
-#pragma unroll
-                for (int t = 0; t < PD4_WB; ++t) {
-                    if (e0 + t < cnt) {
-                        const int col = (int)en[t].x;
-                        if (col != cur) {
-                            *reinterpret_cast<float4 *>(acc + cur * ld + 4 * i4) = sum;
-                            cur = col;
-                            sum = *reinterpret_cast<const float4 *>(acc + cur * ld + 4 * i4);
-                        }
-                        const float v = __uint_as_float(en[t].y);
-                        sum.x = __fmaf_rn(v, wv[t].x, sum.x);
-                        sum.y = __fmaf_rn(v, wv[t].y, sum.y);
-                        sum.z = __fmaf_rn(v, wv[t].z, sum.z);
-                        sum.w = __fmaf_rn(v, wv[t].w, sum.w);
-                    }
-                }
-            }
-            *reinterpret_cast<float4 *>(acc + cur * ld + 4 * i4) = sum;
-        }
+        if (4 * i4 < nch && cnt > 0) pd_chain4(ent + lo, cnt, W + 4 * i4, acc + 4 * i4);
     }
     __syncthreads();
-    const int l0 = tile * PD_TL;
-    if (sizeof(TO) == 2 && (L & 1) == 0) {
-        for (int idx = tid; idx < nch * (PD_TL / 2); idx += nth) {
-            const int r = idx / (PD_TL / 2), col = (idx - r * (PD_TL / 2)) * 2;
-            if (l0 + col >= L) continue;
-            const unsigned pk = cvt_pk_bf16(acc[col * ld + r], acc[(col + 1) * ld + r]);
-            const int ch = ch0 + r;
-            TO *dst = ch < C1 ? gx1 + ((size_t)b * C1 + ch) * L + l0 + col : gx2 + ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col;
-            *reinterpret_cast<unsigned *>(dst) = pk;
-        }
-        return;
-    }
-    for (int idx = tid; idx < nch * PD_TL; idx += nth) {
-        const int r = idx / PD_TL, col = idx - r * PD_TL;
-        if (l0 + col >= L) continue;
-        const float v = acc[col * ld + r];
-        const int ch = ch0 + r;
-        if (ch < C1) st_rne(gx1, ((size_t)b * C1 + ch) * L + l0 + col, v);
-        else st_rne(gx2, ((size_t)b * (Cin - C1) + (ch - C1)) * L + l0 + col, v);
-    }
+    pd_store_tile(acc, ld, tile, b, ch0, nch, C1, Cin, L, gx1, gx2);
 }
 #endif  // SONET_VARIANTS
 
@@ -439,9 +465,9 @@ __global__ __launch_bounds__(PD_CH * PD_CQ) void pooled_dgrad5_kernel(const int3
         for (int t = tid; t < n; t += nth) {
             const int e = beg + base + t;
             const uint32_t key = kb[base + t];
-            const int id = (int)(key & 0xFFFFFu);
+            const int id = pd_key_id(key);
             const int q = (e >= bo[1]) + (e >= bo[2]) + (e >= bo[3]);      // the bucket of the tile this entry sits in
-            ent[t] = make_uint4((unsigned)((int)(key >> 20) + q * PD_SB), __float_as_uint(gb[id]), (unsigned)((id / M) * Cin + ch0), 0u);
+            ent[t] = make_uint4((unsigned)(pd_key_col(key) + q * PD_SB), __float_as_uint(gb[id]), (unsigned)((id / M) * Cin + ch0), 0u);
         }
         __syncthreads();
         // chunk grp: the first n % 16 chunks take one entry more (the non-empty chunks are the first ones)
@@ -605,11 +631,8 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
     const int mhalf = wave & 1, chalf = wave >> 1;                          // cin tiles [mhalf NMT, ...), columns [64 chalf, 64 chalf + 64) of the tile
     const int n = lane & 31, h = lane >> 5;
     for (int t = tid; t < 2 * NR * PM_PITCH / 16; t += 128 * CH) pm_lds[t] = make_uint4(0u, 0u, 0u, 0u);
-    const int sb0 = tile * 2 * CH;
-    const int32_t *off = tile_off + (size_t)b * (nbucket + 1);
     int bnd[2 * CH + 1];
-#pragma unroll
-    for (int k = 0; k <= 2 * CH; ++k) bnd[k] = off[min(sb0 + k, nbucket)];
+    pd_bounds<2 * CH>(tile_off, b, nbucket, tile * 2 * CH, bnd);
     // A fragments of the first chunks: on their way while the tile is built.  (With CH = 2 the two waves of a cin half request the same
     // fragments a few hundred cycles apart: the second request is an L1 hit, and W^T crosses the L2 once per 128 columns.)
     const uint4 *wt = Wtp + ((size_t)(mhalf * NMT) * KC) * 64 + lane;
@@ -624,7 +647,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
         int bk = 0;
 #pragma unroll
         for (int k = 1; k < 2 * CH; ++k) bk += e >= bnd[k];
-        const int l = (int)(key >> 20) + 32 * bk, c = (int)(key & 0xFFFFFu) / M;
+        const int l = pd_key_col(key) + PD_SB * bk, c = pd_key_id(key) / M;
         // (a compare-and-swap on the dword that holds the channel pair: two channels of a column share it, and a (channel, column) pair
         //  that does occur twice -- not in this model -- adds up instead of being overwritten, in arrival order)
         unsigned *wd = reinterpret_cast<unsigned *>(((l & 1) ? Go : Ge) + (l >> 1) * PM_PITCH + (c >> 1) * 4);
@@ -686,7 +709,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
         for (int ci = tid >> 4; ci < C1 + C2; ci += (128 * CH) >> 4) {
             const int c0 = l0 + 8 * piece;
             if (c0 >= L) continue;
-            uint16_t *dst = ci < C1 ? gx1 + ((size_t)b * C1 + ci) * L + c0 : gx2 + ((size_t)b * C2 + (ci - C1)) * L + c0;
+            uint16_t *dst = pd_out(gx1, gx2, b, ci, C1, C1 + C2, L) + c0;
             const uint4 v = *reinterpret_cast<const uint4 *>(ot + ci * OP + piece * 16);
             if (vec && c0 + 8 <= L) {
                 *reinterpret_cast<uint4 *>(dst) = v;
@@ -707,6 +730,7 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
                 const int ci = (mhalf * NMT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (ci >= C1 + C2) continue;
                 const unsigned pk = cvt_pk_bf16(acc[mt][0][r], acc[mt][1][r]);
+                // (pd_out spelled out: through the helper these 16 NMT unrolled stores measured 2 % slower, docs/findings.md)
                 uint16_t *dst = ci < C1 ? gx1 + ((size_t)b * C1 + ci) * L + col : gx2 + ((size_t)b * C2 + (ci - C1)) * L + col;
                 *reinterpret_cast<unsigned *>(dst) = pk;
             }
@@ -715,13 +739,35 @@ __global__ __launch_bounds__(128 * CH) void pooled_dgrad_mfma_kernel(const int32
     }
 }
 
+// The workspace of the dgrad launchers: the bucket lists (key, value) of B clouds of E entries, the sorted keys, the bucket offsets.  The
+// matrix-core launcher sorts nothing and puts the offsets right behind the values (`sorted` false); the size is the same for both.
+struct PdWs {
+    uint32_t *ent_key;
+    float *ent_val;
+    uint32_t *skey;
+    int32_t *tile_off;
+    static size_t bytes(size_t B, size_t E, size_t nbucket) { return B * (E * 12 + (nbucket + 1) * 4); }
+    PdWs(void *ws, int B, int E, bool sorted)
+        : ent_key(reinterpret_cast<uint32_t *>(ws)), ent_val(reinterpret_cast<float *>(ent_key + (size_t)B * E)),
+          skey(reinterpret_cast<uint32_t *>(ent_val + (size_t)B * E)), tile_off(reinterpret_cast<int32_t *>(sorted ? skey + (size_t)B * E : skey)) {}
+};
+
+// what both dgrad launchers check first (`w`: the weights or their pack)
+int pd_check(const char *what, const void *g_pooled, const void *pos, const void *w, const void *ws, const void *gx1, const void *gx2, int B,
+             int C, int M, int C1, int C2, int L)
+{
+    SONET_REQUIRE(g_pooled && pos && w && ws && gx1, "%s: NULL pointer", what);
+    SONET_REQUIRE(B > 0 && C > 0 && M > 0 && C1 > 0 && C2 >= 0 && L > 0, "%s: non-positive size", what);
+    SONET_REQUIRE((C2 == 0) == (gx2 == nullptr), "%s: gx2 and C2 disagree", what);
+    return SONET_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sonet_pooled_dgrad_ws_size(int B, int C, int M, int L)
 {
     if (B <= 0 || C <= 0 || M <= 0 || L <= 0) return 0;
-    const size_t E = (size_t)C * M, nbucket = (size_t)sonet::ceil_div(L, PD_SB);
-    return (size_t)B * (E * 12 + (nbucket + 1) * 4);            // bucket lists (key, value), the sorted keys, bucket offsets
+    return PdWs::bytes((size_t)B, (size_t)C * M, (size_t)sonet::ceil_div(L, PD_SB));
 }
 
 // Sparse wgrad of the pooled last layer: the gradient of first_pn_out exists only at the C*M gathered positions of a
@@ -919,22 +965,17 @@ template <typename TO>
 static int pooled_dgrad_impl(const char *what, const float *g_pooled, const int32_t *pos, const float *W, int B, int C, int M, int C1, int C2,
                              int L, void *ws, TO *gx1, TO *gx2, sonet_stream_t stream, const PdTail *tail = nullptr, double *tail_sums = nullptr)
 {
-    SONET_REQUIRE(g_pooled && pos && W && ws && gx1, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && M > 0 && C1 > 0 && C2 >= 0 && L > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (gx2 == nullptr), "%s: gx2 and C2 disagree", what);
+    if (const int rc = pd_check(what, g_pooled, pos, W, ws, gx1, gx2, B, C, M, C1, C2, L)) return rc;
     const int Cin = C1 + C2, E = C * M, ntile = sonet::ceil_div(L, PD_TL), nbucket = sonet::ceil_div(L, PD_SB);
-    if ((long long)C * M >= (1 << 20) || B > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: C*M=%d entries per cloud (max 2^20)", what, E);
+    if ((long long)C * M >= PD_KEY_IDS || B > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: C*M=%d entries per cloud (max 2^20)", what, E);
     const size_t lds2 = ((size_t)PD_TL * (PD_CH + 1) + (size_t)PD_CQ * 3 * PD_SQ) * 4;
     if ((size_t)(2 * nbucket + 1) * 4 > 64 * 1024) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: L=%d too large for the bucket counters", what, L);
-    uint32_t *ent_key = reinterpret_cast<uint32_t *>(ws);
-    float *ent_val = reinterpret_cast<float *>(ent_key + (size_t)B * E);
-    uint32_t *skey = reinterpret_cast<uint32_t *>(ent_val + (size_t)B * E);
-    int32_t *tile_off = reinterpret_cast<int32_t *>(skey + (size_t)B * E);
+    const PdWs w(ws, B, E, true);
     hipStream_t st = sonet::as_stream(stream);
     int abl = 0;
     if (const char *e = sonet::knob("SONET_PD_ABL")) abl = atoi(e);
-    hipLaunchKernelGGL(pooled_bucket_kernel, dim3(B, PB_Q), dim3(1024), (size_t)(2 * sonet::ceil_div(nbucket, PB_Q) + 1) * 4, st, pos, g_pooled, E, L, nbucket, tile_off, ent_key, ent_val);
-    if (!(abl & 4)) hipLaunchKernelGGL(pooled_sort_kernel, dim3(nbucket, B), dim3(64), 0, st, tile_off, ent_key, skey, E, nbucket);
+    hipLaunchKernelGGL(pooled_bucket_kernel, dim3(B, PB_Q), dim3(1024), (size_t)(2 * sonet::ceil_div(nbucket, PB_Q) + 1) * 4, st, pos, g_pooled, E, L, nbucket, w.tile_off, w.ent_key, w.ent_val);
+    if (!(abl & 4)) hipLaunchKernelGGL(pooled_sort_kernel, dim3(nbucket, B), dim3(64), 0, st, w.tile_off, w.ent_key, w.skey, E, nbucket);
     int one = 0;
     if (const char *e = sonet::knob("SONET_PD_ONE")) one = atoi(e);     // (variants build: 1 = the one-channel-per-thread kernel)
     int which = PD_SPARSE_KERNEL;
@@ -946,26 +987,26 @@ static int pooled_dgrad_impl(const char *what, const float *g_pooled, const int3
 #ifdef SONET_VARIANTS
         if (tail) {
             if constexpr (sizeof(TO) == 4) {
-                hipLaunchKernelGGL((pooled_dgrad5_kernel<TO, true>), dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds5, st, tile_off, skey, g_pooled, W, E, M,
+                hipLaunchKernelGGL((pooled_dgrad5_kernel<TO, true>), dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds5, st, w.tile_off, w.skey, g_pooled, W, E, M,
                                    Cin, C1, L, nbucket, gx1, gx2 ? gx2 : gx1, *tail);
                 if (tail->sraw) hipLaunchKernelGGL(pd_sums_finalize_kernel, dim3((unsigned)C2), dim3(256), 0, st, tail->spart, B * ntile, C2, tail_sums);
                 return sonet::launched(what);
             }
         }
 #endif
-        hipLaunchKernelGGL(pooled_dgrad5_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds5, st, tile_off, skey, g_pooled, W, E, M, Cin, C1,
+        hipLaunchKernelGGL(pooled_dgrad5_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds5, st, w.tile_off, w.skey, g_pooled, W, E, M, Cin, C1,
                            L, nbucket, gx1, gx2 ? gx2 : gx1, PdTail{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr});
         return sonet::launched(what);
     }
 #ifdef SONET_VARIANTS
     if (Cin % 4 == 0 && abl == 0 && !one && which == 4) {
         const size_t lds4 = (size_t)PD_TL * PD4_LD * 4 + (size_t)PD_CQ * PD_SQ * 16;
-        hipLaunchKernelGGL(pooled_dgrad4_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds4, st, tile_off, skey, g_pooled, W, E, M, Cin, C1,
+        hipLaunchKernelGGL(pooled_dgrad4_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds4, st, w.tile_off, w.skey, g_pooled, W, E, M, Cin, C1,
                            L, nbucket, gx1, gx2 ? gx2 : gx1);
         return sonet::launched(what);
     }
 #endif
-    hipLaunchKernelGGL(pooled_dgrad_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds2, st, tile_off, (abl & 4) ? ent_key : skey, ent_val, g_pooled, W, E, M, Cin, C1,
+    hipLaunchKernelGGL(pooled_dgrad_kernel<TO>, dim3(ntile, B, sonet::ceil_div(Cin, PD_CH)), dim3(PD_CH * PD_CQ), lds2, st, w.tile_off, (abl & 4) ? w.ent_key : w.skey, g_pooled, W, E, M, Cin, C1,
                        L, nbucket, gx1, gx2 ? gx2 : gx1, abl);
     return sonet::launched(what);
 }
@@ -1017,18 +1058,14 @@ extern "C" int sonet_pooled_dgrad_mfma_bf16(const float *g_pooled, const int32_t
                                             int L, void *ws, uint16_t *gx1, uint16_t *gx2, sonet_stream_t stream)
 {
     const char *what = "sonet_pooled_dgrad_mfma_bf16";
-    SONET_REQUIRE(g_pooled && pos && wt_pack && ws && gx1, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && C > 0 && M > 0 && C1 > 0 && C2 >= 0 && L > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((C2 == 0) == (gx2 == nullptr), "%s: gx2 and C2 disagree", what);
+    if (const int rc = pd_check(what, g_pooled, pos, wt_pack, ws, gx1, gx2, B, C, M, C1, C2, L)) return rc;
     const int Cin = C1 + C2, E = C * M, CT = sonet::ceil_div(Cin, 32), nbucket = sonet::ceil_div(L, PD_SB);
-    if ((L & 1) || C % 16 || C * 2 + 16 > PM_PITCH || (CT & 1) || CT > 12 || (long long)C * M >= (1 << 20) || B > 65535 ||
+    if ((L & 1) || C % 16 || C * 2 + 16 > PM_PITCH || (CT & 1) || CT > 12 || (long long)C * M >= PD_KEY_IDS || B > 65535 ||
         (size_t)(2 * nbucket + 1) * 4 > 64 * 1024 || ((reinterpret_cast<uintptr_t>(gx1) | reinterpret_cast<uintptr_t>(gx2)) & 3))
         return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: shape B=%d C=%d M=%d C1=%d C2=%d L=%d not supported", what, B, C, M, C1, C2, L);
-    uint32_t *ent_key = reinterpret_cast<uint32_t *>(ws);
-    float *ent_val = reinterpret_cast<float *>(ent_key + (size_t)B * E);
-    int32_t *tile_off = reinterpret_cast<int32_t *>(ent_val + (size_t)B * E);
+    const PdWs w(ws, B, E, false);
     hipStream_t st = sonet::as_stream(stream);
-    hipLaunchKernelGGL(pooled_bucket_kernel, dim3(B, PB_Q), dim3(1024), (size_t)(2 * sonet::ceil_div(nbucket, PB_Q) + 1) * 4, st, pos, g_pooled, E, L, nbucket, tile_off, ent_key, ent_val);
+    hipLaunchKernelGGL(pooled_bucket_kernel, dim3(B, PB_Q), dim3(1024), (size_t)(2 * sonet::ceil_div(nbucket, PB_Q) + 1) * 4, st, pos, g_pooled, E, L, nbucket, w.tile_off, w.ent_key, w.ent_val);
     // 128-column workgroups (four waves, one per CU: W^T crosses the L2 once per 128 columns) on big launches, 64-column ones otherwise
     int ch = (long long)B * sonet::ceil_div(L, 2 * PM_TL) >= 2048 ? 2 : 1;
     if (const char *e = sonet::knob("SONET_PM_CH")) { const int v = atoi(e); if (v == 1 || v == 2) ch = v; }
@@ -1037,18 +1074,15 @@ extern "C" int sonet_pooled_dgrad_mfma_bf16(const float *g_pooled, const int32_t
     if (ch == 2 && (size_t)CT * 32 * 272 > lds) lds = (size_t)CT * 32 * 272;          // (the output tile reuses the image)
     const uint4 *wtp = reinterpret_cast<const uint4 *>(wt_pack);
     uint16_t *g2 = gx2 ? gx2 : gx1;
-#define PM_LAUNCH1(NN, CC) do { if (const int rc_ = sonet::launch_lds_once<&pooled_dgrad_mfma_kernel<NN, CC>, 128 * 1024>(what, dim3(ntile_l, B), dim3(128 * CC), lds, st, \
-                tile_off, ent_key, ent_val, wtp, E, M, C, C / 16, C1, C2, L, nbucket, gx1, g2)) return rc_; } while (0)
-#define PM_LAUNCH(NN) do { if (ch == 2) PM_LAUNCH1(NN, 2); else PM_LAUNCH1(NN, 1); } while (0)
-    switch (CT / 2) {
-        case 1: PM_LAUNCH(1); break;
-        case 2: PM_LAUNCH(2); break;
-        case 3: PM_LAUNCH(3); break;
-        case 4: PM_LAUNCH(4); break;
-        case 5: PM_LAUNCH(5); break;
-        default: PM_LAUNCH(6); break;
-    }
-#undef PM_LAUNCH1
-#undef PM_LAUNCH
+    int rc = SONET_OK;
+    with_int_c<1, 2, 3, 4, 5, 6>(CT / 2, [&](auto nmt) {       // (pairs of 32-row tiles per cin half; a count outside the list takes the last)
+        auto launch = [&](auto cc) {
+            constexpr int NN = decltype(nmt)::value, CC = decltype(cc)::value;
+            rc = sonet::launch_lds_once<&pooled_dgrad_mfma_kernel<NN, CC>, 128 * 1024>(what, dim3(ntile_l, B), dim3(128 * CC), lds, st, w.tile_off, w.ent_key,
+                                                                                    w.ent_val, wtp, E, M, C, C / 16, C1, C2, L, nbucket, gx1, g2);
+        };
+        if (ch == 2) launch(int_c<2>{}); else launch(int_c<1>{});
+    });
+    if (rc) return rc;
     return sonet::launched(what);
 }

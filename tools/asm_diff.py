@@ -11,7 +11,8 @@ scratch / occupancy summary) over ALL SRCS of either tree, whichever file it sit
 normalised (.LBB<n>_<m> to the order of the labels in the function, .Lfunc_end<n>, .Ltmp<n>, the names of static LDS symbols, the .section lines, the function's own name) and every
 function of the parent is compared with the one of this tree that tests/golden/launch/renamed.txt (old mangled name -> new, one pair per
 line) names for it, else with the one of the same name.  Prints per
-source file of this tree how many of its functions are identical and names every one that differs (with the number of differing lines),
+source file of this tree how many of its functions are identical and names every one that differs (with the number of differing lines
+and, for both sides, VGPRs, AGPRs, SGPRs, static LDS bytes, scratch bytes and occupancy from the function's summary comments),
 is new, or is gone.  Exit status 1 if any function differs or exists on one side only."""
 import difflib
 import os
@@ -99,6 +100,14 @@ def functions(lines, src):
     return out
 
 
+def resources(blocks):
+    """'VGPR a (+ AGPR), SGPR, LDS, scratch, occupancy' of a function, from the summary comments behind its code"""
+    text = '\n'.join(l for b in blocks for l in b)
+    get = lambda key: '/'.join(re.findall(r'; %s: (\d+)' % key, text)) or '?'
+    return 'VGPR %s AGPR %s SGPR %s LDS %s scratch %s occupancy %s' % tuple(
+        get(k) for k in ('NumVgprs', 'NumAgprs', 'TotalNumSgprs', 'LDSByteSize', 'ScratchSize', 'Occupancy'))
+
+
 def by_kernel(parent, extra, tmp, pool):
     names = renamed()
     sides = []
@@ -123,7 +132,7 @@ def by_kernel(parent, extra, tmp, pool):
             r[1].append('%s: only in the parent' % sym)
         else:
             nd = sum(1 for a, b in zip(o, n) for d in difflib.ndiff(a, b) if d[0] in '+-')
-            r[1].append('%s: %d differing lines of %d (was %s)' % (to, nd, sum(map(len, n)), was))
+            r[1].append('%s: %d differing lines of %d (was %s)\n        parent: %s\n        here:   %s' % (to, nd, sum(map(len, n)), was, resources(o), resources(n)))
     for sym in sorted(set(new) - seen):
         res.setdefault(new[sym][0][0], [0, []])[1].append('%s: only in this tree' % sym)
     for where in sorted(res):
