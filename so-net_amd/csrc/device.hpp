@@ -197,7 +197,7 @@ __device__ __forceinline__ void gmax_p16_store(float m0, float m1, float split_l
     dst[Lout * 8] = mv;                                        // form 1: two half planes (2 x Lout x 16 bytes) further
 }
 
-// ---- three-way bf16 split of an f32 pair (the "x3" arithmetic: pointmlp_x3.hip, upconv_bwd.hip) ------------------------------------
+// ---- three-way bf16 split of an f32 pair (the "x3" arithmetic: pointmlp_x3.hip, upconv_bwd.hip, upconv_wgrad.hip) ------------------------------------
 // (x0, x1) -> three packed bf16 pairs (hi, mid, lo), round-to-nearest at each level, residuals exact in f32
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
     h = cvt_pk_bf16(x0, x1);
@@ -228,6 +228,17 @@ __device__ __forceinline__ void split3_pair_w(float w0, float w1, unsigned &h, u
     split3_fix_w(w0, h0, m0, l0);
     split3_fix_w(w1, h1, m1, l1);
     h = h0 | (h1 << 16); m = m0 | (m1 << 16); l = l0 | (l1 << 16);
+}
+
+// The product of two split operands on v_mfma_f32_32x32x16_bf16: six of the nine piece products (Al.Bl, Al.Bm, Am.Bl are below f32's
+// last bit), the smallest first, added to acc in this order (pointmlp_x3.hip, upconv_bwd.hip, upconv_wgrad.hip)
+__device__ __forceinline__ void x3_chain(f32x16 &acc, bf16x8 Ah, bf16x8 Am, bf16x8 Al, bf16x8 Bh, bf16x8 Bm, bf16x8 Bl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
 }
 
 // cluster mean of the SOM stage (models/networks.py:142): sum / (count + 1e-5), every step rounded to f32 (no reciprocal, no FMA)

@@ -525,13 +525,7 @@ __global__ __launch_bounds__(X3_THREADS) void pointmlp_x3_kernel(
                     const bf16x8 Ah = __builtin_bit_cast(bf16x8, wsm[slot][(i * MT + mt) * 3 + 0][lane]);
                     const bf16x8 Am = __builtin_bit_cast(bf16x8, wsm[slot][(i * MT + mt) * 3 + 1][lane]);
                     const bf16x8 Al = __builtin_bit_cast(bf16x8, wsm[slot][(i * MT + mt) * 3 + 2][lane]);
-                    // smallest terms first
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[mt], 0, 0, 0);
+                    x3_chain(acc[mt], Ah, Am, Al, Bh, Bm, Bl);      // smallest terms first
                 }
                 }
             }

@@ -25,7 +25,7 @@
 //   * the sixteen (parity, tap) A fragments of its Cout block (2 KiB each) -- except those whose shifted operand lies in the padding for
 //     EVERY column of the tile, which are neither read nor multiplied (at 1 x 1: twelve of sixteen).
 // The next chunk's global loads are in flight in registers while this chunk's MFMAs run.
-#include "upconv_fold.hpp"               // tile extents, fold_range, acc_row, shape_ok: shared with upconv_bwd.hip
+#include "upconv_fold.hpp"               // the family's building blocks: shared with upconv_bwd.hip and upconv_wgrad.hip
 
 namespace {
 
@@ -38,30 +38,15 @@ __global__ __launch_bounds__(256) void upconv_pack_kernel(const float *__restric
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;        // ((ct * KC + kc) * 16 + pt) * 64 + lane; total is a multiple of 64
     if (t >= total) return;
     RangeAcc wr = {0, 0u};
-    const int lane = (int)(t & 63);
-    const long long r = t >> 6;
-    const int pt = (int)(r & 15);
-    const long long r2 = r >> 4;
-    const int kc = (int)(r2 % KC), ct = (int)(r2 / KC);
-    int ky0, ky1, kx0, kx1;
-    fold_range(pt >> 3, (pt >> 1) & 1, ky0, ky1);
-    fold_range((pt >> 2) & 1, pt & 1, kx0, kx1);
-    const int o = ct * UP_CB + (lane & 31), hh = lane >> 5;
+    const PackIdx ix = pack_index(t, KC);
+    const int lane = ix.lane;
+    const FoldRect rect = fold_rect(ix.pt);
+    const int o = ix.ct * UP_CB + (lane & 31), hh = lane >> 5;
     float wf[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int c = kc * UP_KC + 8 * hh + e;
-        double s = 0.0;
-        if (c < Cin) {
-            const float *w9 = W + ((long long)o * Cin + c) * 9;
-            for (int ky = ky0; ky <= ky1; ++ky)
-                for (int kx = kx0; kx <= kx1; ++kx) {
-                    const float v = w9[ky * 3 + kx];
-                    range_track(wr, v, v);
-                    s += (double)v;
-                }
-        }
-        wf[e] = (float)s;
+        const int c = ix.kc * UP_KC + 8 * hh + e;
+        wf[e] = c < Cin ? fold_sum(W + ((long long)o * Cin + c) * 9, rect, [&](float v) { range_track(wr, v, v); }) : 0.f;
     }
     unsigned h[4], m[4];
 #pragma unroll
@@ -69,7 +54,7 @@ __global__ __launch_bounds__(256) void upconv_pack_kernel(const float *__restric
         range_track(wr, wf[2 * p], wf[2 * p + 1]);
         p16_split_pair(wf[2 * p], wf[2 * p + 1], h[p], m[p]);
     }
-    uint4 *dst = Wp + (r * 2) * 64 + lane;
+    uint4 *dst = Wp + (ix.r * 2) * 64 + lane;
     dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
     dst[64] = make_uint4(m[0], m[1], m[2], m[3]);
     range_publish(trailer, wave_umax(range_amax_bits(wr)), lane);
@@ -102,7 +87,8 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_kernel(const UpArgs a
     const int NS = UP_TP + 2 * W + 2;
     const int c0 = cb * UP_TP;
 
-    // this lane's column and the LDS slots of its nine shifted neighbours
+    // this lane's column and the LDS slots of its nine shifted neighbours (the same text as upconv_bwd.hip, kept apart on purpose:
+    // docs/findings.md)
     const int c = c0 + wave * 32 + j;
     const bool colvalid = c < a.ncols;
     const int cc = colvalid ? c : 0;
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_kernel(const UpArgs a
     unsigned ptmask = 0;                  // (parity, tap) pairs whose weights are needed
 #pragma unroll
     for (int pt = 0; pt < 16; ++pt) {
-        const int k = ((pt >> 3) + ((pt >> 1) & 1)) * 3 + ((pt >> 2) & 1) + (pt & 1);
+        const int k = pair_shift(pt).k();
         if ((gmask >> k) & 1u) ptmask |= 1u << pt;
     }
 
@@ -169,9 +155,7 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_kernel(const UpArgs a
 
     f32x16 acc[4], tot[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[p][r] = 0.f; tot[p][r] = 0.f; }
+    for (int p = 0; p < 4; ++p) { zero_acc(acc[p]); zero_acc(tot[p]); }
     RangeAcc xrng = {0, 0u};
 
     fetch(0);
@@ -222,11 +206,7 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_kernel(const UpArgs a
         }
         if ((kc % UP_FLUSH) == UP_FLUSH - 1 || kc == KC - 1) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                tot[p] += acc[p];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-            }
+            for (int p = 0; p < 4; ++p) flush_chain(tot[p], acc[p]);
         }
     }
 
@@ -272,12 +252,9 @@ extern "C" size_t sonet_upconv3x3_pack_size(int Cin, int Cout)
 extern "C" int sonet_upconv3x3_pack_f32(const float *W, void *Wp, int Cin, int Cout, sonet_stream_t stream)
 {
     const char *what = "sonet_upconv3x3_pack_f32";
-    SONET_REQUIRE(W && Wp, "%s: NULL pointer", what);
-    SONET_REQUIRE(Cin > 0 && Cout > 0, "%s: non-positive size", what);
-    if (!shape_ok(Cin, Cout, 1, 1)) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout = %d is not a multiple of %d", what, Cout, UP_CB);
     const int KC = sonet::ceil_div(Cin, UP_KC);
     const long long total = (long long)(Cout / UP_CB) * KC * 16 * 64;
-    if (sonet::ceil_div64(total, 256) > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: %d x %d is too large", what, Cout, Cin);
+    if (const int rc = up_pack_check(what, W && Wp, /*aligned: not checked here*/ true, Cin, Cout, total)) return rc;
     unsigned *trailer = reinterpret_cast<unsigned *>(reinterpret_cast<uint4 *>(Wp) + total * 2);
     if (sonet::zero_words(trailer, 64, sonet::as_stream(stream)) != 0) return sonet::fail(SONET_ERR_LAUNCH, "%s: clearing the trailer failed", what);
     hipLaunchKernelGGL(upconv_pack_kernel, dim3((unsigned)sonet::ceil_div64(total, 256)), dim3(256), 0, sonet::as_stream(stream),
@@ -289,18 +266,12 @@ extern "C" int sonet_upconv3x3_f32(const float *x, const void *Wp, const float *
                                    int B, int Cin, int Cout, int H, int W, uint32_t *range_log, sonet_stream_t stream)
 {
     const char *what = "sonet_upconv3x3_f32";
-    SONET_REQUIRE(x && Wp && scale && shift && y, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((reinterpret_cast<uintptr_t>(Wp) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(x) & 3) == 0, "%s: misaligned pointer", what);
-    if (!shape_ok(Cin, Cout, H, W))
-        return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: needs Cout %% %d == 0 and 1 <= H, W <= %d (got Cout=%d H=%d W=%d)", what, UP_CB, UP_MAXHW,
-                           Cout, H, W);
-    const long long ncols = (long long)B * H * W;
+    const bool aligned = (reinterpret_cast<uintptr_t>(Wp) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(x) & 3) == 0;
+    if (const int rc = up_check(what, x && Wp && scale && shift && y, aligned, B, Cin, Cout, H, W)) return rc;
     const int CT = Cout / UP_CB, KC = sonet::ceil_div(Cin, UP_KC);
-    const long long nblk = sonet::ceil_div64(ncols, UP_TP) * CT;
-    if (ncols > 0x7FFF0000ll || nblk > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B * H * W = %lld is too large", what, ncols);
+    unsigned nblk;
     UpArgs a;
+    if (const int rc = up_grid(what, B, H, W, CT, a.ncols, nblk)) return rc;
     a.x = x;
     a.Wp = reinterpret_cast<const uint4 *>(Wp);
     a.scale = scale;
@@ -308,7 +279,7 @@ extern "C" int sonet_upconv3x3_f32(const float *x, const void *Wp, const float *
     a.y = y;
     a.rlog = range_log;
     a.trailer = reinterpret_cast<const unsigned *>(a.Wp + (size_t)CT * KC * 16 * 128);
-    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KC = KC; a.CT = CT; a.relu = relu != 0; a.ncols = (int)ncols;
-    hipLaunchKernelGGL(upconv3x3_kernel, dim3((unsigned)nblk), dim3(UP_THREADS), 0, sonet::as_stream(stream), a);
+    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KC = KC; a.CT = CT; a.relu = relu != 0;
+    hipLaunchKernelGGL(upconv3x3_kernel, dim3(nblk), dim3(UP_THREADS), 0, sonet::as_stream(stream), a);
     return sonet::launched(what);
 }

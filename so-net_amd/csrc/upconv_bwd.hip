@@ -33,31 +33,20 @@ __global__ __launch_bounds__(256) void upconv_dgrad_pack_kernel(const float *__r
 {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;        // ((ct * KC + kc) * 16 + pt) * 64 + lane; total is a multiple of 64
     if (t >= total) return;
-    const int lane = (int)(t & 63);
-    const long long r = t >> 6;
-    const int pt = (int)(r & 15);
-    const long long r2 = r >> 4;
-    const int kc = (int)(r2 % KC), ct = (int)(r2 / KC);
-    int ky0, ky1, kx0, kx1;
-    fold_range(pt >> 3, (pt >> 1) & 1, ky0, ky1);
-    fold_range((pt >> 2) & 1, pt & 1, kx0, kx1);
-    const int c = ct * 32 + (lane & 31), hh = lane >> 5;
+    const PackIdx ix = pack_index(t, KC);
+    const int lane = ix.lane;
+    const FoldRect rect = fold_rect(ix.pt);
+    const int c = ix.ct * 32 + (lane & 31), hh = lane >> 5;         // (the forward's pack with the two channel roles exchanged)
     float wf[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int o = kc * UP_KC + 8 * hh + e;
-        double s = 0.0;
-        if (c < Cin) {
-            const float *w9 = W + ((long long)o * Cin + c) * 9;
-            for (int ky = ky0; ky <= ky1; ++ky)
-                for (int kx = kx0; kx <= kx1; ++kx) s += (double)w9[ky * 3 + kx];
-        }
-        wf[e] = (float)s;
+        const int o = ix.kc * UP_KC + 8 * hh + e;
+        wf[e] = c < Cin ? fold_sum(W + ((long long)o * Cin + c) * 9, rect, [](float) {}) : 0.f;
     }
     unsigned h[4], m[4], l[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) split3_pair_w(wf[2 * p], wf[2 * p + 1], h[p], m[p], l[p]);
-    uint4 *dst = Wpt + (r * 3) * 64 + lane;
+    uint4 *dst = Wpt + (ix.r * 3) * 64 + lane;
     dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
     dst[64] = make_uint4(m[0], m[1], m[2], m[3]);
     dst[128] = make_uint4(l[0], l[1], l[2], l[3]);
@@ -91,7 +80,8 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_dgrad_kernel(const Dg
     const int NS = UP_TP + 2 * W + 2;
     const int c0 = cb * UP_TP;
 
-    // this lane's column and the LDS slots of its nine shifted neighbours, k = (sy + 1) * 3 + (sx + 1)
+    // this lane's column and the LDS slots of its nine shifted neighbours, k = (sy + 1) * 3 + (sx + 1) (the same text as upconv.hip, kept
+    // apart on purpose: docs/findings.md)
     const int c = c0 + wave * 32 + j;
     const bool colvalid = c < a.ncols;
     const int cc = colvalid ? c : 0;
@@ -111,10 +101,10 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_dgrad_kernel(const Dg
     if (lane == 0) atomicOr(&lds.mask, wmask);
     __syncthreads();
     const unsigned gmask = lds.mask;      // ... of the WORKGROUP
-    unsigned ptmask = 0;                  // (parity, tap) pairs whose weights are needed: pair pt reads the shift (1 - py - dy, 1 - px - dx)
+    unsigned ptmask = 0;                  // (parity, tap) pairs whose weights are needed: pair pt reads the MIRRORED shift (1 - py - dy, 1 - px - dx)
 #pragma unroll
     for (int pt = 0; pt < 16; ++pt) {
-        const int k = (2 - (pt >> 3) - ((pt >> 1) & 1)) * 3 + 2 - ((pt >> 2) & 1) - (pt & 1);
+        const int k = 8 - pair_shift(pt).k();
         if ((gmask >> k) & 1u) ptmask |= 1u << pt;
     }
 
@@ -160,8 +150,8 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_dgrad_kernel(const Dg
     };
 
     f32x16 acc, tot;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; tot[r] = 0.f; }
+    zero_acc(acc);
+    zero_acc(tot);
 
     const int NST = 2 * KC;
     fetch(0);
@@ -208,19 +198,10 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_dgrad_kernel(const Dg
                 const bf16x8 Ah = __builtin_bit_cast(bf16x8, lds.wsm[ptl][0][lane]);
                 const bf16x8 Am = __builtin_bit_cast(bf16x8, lds.wsm[ptl][1][lane]);
                 const bf16x8 Al = __builtin_bit_cast(bf16x8, lds.wsm[ptl][2][lane]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
+                x3_chain(acc, Ah, Am, Al, Bh, Bm, Bl);
             }
         }
-        if (py == 1 && (((st >> 1) % DG_FLUSH) == DG_FLUSH - 1 || st == NST - 1)) {
-            tot += acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        }
+        if (py == 1 && (((st >> 1) % DG_FLUSH) == DG_FLUSH - 1 || st == NST - 1)) flush_chain(tot, acc);
     }
 
     // epilogue: rows (r, h) of the Cin block that exist, this lane's column
@@ -245,13 +226,10 @@ extern "C" size_t sonet_upconv3x3_dgrad_pack_size(int Cin, int Cout)
 extern "C" int sonet_upconv3x3_dgrad_pack_f32(const float *W, void *Wpt, int Cin, int Cout, sonet_stream_t stream)
 {
     const char *what = "sonet_upconv3x3_dgrad_pack_f32";
-    SONET_REQUIRE(W && Wpt, "%s: NULL pointer", what);
-    SONET_REQUIRE(Cin > 0 && Cout > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((reinterpret_cast<uintptr_t>(Wpt) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 3) == 0, "%s: misaligned pointer", what);
-    if (!shape_ok(Cin, Cout, 1, 1)) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: Cout = %d is not a multiple of %d", what, Cout, UP_CB);
     const int KC = Cout / UP_KC;
     const long long total = (long long)sonet::ceil_div(Cin, 32) * KC * 16 * 64;
-    if (sonet::ceil_div64(total, 256) > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: %d x %d is too large", what, Cout, Cin);
+    const bool aligned = (reinterpret_cast<uintptr_t>(Wpt) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 3) == 0;
+    if (const int rc = up_pack_check(what, W && Wpt, aligned, Cin, Cout, total)) return rc;
     hipLaunchKernelGGL(upconv_dgrad_pack_kernel, dim3((unsigned)sonet::ceil_div64(total, 256)), dim3(256), 0, sonet::as_stream(stream),
                        W, reinterpret_cast<uint4 *>(Wpt), Cin, KC, total);
     return sonet::launched(what);
@@ -260,23 +238,17 @@ extern "C" int sonet_upconv3x3_dgrad_pack_f32(const float *W, void *Wpt, int Cin
 extern "C" int sonet_upconv3x3_dgrad_f32(const float *g, const void *Wpt, float *dx, int B, int Cin, int Cout, int H, int W, sonet_stream_t stream)
 {
     const char *what = "sonet_upconv3x3_dgrad_f32";
-    SONET_REQUIRE(g && Wpt && dx, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((reinterpret_cast<uintptr_t>(Wpt) & 15) == 0 && (reinterpret_cast<uintptr_t>(g) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(dx) & 3) == 0, "%s: misaligned pointer", what);
-    if (!shape_ok(Cin, Cout, H, W))
-        return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: needs Cout %% %d == 0 and 1 <= H, W <= %d (got Cout=%d H=%d W=%d)", what, UP_CB, UP_MAXHW,
-                           Cout, H, W);
-    const long long ncols = (long long)B * H * W;
+    const bool aligned = (reinterpret_cast<uintptr_t>(Wpt) & 15) == 0 && (reinterpret_cast<uintptr_t>(g) & 7) == 0 && (reinterpret_cast<uintptr_t>(dx) & 3) == 0;
+    if (const int rc = up_check(what, g && Wpt && dx, aligned, B, Cin, Cout, H, W)) return rc;
     const int CT = sonet::ceil_div(Cin, 32), KC = Cout / UP_KC;
-    const long long nblk = sonet::ceil_div64(ncols, UP_TP) * CT;
-    if (ncols > 0x7FFF0000ll || nblk > 0x7FFFFFFFll) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B * H * W = %lld is too large", what, ncols);
+    unsigned nblk;
     DgArgs a;
+    if (const int rc = up_grid(what, B, H, W, CT, a.ncols, nblk)) return rc;
     a.g = g;
     a.Wpt = reinterpret_cast<const uint4 *>(Wpt);
     a.dx = dx;
-    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KC = KC; a.CT = CT; a.ncols = (int)ncols;
-    const int rc = sonet::launch_lds_once<upconv3x3_dgrad_kernel, DG_LDS>(what, dim3((unsigned)nblk), dim3(UP_THREADS), DG_LDS,
+    a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KC = KC; a.CT = CT;
+    const int rc = sonet::launch_lds_once<upconv3x3_dgrad_kernel, DG_LDS>(what, dim3(nblk), dim3(UP_THREADS), DG_LDS,
                                                                           sonet::as_stream(stream), a);
     if (rc != SONET_OK) return rc;
     return sonet::launched(what);

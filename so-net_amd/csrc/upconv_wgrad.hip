@@ -46,6 +46,16 @@ constexpr int UW_CB = SONET_UPWGRAD_CIN_BLOCK;                         // input 
 constexpr size_t UW_WS_CAP = (size_t)64 << 20;                              // more slices than fit in this are not taken
 static_assert(UW_KSTEP == 16 && UW_CB == 32 && UW_FLUSH * UW_KSTEP <= 1024, "the kernel is written for these extents");
 
+// pair_shift(8 py + 4 px + q).k() from the wave's (py, px) and q = 2 dy + dx.  (Through pt the kernel's code changes: the MFMA loop keeps
+// this form, and the assertion holds it to the header's.)
+__host__ __device__ constexpr int uw_shift_k(int py, int px, int q) { return (py + (q >> 1)) * 3 + px + (q & 1); }
+constexpr bool uw_shift_k_ok() {
+    for (int pt = 0; pt < 16; ++pt)
+        if (uw_shift_k(pt >> 3, (pt >> 2) & 1, pt & 3) != pair_shift(pt).k()) return false;
+    return true;
+}
+static_assert(uw_shift_k_ok(), "the weight gradient's shift index is pair_shift's");
+
 struct UwPlan { int OB, CT, nstep, sps, nslice; long long ncols; size_t ws_bytes; };
 
 // slices: one per UW_SLICE columns, at most UW_MAXSL and at most what UW_WS_CAP holds; whole steps per slice, no empty slice
@@ -183,9 +193,7 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_wgrad_kernel(const Uw
 
     f32x16 acc[4], tot[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[q][r] = 0.f; tot[q][r] = 0.f; }
+    for (int q = 0; q < 4; ++q) { zero_acc(acc[q]); zero_acc(tot[q]); }
 
     int buf = 0, chain = 0;
     load(st0);
@@ -232,25 +240,16 @@ __global__ __launch_bounds__(UP_THREADS, 2) void upconv3x3_wgrad_kernel(const Uw
         for (int q = 0; q < 4; ++q) {                              // q = 2 dy + dx
             const int pt = 8 * py + 4 * px + q;
             if ((a.pairmask >> pt) & 1u) {
-                const int k = (py + (q >> 1)) * 3 + px + (q & 1);  // (sy + 1) * 3 + sx + 1 of the pair's shift
+                const int k = uw_shift_k(py, px, q);
                 const bf16x8 Bh = __builtin_bit_cast(bf16x8, lds.xs[buf][k][0][lane]);
                 const bf16x8 Bm = __builtin_bit_cast(bf16x8, lds.xs[buf][k][1][lane]);
                 const bf16x8 Bl = __builtin_bit_cast(bf16x8, lds.xs[buf][k][2][lane]);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[q], 0, 0, 0);
+                x3_chain(acc[q], Ah, Am, Al, Bh, Bm, Bl);
             }
         }
         if (++chain == UW_FLUSH || st + 1 == st1) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                tot[q] += acc[q];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-            }
+            for (int q = 0; q < 4; ++q) flush_chain(tot[q], acc[q]);
             chain = 0;
         }
         buf ^= 1;
@@ -293,10 +292,7 @@ __global__ __launch_bounds__(256) void upconv3x3_wgrad_reduce_kernel(const float
             double d = 0.0;
 #pragma unroll
             for (int q = 0; q < 16; ++q) {                         // q = 8 py + 4 px + 2 dy + dx, in this order
-                int y0, y1, x0, x1;
-                fold_range(q >> 3, (q >> 1) & 1, y0, y1);
-                fold_range((q >> 2) & 1, q & 1, x0, x1);
-                if (ky >= y0 && ky <= y1 && kx >= x0 && kx <= x1) d += sums[e2][q];
+                if (fold_rect(q).holds(ky, kx)) d += sums[e2][q];
             }
             dw[t2 * 9 + k9] = (float)d;
         }
@@ -315,15 +311,11 @@ extern "C" int sonet_upconv3x3_wgrad_f32(const float *g, const float *x, float *
                                          sonet_stream_t stream)
 {
     const char *what = "sonet_upconv3x3_wgrad_f32";
-    SONET_REQUIRE(g && x && dw && ws, "%s: NULL pointer", what);
-    SONET_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: non-positive size", what);
-    SONET_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(g) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(dw) & 3) == 0, "%s: misaligned pointer", what);
-    if (!shape_ok(Cin, Cout, H, W))
-        return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: needs Cout %% %d == 0 and 1 <= H, W <= %d (got Cout=%d H=%d W=%d)", what, UP_CB, UP_MAXHW,
-                           Cout, H, W);
+    const bool aligned = (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && (reinterpret_cast<uintptr_t>(g) & 7) == 0 &&
+                         (reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(dw) & 3) == 0;
+    if (const int rc = up_check(what, g && x && dw && ws, aligned, B, Cin, Cout, H, W)) return rc;
     UwPlan p;
-    if (!uw_plan(B, Cin, Cout, H, W, p)) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B * H * W = %lld is too large", what, (long long)B * H * W);
+    if (!uw_plan(B, Cin, Cout, H, W, p)) return up_too_many_columns(what, (long long)B * H * W);
     const long long nblk = (long long)p.nslice * p.OB * p.CT, total = (long long)Cout * Cin;
     if (nblk > 0x7FFFFFFFll || sonet::ceil_div64(total, 16) > 0x7FFFFFFFll)
         return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: %d x %d is too large", what, Cout, Cin);
@@ -331,11 +323,7 @@ extern "C" int sonet_upconv3x3_wgrad_f32(const float *g, const float *x, float *
     a.g = g; a.x = x;
     a.part = reinterpret_cast<float *>(ws);
     a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.CT = p.CT; a.OB = p.OB; a.ncols = (int)p.ncols; a.sps = p.sps; a.nstep = p.nstep;
-    a.pairmask = 0u;
-    for (int pt = 0; pt < 16; ++pt) {
-        const int sy = (pt >> 3) + ((pt >> 1) & 1) - 1, sx = ((pt >> 2) & 1) + (pt & 1) - 1;
-        if ((H > 1 || sy == 0) && (W > 1 || sx == 0)) a.pairmask |= 1u << pt;
-    }
+    a.pairmask = live_pairs(H, W);
     hipStream_t st = sonet::as_stream(stream);
     const bool vec = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
     const int rc = vec ? sonet::launch_lds_once<&upconv3x3_wgrad_kernel<true>, UW_LDS>(what, dim3((unsigned)nblk), dim3(UP_THREADS), UW_LDS, st, a)

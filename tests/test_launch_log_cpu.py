@@ -10,7 +10,11 @@ and the pooled sparse gradient) were appended later, recorded from the parent of
 them are byte for byte what they were.  That refactor merged kernels: tests/golden/launch/renamed.txt lists old name -> new name (names
 only), the tool prints a kernel under the first old name listed for it, and where the recording tells two merged kernels apart the texts
 are compared case by case with the names resolved (launch_log.expand) -- every case, return code, message, kernel, grid, block and LDS
-size still has to agree."""
+size still has to agree.
+
+The sections "upconv: ..." behind them (the decoder's up-convolutions: pack sizes, pack kernels, forward, input gradient, weight gradient
+and its workspace size) were appended the same way, recorded from the parent of that family's refactor.  The family reads no knob, so the
+variants fixture holds the half only where the variants build differs from the product build: nowhere."""
 import difflib
 import lzma
 import os
@@ -41,7 +45,7 @@ def test_renamed_holds_names_only():
 @pytest.mark.parametrize("name, flags", [("product", []), ("variants", ["--variants"])])
 def test_launchers_dispatch_as_recorded(name, flags):
     import launch_log
-    got = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "launch_log.py"), ROOT, "--bn"] + flags, stdout=subprocess.PIPE,
+    got = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "launch_log.py"), ROOT, "--bn", "--upconv"] + flags, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, universal_newlines=True)
     assert got.returncode == 0, got.stderr[-4000:]
     with lzma.open(os.path.join(GOLDEN, name + ".txt.xz"), "rt") as f:

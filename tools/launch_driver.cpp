@@ -3,7 +3,8 @@
 //   group \t case \t return code \t sonet_last_error() when refused \t the launches the stub recorded
 // group = entry point, optional features and channel pair; case = B x L and whatever else varies inside the group.
 // argv[1..]: group prefixes to run (none: all); "@bn": the family of the BatchNorm / ReLU passes (run_bn_* below) instead of the layer
-// launchers.  Built with -DSONET_VARIANTS for the variants library's extra entry points.
+// launchers; "@upconv": the decoder's up-convolution family (run_upconv below) instead.  Built with -DSONET_VARIANTS for the variants
+// library's extra entry points.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -550,6 +551,110 @@ void run_bn_pooled()
 #endif
 }
 
+// ---- the decoder's up-convolutions ("@upconv" in argv): the two pack sizes and pack kernels, the forward, the input gradient, the weight
+// gradient with its workspace size.  A size function's return value stands in the return-code column. ----
+void report_value(const std::string &group, const std::string &cs, size_t v)
+{
+    if (wanted(group)) printf("%s\t%s\t%zu\t\t%s\n", group.c_str(), cs.c_str(), v, launch_log_take());
+}
+
+const int UP_CINS[] = {1, 15, 16, 17, 33, 128, 1024}, UP_COUTS[] = {16, 32, 48, 96, 1024};
+const int UP_HW[] = {0, 1, 2, 5, 64, 65}, UP_BS[] = {0, 1, 3, 64};
+const int UP_B_MOST = 0x7FFF0000 / (64 * 64);   // B H W = 0x7FFF0000 at 64 x 64: the most columns taken; one more cloud is refused
+
+struct UpShape { int B, Cin, Cout, H, W; };
+// pointers: number -1 = none, else that one is NULL (mis = 0) or mis bytes off its allocation
+struct UpPtr {
+    int which = -1, mis = 0;
+    template <typename T = float> T *p(int i) const { return which == i ? (mis ? P<T>(i + 1, mis) : nullptr) : P<T>(i + 1); }
+};
+int up_fwd(const UpShape &s, const UpPtr &q = UpPtr()) {
+    return sonet_upconv3x3_f32(q.p(0), q.p<void>(1), q.p(2), q.p(3), 1, q.p(4), s.B, s.Cin, s.Cout, s.H, s.W, nullptr, ST); }
+int up_dgrad(const UpShape &s, const UpPtr &q = UpPtr()) {
+    return sonet_upconv3x3_dgrad_f32(q.p(0), q.p<void>(1), q.p(2), s.B, s.Cin, s.Cout, s.H, s.W, ST); }
+int up_wgrad(const UpShape &s, const UpPtr &q = UpPtr()) {
+    return sonet_upconv3x3_wgrad_f32(q.p(0), q.p(1), q.p(2), q.p<void>(3), s.B, s.Cin, s.Cout, s.H, s.W, ST); }
+int up_pack(const UpShape &s, const UpPtr &q = UpPtr()) { return sonet_upconv3x3_pack_f32(q.p(0), q.p<void>(1), s.Cin, s.Cout, ST); }
+int up_dgrad_pack(const UpShape &s, const UpPtr &q = UpPtr()) { return sonet_upconv3x3_dgrad_pack_f32(q.p(0), q.p<void>(1), s.Cin, s.Cout, ST); }
+
+struct UpEntry { const char *name; int (*call)(const UpShape &, const UpPtr &); int nptr; bool sized; };
+const UpEntry UP_ENTRIES[] = {{"sonet_upconv3x3_pack_f32", up_pack, 2, false}, {"sonet_upconv3x3_dgrad_pack_f32", up_dgrad_pack, 2, false},
+                              {"sonet_upconv3x3_f32", up_fwd, 5, true}, {"sonet_upconv3x3_dgrad_f32", up_dgrad, 3, true},
+                              {"sonet_upconv3x3_wgrad_f32", up_wgrad, 4, true}};
+
+void run_upconv()
+{
+    // the size functions
+    for (int Cin : {0, 1, 15, 16, 17, 33, 128, 1024})
+        for (int Cout : {0, 16, 32, 48, 96, 1024}) {
+            const std::string cs = fmt("%d>%d", Cin, Cout);
+            report_value("sonet_upconv3x3_pack_size", cs, sonet_upconv3x3_pack_size(Cin, Cout));
+            report_value("sonet_upconv3x3_dgrad_pack_size", cs, sonet_upconv3x3_dgrad_pack_size(Cin, Cout));
+        }
+    auto ws = [](const std::string &group, const UpShape &s) {
+        report_value(group, fmt("%dx%dx%d", s.B, s.H, s.W), sonet_upconv3x3_wgrad_ws_size(s.B, s.Cin, s.Cout, s.H, s.W));
+    };
+    for (const UpEntry &e : UP_ENTRIES) {
+        // every channel pair at three sizes
+        for (int Cin : UP_CINS)
+            for (int Cout : UP_COUTS) {
+                const std::string group = fmt("%s %d>%d", e.name, Cin, Cout);
+                if (!wanted(group)) continue;
+                if (!e.sized) { report(group, "pack", e.call({1, Cin, Cout, 1, 1}, UpPtr())); continue; }
+                for (const UpShape &s : {UpShape{1, Cin, Cout, 1, 1}, UpShape{3, Cin, Cout, 2, 5}, UpShape{64, Cin, Cout, 64, 64}}) {
+                    report(group, fmt("%dx%dx%d", s.B, s.H, s.W), e.call(s, UpPtr()));
+                    if (e.call == up_wgrad) ws(fmt("sonet_upconv3x3_wgrad_ws_size %d>%d", Cin, Cout), s);
+                }
+            }
+        const std::string R = fmt("%s refused", e.name);
+        for (int i = 0; i < e.nptr; ++i)
+            for (int mis : {0, 4, 8}) {
+                UpPtr q;
+                q.which = i; q.mis = mis;
+                // (W = 4 on 16-byte aligned operands is the weight gradient's vector kernel: a pointer 8 bytes off takes the other one)
+                if (wanted(R)) report(R, fmt(mis ? "pointer %d + %d" : "null pointer %d", i, mis), e.call({3, 17, 32, 2, 4}, q));
+            }
+        if (!wanted(R)) continue;
+        report(R, "Cin=0", e.call({3, 0, 32, 2, 4}, UpPtr()));
+        report(R, "Cout=0", e.call({3, 17, 0, 2, 4}, UpPtr()));
+        report(R, "Cin=-1", e.call({3, -1, 32, 2, 4}, UpPtr()));
+        if (!e.sized) continue;
+        // every B, H, W at three channel pairs
+        for (const UpShape &c : {UpShape{0, 17, 32, 0, 0}, UpShape{0, 128, 96, 0, 0}, UpShape{0, 1024, 1024, 0, 0}}) {
+            const std::string group = fmt("%s sizes %d>%d", e.name, c.Cin, c.Cout);
+            if (!wanted(group)) continue;
+            for (int B : UP_BS)
+                for (int H : UP_HW)
+                    for (int W : UP_HW) {
+                        const UpShape s{B, c.Cin, c.Cout, H, W};
+                        report(group, fmt("%dx%dx%d", B, H, W), e.call(s, UpPtr()));
+                        if (e.call == up_wgrad) ws(fmt("sonet_upconv3x3_wgrad_ws_size sizes %d>%d", c.Cin, c.Cout), s);
+                    }
+            for (int B : {UP_B_MOST, UP_B_MOST + 1, -1}) {
+                const UpShape s{B, c.Cin, c.Cout, 64, 64};
+                report(group, fmt("%dx64x64", B), e.call(s, UpPtr()));
+                if (e.call == up_wgrad) ws(fmt("sonet_upconv3x3_wgrad_ws_size sizes %d>%d", c.Cin, c.Cout), s);
+            }
+        }
+    }
+    // the weight gradient's choices: 16-byte loads (W % 4 == 0, g and x 16-byte aligned) or element-wise; the slice count against the
+    // 64 MiB workspace cap (16 x 1024 x 1024 floats = one slice exactly; a padded Cin above it: still one)
+    const char *G = "sonet_upconv3x3_wgrad_f32 vec";
+    for (int W : {4, 5, 8, 64})
+        for (int which : {-1, 0, 1}) {
+            UpPtr q;
+            q.which = which; q.mis = 8;
+            if (wanted(G)) report(G, fmt(which < 0 ? "W=%d aligned" : "W=%d pointer %d + 8", W, which), up_wgrad({3, 16, 32, 4, W}, q));
+        }
+    const char *C = "sonet_upconv3x3_wgrad_f32 workspace cap";
+    for (const UpShape &s : {UpShape{64, 1024, 1024, 64, 64}, UpShape{1, 1024, 1024, 64, 64}, UpShape{64, 1025, 1024, 64, 64}, UpShape{64, 512, 1024, 64, 64},
+                             UpShape{64, 1024, 512, 64, 64}, UpShape{64, 33, 32, 64, 64}}) {
+        if (wanted(C)) report(C, fmt("%dx%dx%d %d>%d", s.B, s.H, s.W, s.Cin, s.Cout), up_wgrad(s));
+        report_value("sonet_upconv3x3_wgrad_ws_size workspace cap", fmt("%dx%dx%d %d>%d", s.B, s.H, s.W, s.Cin, s.Cout),
+                     sonet_upconv3x3_wgrad_ws_size(s.B, s.Cin, s.Cout, s.H, s.W));
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -562,6 +667,9 @@ int main(int argc, char **argv)
             run_bn_coeffs();
             run_bn_head();
             run_bn_pooled();
+            return 0;
+        } else if (strcmp(argv[i], "@upconv") == 0) {
+            run_upconv();
             return 0;
         }
     run_pointmlp();

@@ -1,4 +1,4 @@
-"""tools/launch_log.py TREE [--variants] [--bn] [--full] [--summary] [--sanitize] -- what the layer launchers of a checkout launch, without a GPU.
+"""tools/launch_log.py TREE [--variants] [--bn] [--upconv] [--full] [--summary] [--sanitize] -- what the layer launchers of a checkout launch, without a GPU.
 
 Compiles every source of TREE's so-net_amd/csrc/Makefile SRCS host-only (the Makefile's FLAGS plus --cuda-host-only), links them with a
 recording stand-in for the HIP runtime (tools/launch_stub.cpp) and a driver with its own main (tools/launch_driver.cpp: the C ABI of
@@ -11,6 +11,9 @@ dropped; m = a hipMemsetAsync; E = index into the table of error texts; consecut
   == LAUNCH_LOG_CUS=...        the cases that differ from base with another CU count / a failing CU query
   == bn passes: ...            with --bn (without it the output is what it was before this half existed, byte for byte): the same for the family of the BatchNorm / ReLU passes (the driver's "@bn" half: the element-wise passes, the
                                coefficient kernels, the eval-mode head kernels, the pooled sparse gradient), behind K / E tables of its own
+  == upconv: ...               with --upconv (appended the same way): the decoder's up-convolutions (the driver's "@upconv" half: the two
+                               pack sizes and pack kernels, the forward, the input gradient, the weight gradient and its workspace size;
+                               a size function's return value stands where a return code does)
   --variants: the -DSONET_VARIANTS build.  base lists the cases that differ from the product build's; then one section per SONET_*
               knob setting (each value the code distinguishes and one it rejects) over the launchers that read it: per group of cases
               (entry point, features, channel pair) the number of cases that differ from base and a digest of the group's text --
@@ -274,8 +277,17 @@ def main():
                     bn_sections.append(('bn passes: %s=%s' % (knob, v), run(exe, {knob: v}, ['@bn'] + prefixes), bn, False))   # (always in full: a digest hangs on table indices)
         else:
             bn_sections.append(('bn passes: base', bn, None, False))
+        # the third half (--upconv): the decoder's up-convolutions.  The family reads no knob and asks for no CU count: the variants
+        # build gets the half only where its text differs from the product build's
+        up = run(exe, {}, ['@upconv']) if '--upconv' in flags else None
+        up_sections = []
+        if up is not None and not variants:
+            up_sections.append(('upconv: base', up, None, False))
+        elif up is not None and up != run(product, {}, ['@upconv']):
+            up_sections.append(('upconv: base, where it differs from the product build', up, run(product, {}, ['@upconv']), False))
     out = []
-    for head, secs in ((None, sections), ('bn passes: kernels and refusal texts', bn_sections))[:2 if bn_sections else 1]:
+    halves = [(None, sections)] + [(h, s) for h, s in (('bn passes: kernels and refusal texts', bn_sections), ('upconv: kernels and refusal texts', up_sections)) if s]
+    for head, secs in halves:
         names = Names([s[1] for s in secs] + [s[2] for s in secs if s[2] is not None])
         out += ([] if head is None else ['== ' + head]) + ['K%d %s' % (i, n) for i, n in enumerate(names.table)] + ['E%d %s' % (i, n) for i, n in enumerate(names.errors)]
         for title, res, ref, digest in secs:
