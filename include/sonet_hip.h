@@ -814,6 +814,36 @@ int sonet_chamfer_grad_f32(const float *pred, const float *gt, const int32_t *nn
                            const float *elem_bwd, const float *gscale, float *dpred, int32_t *bad, int B, int M, int N,
                            sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * chamfer_pyramid_loss / chamfer_pyramid_grad -- every Chamfer term of an autoencoder step in two launches
+ *   reference: models/autoencoder.py:83-98 (Model.optimize: up to three ChamferLoss calls against the same gt cloud)
+ * L in {1, 2, 3} predicted clouds pred[l] [B][3][M[l]] f32 against ONE gt [B][3][N] f32.  pred, nn_pg, nn_gp, elem_fwd, elem_bwd and
+ * dpred are HOST arrays of L device pointers, M a HOST array of L ints; they are read before the entry returns.
+ * sonet_chamfer_pyramid_loss_f32: one launch for every (level, direction), then a small launch for the sums.  Per level l the outputs
+ * of sonet_chamfer_loss_f32(pred[l], gt), bit for bit: nn_pg[l] [B][M[l]] i32, nn_gp[l] [B][N] i32, elem_fwd[l] [B][M[l]] f32,
+ * elem_bwd[l] [B][N] f32, and sums [B][L][2] f64 (the same float64 partials per 256 queries, added in the same ascending order; no
+ * floating-point atomics).  Each of the four output arrays may be NULL, and so may each of their entries: that output is not written;
+ * sums is always written.  ws: sonet_chamfer_pyramid_ws_size bytes (0 for non-positive sizes or L outside 1..3; M1, M2 are ignored
+ * for levels at or above L).
+ * sonet_chamfer_pyramid_grad_f32: dpred[l] [B][3][M[l]] f32 for every level in one launch, bit for bit what sonet_chamfer_grad_f32
+ * gives for (pred[l], gt, nn_pg[l], nn_gp[l], elem_fwd[l], elem_bwd[l], gscale + 2 l): gscale [L][2] f32 ON THE DEVICE, float64 terms,
+ * the level's own forward term first, then the backward terms in ascending n, rounded once.  The terms of a predicted point are found
+ * through a stable inverse list (the keys (nn_gp[n] << 16) | n of a cloud sorted in LDS), not by comparing every predicted point with
+ * every gt point: two runs, and a replay from a captured graph, give the same bits.  An index entry outside its range contributes
+ * nothing, is never used as an address, and is counted in bad[l] (bad [L] i32, zeroed by the entry).
+ * B <= 65535, N <= sonet_chamfer_pyramid_max_n(), M[l] <= sonet_chamfer_pyramid_max_m(): beyond them both entries return
+ * SONET_ERR_UNSUPPORTED before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+int sonet_chamfer_pyramid_max_n(void);
+int sonet_chamfer_pyramid_max_m(void);
+size_t sonet_chamfer_pyramid_ws_size(int B, int L, int M0, int M1, int M2, int N);
+int sonet_chamfer_pyramid_loss_f32(const float *const *pred, const float *gt, int32_t *const *nn_pg /* may be NULL */,
+                                   int32_t *const *nn_gp /* may be NULL */, float *const *elem_fwd /* may be NULL */,
+                                   float *const *elem_bwd /* may be NULL */, double *sums, void *ws, int B, int L, const int *M, int N,
+                                   sonet_stream_t stream);
+int sonet_chamfer_pyramid_grad_f32(const float *const *pred, const float *gt, const int32_t *const *nn_pg, const int32_t *const *nn_gp,
+                                   const float *const *elem_fwd, const float *const *elem_bwd, const float *gscale, float *const *dpred,
+                                   int32_t *bad, int B, int L, const int *M, int N, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * seg_metrics  -- everything the part-segmentation test loop reports, from one read of the score tensor
  *   reference: part-seg/train.py:87-104 (loss, accuracy, IoU per test batch), models/losses.py:119-189 (compute_iou)
  * score [B][C][N] f32 (the layout of score_segmenter), seg [B][N] i64 per-point part labels, label [B] i64 category of every cloud,

@@ -282,6 +282,199 @@ __global__ __launch_bounds__(256) void chamfer_nn2_finalize_kernel(const unsigne
     nn_b[t] = k < C2_INIT ? (int32_t)(unsigned)(k & 0xFFFFFFFFull) : 0;
 }
 #endif  // SONET_VARIANTS
+
+// ---- the loss pyramid of one autoencoder step (models/autoencoder.py:83-98): up to three predicted clouds against ONE gt cloud ------
+// chamfer_pyramid_loss_kernel is chamfer_loss_kernel with the level picked by the workgroup index: per cloud, level l owns the
+// workgroups [blk0, blk0 + nblk_f + nblk_b) -- predicted -> gt first, then gt -> predicted, 256 consecutive queries each -- so every
+// index, element and float64 partial is the one chamfer_loss_kernel forms for that level alone, and the sums kernel adds a
+// (cloud, level, direction)'s partials in the same ascending order.
+constexpr int PYR_LEVELS = 3;
+constexpr int PYR_THREADS = 1024;                                // the gradient kernel's workgroup
+constexpr int PYR_MAX_N = 8192;                                  // gt points: one cloud's keys are sorted in one LDS array
+constexpr int PYR_MAX_M = 65535;                                 // predicted points: m sits in the upper 16 bits of a key, 0xFFFF is "no owner"
+constexpr unsigned PYR_NO_OWNER = 0xFFFFFFFFu;
+
+struct PyrLossLevel {
+    const float *pred;
+    int32_t *nn_pg, *nn_gp;
+    float *elem_fwd, *elem_bwd;
+    int M, blk0, nblk_f;
+};
+struct PyrLossArgs {
+    PyrLossLevel lv[PYR_LEVELS];
+};
+
+__global__ __launch_bounds__(CH_THREADS) void chamfer_pyramid_loss_kernel(const PyrLossArgs a, const float *__restrict__ gt,
+                                                                           double *__restrict__ part, int L, int N)
+{
+    __shared__ float4 txy[CH_TILE / 2];
+    __shared__ float2 tz[CH_TILE / 2];
+    __shared__ double s_sum[CH_WAVES];
+    const int b = blockIdx.y;
+    PyrLossLevel v = a.lv[0];                                    // (uniform over the workgroup: kernel arguments and blockIdx)
+    if (L > 1 && (int)blockIdx.x >= a.lv[1].blk0) v = a.lv[1];
+    if (L > 2 && (int)blockIdx.x >= a.lv[2].blk0) v = a.lv[2];
+    const int M = v.M;
+    const int rel = (int)blockIdx.x - v.blk0;
+    const bool fwd = rel < v.nblk_f;
+    const int blk = fwd ? rel : rel - v.nblk_f;
+    const int Nq = fwd ? M : N, Nd = fwd ? N : M;
+    const float *qb = (fwd ? v.pred : gt) + (size_t)b * 3 * Nq, *dbb = (fwd ? gt : v.pred) + (size_t)b * 3 * Nd;
+    int32_t *nn = fwd ? v.nn_pg : v.nn_gp;
+    float *elem = fwd ? v.elem_fwd : v.elem_bwd;
+    const int i = blk * CH_THREADS + threadIdx.x;
+    const bool valid = i < Nq;
+    const float px = valid ? qb[i] : 0.f, py = valid ? qb[Nq + i] : 0.f, pz = valid ? qb[2 * (size_t)Nq + i] : 0.f;
+    const int bi = chamfer_search(dbb, Nd, px, py, pz, txy, tz);          // in [0, Nd)
+    double e64 = 0.0;
+    if (valid) {
+        const float e = chamfer_element(dbb[bi], dbb[Nd + bi], dbb[2 * (size_t)Nd + bi], px, py, pz);
+        if (nn) nn[(size_t)b * Nq + i] = bi;
+        if (elem) elem[(size_t)b * Nq + i] = e;
+        e64 = (double)e;
+    }
+    const double wsum = ch_wave_sum_f64(e64);
+    if ((threadIdx.x & (sonet::WAVE - 1)) == 0) s_sum[threadIdx.x / sonet::WAVE] = wsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double acc = s_sum[0];
+#pragma unroll
+        for (int w = 1; w < CH_WAVES; ++w) acc += s_sum[w];
+        part[(size_t)b * gridDim.x + blockIdx.x] = acc;
+    }
+}
+
+struct PyrSumsArgs {
+    int blk0[PYR_LEVELS], nblk_f[PYR_LEVELS];
+};
+
+// one thread per (cloud, level, direction): sums [B][L][2] from the workgroup partials [B][nblk], ascending
+__global__ __launch_bounds__(64) void chamfer_pyramid_sums_kernel(const PyrSumsArgs a, const double *__restrict__ part,
+                                                                   double *__restrict__ sums, int B, int L, int nblk, int nblk_b)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= 2 * B * L) return;
+    const int dir = t & 1, l = (t >> 1) % L, b = (t >> 1) / L;
+    const int blk0 = l == 0 ? a.blk0[0] : l == 1 ? a.blk0[1] : a.blk0[2];
+    const int nblk_f = l == 0 ? a.nblk_f[0] : l == 1 ? a.nblk_f[1] : a.nblk_f[2];
+    const double *p = part + (size_t)b * nblk + blk0 + (dir ? nblk_f : 0);
+    const int n = dir ? nblk_b : nblk_f;
+    double acc = p[0];
+    for (int k = 1; k < n; ++k) acc += p[k];
+    sums[t] = acc;
+}
+
+// ---- gradient of every level in one launch, from stable inverse lists instead of an M x N compare --------------------------------
+// One workgroup per (cloud, level).  The keys (nn_gp[n] << 16) | n of the cloud's gt points are sorted in LDS (the bitonic network of
+// retrieval.hip on 32-bit keys; n makes every key distinct, so the order is total: ascending owner m, then ascending n -- the order
+// chamfer_grad_kernel meets the terms of m in).  An entry outside [0, M) gets the key PYR_NO_OWNER, which sorts behind every owner,
+// is counted and is never an address.  A thread then takes predicted points m = tid, tid + 1024, ...: its own forward term first,
+// then a binary search for the first key of m and a walk to the last one.  B (M + N) terms and N log^2 N compare-exchanges per level,
+// the arithmetic of chamfer_grad_kernel term for term: the same bits.
+__device__ __forceinline__ void pyr_compare_exchange(unsigned *buf, int i, int j, int k)
+{
+    const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+    const unsigned a = buf[lo], b = buf[hi];
+    if ((a > b) == ((lo & k) == 0)) {
+        buf[lo] = b;
+        buf[hi] = a;
+    }
+}
+
+// P keys (a power of two), thread t owning the pairs t, t + PYR_THREADS, ...: the stages with a stride above 64 end in a workgroup
+// barrier; at strides 64 .. 1 the 64 pairs of a wave stay inside one block of 128 keys that no other wave touches, so those stages run
+// back to back in the wave's own in-order LDS queue and one barrier closes them.
+__device__ __forceinline__ void pyr_bitonic_sort(unsigned *buf, int P, int tid)
+{
+    for (int k = 2; k <= P; k <<= 1) {
+        int j = k >> 1;
+        for (; j > 64; j >>= 1) {
+            for (int i = tid; i < (P >> 1); i += PYR_THREADS) pyr_compare_exchange(buf, i, j, k);
+            __syncthreads();
+        }
+        for (int i = tid; i < (P >> 1); i += PYR_THREADS) {
+            for (int jj = j; jj > 0; jj >>= 1) {
+                pyr_compare_exchange(buf, i, jj, k);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+    }
+}
+
+struct PyrGradLevel {
+    const float *pred;
+    const int32_t *nn_pg, *nn_gp;
+    const float *elem_fwd, *elem_bwd;
+    float *dpred;
+    int M;
+};
+struct PyrGradArgs {
+    PyrGradLevel lv[PYR_LEVELS];
+};
+
+__global__ __launch_bounds__(PYR_THREADS) void chamfer_pyramid_grad_kernel(const PyrGradArgs a, const float *__restrict__ gt,
+                                                                            const float *__restrict__ gscale, int32_t *__restrict__ bad,
+                                                                            int B, int N, int P)
+{
+    __shared__ unsigned keys[PYR_MAX_N];
+    __shared__ int s_bad;
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const PyrGradLevel v = l == 0 ? a.lv[0] : l == 1 ? a.lv[1] : a.lv[2];
+    const int M = v.M;
+    const float *pb = v.pred + (size_t)b * 3 * M, *gb = gt + (size_t)b * 3 * N;
+    if (tid == 0) s_bad = 0;
+    int nbad = 0;
+    for (int n = tid; n < P; n += PYR_THREADS) {                 // (P <= PYR_MAX_N; the tail [N, P) is padding)
+        unsigned key = PYR_NO_OWNER;
+        if (n < N) {
+            const int j = v.nn_gp[(size_t)b * N + n];
+            if (j >= 0 && j < M) key = ((unsigned)j << 16) | (unsigned)n;
+            else ++nbad;
+        }
+        keys[n] = key;
+    }
+    __syncthreads();
+    pyr_bitonic_sort(keys, P, tid);
+    const double cf = (double)gscale[2 * l] / ((double)B * (double)M), cb = (double)gscale[2 * l + 1] / ((double)B * (double)N);
+    for (int m = tid; m < M; m += PYR_THREADS) {
+        const float px = pb[m], py = pb[M + m], pz = pb[2 * (size_t)M + m];
+        double ax = 0.0, ay = 0.0, az = 0.0;
+        const int j = v.nn_pg[(size_t)b * M + m];
+        if (j >= 0 && j < N) {
+            const double e = (double)v.elem_fwd[(size_t)b * M + m];
+            ax = cf * ((double)px - (double)gb[j]) / e;
+            ay = cf * ((double)py - (double)gb[N + j]) / e;
+            az = cf * ((double)pz - (double)gb[2 * (size_t)N + j]) / e;
+        } else {
+            ++nbad;
+        }
+        const unsigned first = (unsigned)m << 16;                // the smallest key m can own
+        int lo = 0, hi = N;                                      // (keys [0, N): every real entry; the padding sorts behind them)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (keys[mid] < first) lo = mid + 1;
+            else hi = mid;
+        }
+        for (int i = lo; i < N; ++i) {
+            const unsigned key = keys[i];
+            if ((key >> 16) != (unsigned)m) break;
+            const int n = (int)(key & 0xFFFFu);                  // < N: only entries with n < N carry an owner
+            const double e = (double)v.elem_bwd[(size_t)b * N + n];
+            ax += cb * ((double)px - (double)gb[n]) / e;
+            ay += cb * ((double)py - (double)gb[N + n]) / e;
+            az += cb * ((double)pz - (double)gb[2 * (size_t)N + n]) / e;
+        }
+        float *o = v.dpred + (size_t)b * 3 * M;
+        o[m] = (float)ax;
+        o[M + m] = (float)ay;
+        o[2 * (size_t)M + m] = (float)az;
+    }
+    if (nbad) atomicAdd(&s_bad, nbad);
+    __syncthreads();
+    if (tid == 0 && s_bad) atomicAdd(bad + l, s_bad);
+}
 }  // namespace
 
 #ifdef SONET_VARIANTS
@@ -359,5 +552,90 @@ extern "C" int sonet_chamfer_grad_f32(const float *pred, const float *gt, const 
     if (int rc = sonet::zero_words(bad, 4, st)) return rc;
     hipLaunchKernelGGL(chamfer_grad_kernel, dim3(sonet::ceil_div(M, CH_THREADS), B), dim3(CH_THREADS), 0, st, pred, gt, nn_pg, nn_gp,
                        elem_fwd, elem_bwd, gscale, dpred, bad, (double)B * (double)M, (double)B * (double)N, M, N);
+    return sonet::launched(what);
+}
+
+// ---- the loss pyramid: every level and both directions in one launch, every level's gradient in one more ------------------------------
+extern "C" int sonet_chamfer_pyramid_max_n(void) { return PYR_MAX_N; }
+extern "C" int sonet_chamfer_pyramid_max_m(void) { return PYR_MAX_M; }
+
+namespace {
+// what both entries ask of the sizes; M may be NULL only when the caller's own check has failed already
+int pyramid_sizes(const char *what, int B, int L, const int *M, int N)
+{
+    SONET_REQUIRE(L >= 1 && L <= PYR_LEVELS, "%s: L=%d outside 1..%d", what, L, PYR_LEVELS);
+    SONET_REQUIRE(M, "%s: NULL pointer", what);
+    SONET_REQUIRE(B > 0 && N > 0, "%s: non-positive size (B=%d N=%d)", what, B, N);
+    for (int l = 0; l < L; ++l) SONET_REQUIRE(M[l] > 0, "%s: non-positive size (M[%d]=%d)", what, l, M[l]);
+    if (B > 65535) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: B=%d > 65535", what, B);
+    if (N > PYR_MAX_N) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: N=%d > %d", what, N, PYR_MAX_N);
+    for (int l = 0; l < L; ++l)
+        if (M[l] > PYR_MAX_M) return sonet::fail(SONET_ERR_UNSUPPORTED, "%s: M[%d]=%d > %d", what, l, M[l], PYR_MAX_M);
+    return SONET_OK;
+}
+}  // namespace
+
+extern "C" size_t sonet_chamfer_pyramid_ws_size(int B, int L, int M0, int M1, int M2, int N)
+{
+    const int M[PYR_LEVELS] = {M0, M1, M2};
+    if (B <= 0 || L < 1 || L > PYR_LEVELS || N <= 0) return 0;
+    long long nblk = 0;
+    for (int l = 0; l < L; ++l) {
+        if (M[l] <= 0) return 0;
+        nblk += sonet::ceil_div64(M[l], CH_THREADS) + sonet::ceil_div64(N, CH_THREADS);
+    }
+    return (size_t)B * (size_t)nblk * sizeof(double);
+}
+
+extern "C" int sonet_chamfer_pyramid_loss_f32(const float *const *pred, const float *gt, int32_t *const *nn_pg, int32_t *const *nn_gp,
+                                              float *const *elem_fwd, float *const *elem_bwd, double *sums, void *ws, int B, int L,
+                                              const int *M, int N, sonet_stream_t stream)
+{
+    const char *what = "sonet_chamfer_pyramid_loss_f32";
+    if (int rc = pyramid_sizes(what, B, L, M, N)) return rc;
+    SONET_REQUIRE(pred && gt && sums && ws, "%s: NULL pointer", what);
+    for (int l = 0; l < L; ++l) SONET_REQUIRE(pred[l], "%s: NULL pointer (pred[%d])", what, l);
+    hipStream_t st = sonet::as_stream(stream);
+    const int nblk_b = sonet::ceil_div(N, CH_THREADS);
+    PyrLossArgs a = {};
+    PyrSumsArgs s = {};
+    int nblk = 0;
+    for (int l = 0; l < L; ++l) {
+        PyrLossLevel &v = a.lv[l];
+        v.pred = pred[l];
+        v.nn_pg = nn_pg ? nn_pg[l] : nullptr;
+        v.nn_gp = nn_gp ? nn_gp[l] : nullptr;
+        v.elem_fwd = elem_fwd ? elem_fwd[l] : nullptr;
+        v.elem_bwd = elem_bwd ? elem_bwd[l] : nullptr;
+        v.M = M[l];
+        v.blk0 = s.blk0[l] = nblk;
+        v.nblk_f = s.nblk_f[l] = sonet::ceil_div(M[l], CH_THREADS);
+        nblk += v.nblk_f + nblk_b;
+    }
+    double *part = reinterpret_cast<double *>(ws);
+    hipLaunchKernelGGL(chamfer_pyramid_loss_kernel, dim3(nblk, B), dim3(CH_THREADS), 0, st, a, gt, part, L, N);
+    hipLaunchKernelGGL(chamfer_pyramid_sums_kernel, dim3(sonet::ceil_div(2 * B * L, 64)), dim3(64), 0, st, s, part, sums, B, L, nblk,
+                       nblk_b);
+    return sonet::launched(what);
+}
+
+extern "C" int sonet_chamfer_pyramid_grad_f32(const float *const *pred, const float *gt, const int32_t *const *nn_pg,
+                                              const int32_t *const *nn_gp, const float *const *elem_fwd, const float *const *elem_bwd,
+                                              const float *gscale, float *const *dpred, int32_t *bad, int B, int L, const int *M, int N,
+                                              sonet_stream_t stream)
+{
+    const char *what = "sonet_chamfer_pyramid_grad_f32";
+    if (int rc = pyramid_sizes(what, B, L, M, N)) return rc;
+    SONET_REQUIRE(pred && gt && nn_pg && nn_gp && elem_fwd && elem_bwd && gscale && dpred && bad, "%s: NULL pointer", what);
+    PyrGradArgs a = {};
+    for (int l = 0; l < L; ++l) {
+        SONET_REQUIRE(pred[l] && nn_pg[l] && nn_gp[l] && elem_fwd[l] && elem_bwd[l] && dpred[l], "%s: NULL pointer (level %d)", what, l);
+        a.lv[l] = PyrGradLevel{pred[l], nn_pg[l], nn_gp[l], elem_fwd[l], elem_bwd[l], dpred[l], M[l]};
+    }
+    hipStream_t st = sonet::as_stream(stream);
+    if (int rc = sonet::zero_words(bad, 4 * (size_t)L, st)) return rc;
+    int P = 2;                                                   // the sort's extent: the power of two at or above N
+    while (P < N) P <<= 1;
+    hipLaunchKernelGGL(chamfer_pyramid_grad_kernel, dim3(L, B), dim3(PYR_THREADS), 0, st, a, gt, gscale, bad, B, N, P);
     return sonet::launched(what);
 }

@@ -95,3 +95,66 @@ class ChamferLoss(nn.Module):
         self.backward_loss_array = backward_loss_element.mean(dim=1).mean(dim=1)
         self.loss_array = self.forward_loss_array + self.backward_loss_array
         return self.forward_loss + self.backward_loss
+
+
+class AutoencoderLoss(nn.Module):
+    """The Chamfer terms that enter ``loss`` in ``Model.optimize`` (models/autoencoder.py:83-98): the final cloud alone at
+    ``opt.output_conv_pc_num == 0``, plus ``decoder.conv_pc4`` at 1024, plus ``decoder.conv_pc5`` and ``decoder.conv_pc4`` at 4096, each
+    against the same ground-truth cloud.  ``forward(predicted_pc, decoder, gt)`` returns ``loss`` and sets ``loss``, ``loss_chamfer``,
+    ``loss_chamfer_conv4`` and ``loss_chamfer_conv5`` (None where the term does not enter the loss).
+
+    With ``opt.chamfer_pyramid`` set, CUDA float32 clouds, a gt that asks for no gradient and sizes inside the operator's extents, every
+    term comes from ONE ``ops.chamfer_pyramid_loss`` call (one loss launch, one deterministic gradient launch per step).  In every other
+    case -- the option absent included -- the terms are ``ChamferLoss`` calls in the reference's order (conv5, conv4, the final cloud),
+    and ``chamfer_criteria`` holds what the last of them left."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.chamfer_criteria = ChamferLoss(opt)
+        self.loss = self.loss_chamfer = self.loss_chamfer_conv4 = self.loss_chamfer_conv5 = None
+
+    @staticmethod
+    def pyramid_enabled(opt):
+        """``opt.chamfer_pyramid``: absent, None, False or 0 is off."""
+        return bool(getattr(opt, "chamfer_pyramid", False))
+
+    def terms(self, predicted_pc, decoder):
+        """[(attribute name, predicted cloud)] in the order the reference adds them up (autoencoder.py:93-98)."""
+        n = self.opt.output_conv_pc_num
+        out = [("loss_chamfer", predicted_pc)]
+        if n == 4096:
+            out.append(("loss_chamfer_conv5", decoder.conv_pc5))
+        if n in (1024, 4096):
+            out.append(("loss_chamfer_conv4", decoder.conv_pc4))
+        return out
+
+    def _takes_pyramid(self, clouds, gt):
+        if not self.pyramid_enabled(self.opt) or gt.requires_grad or gt.dim() != 3:
+            return False
+        for t in clouds + [gt]:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[1] == 3 and t.shape[0] == gt.shape[0]):
+                return False
+        return 1 <= gt.shape[0] <= 65535 and _ops.chamfer_pyramid_supported([c.shape[2] for c in clouds], gt.shape[2])
+
+    def forward(self, predicted_pc, decoder, gt):
+        terms = self.terms(predicted_pc, decoder)
+        self.loss_chamfer = self.loss_chamfer_conv4 = self.loss_chamfer_conv5 = None
+        clouds = [c for _, c in terms]
+        if self._takes_pyramid(clouds, gt):
+            levels = _ops.chamfer_pyramid_loss([c.contiguous() for c in clouds], gt.contiguous())
+            for (name, _), (fl, bl, _fa, _ba) in zip(terms, levels):
+                setattr(self, name, fl + bl)
+            (self.forward_loss, self.backward_loss, self.forward_loss_array, self.backward_loss_array) = levels[0]
+            self.loss_array = self.forward_loss_array + self.backward_loss_array
+        else:
+            for name, cloud in terms[1:] + terms[:1]:                # the reference's order of calls: conv5, conv4, the final cloud
+                setattr(self, name, self.chamfer_criteria(cloud, gt))
+            c = self.chamfer_criteria
+            (self.forward_loss, self.backward_loss, self.forward_loss_array, self.backward_loss_array, self.loss_array) = (
+                c.forward_loss, c.backward_loss, c.forward_loss_array, c.backward_loss_array, c.loss_array)
+        loss = self.loss_chamfer
+        for name, _ in terms[1:]:                                    # loss_chamfer + loss_chamfer_conv5 + loss_chamfer_conv4
+            loss = loss + getattr(self, name)
+        self.loss = loss
+        return loss

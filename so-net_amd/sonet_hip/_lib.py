@@ -167,6 +167,11 @@ SIGNATURES = {
     "sonet_chamfer_loss_ws_size": [_i, _i, _i],
     "sonet_chamfer_loss_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "sonet_chamfer_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_chamfer_pyramid_max_n": [],
+    "sonet_chamfer_pyramid_max_m": [],
+    "sonet_chamfer_pyramid_ws_size": [_i, _i, _i, _i, _i, _i],
+    "sonet_chamfer_pyramid_loss_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp],
+    "sonet_chamfer_pyramid_grad_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp],
     "sonet_upconv3x3_pack_size": [_i, _i],
     "sonet_upconv3x3_pack_f32": [_vp, _vp, _i, _i, _vp],
     "sonet_upconv3x3_f32": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp],
@@ -209,6 +214,7 @@ _RESTYPES = {
     "sonet_som_assign_sort_ws_size": ctypes.c_size_t,
     "sonet_chamfer_nn2_ws_size": ctypes.c_size_t,
     "sonet_chamfer_loss_ws_size": ctypes.c_size_t,
+    "sonet_chamfer_pyramid_ws_size": ctypes.c_size_t,
     "sonet_upconv3x3_pack_size": ctypes.c_size_t,
     "sonet_upconv3x3_dgrad_pack_size": ctypes.c_size_t,
     "sonet_upconv3x3_wgrad_ws_size": ctypes.c_size_t,

@@ -2535,6 +2535,178 @@ def chamfer_loss(pred, gt):
     return _ChamferLoss.apply(pred, gt)
 
 
+# ------------------------------------------------------------------------------------------ Chamfer loss pyramid
+# Extents of csrc/chamfer.hip (sonet_chamfer_pyramid_max_n / _max_m): a cloud's gt keys are sorted in one LDS array, and a predicted
+# point's index sits in the upper 16 bits of a key.
+CHAMFER_PYRAMID_MAX_LEVELS = 3
+CHAMFER_PYRAMID_MAX_N = 8192
+CHAMFER_PYRAMID_MAX_M = 65535
+
+
+def chamfer_pyramid_supported(Ms, N):
+    """Sizes the pyramid operator takes: 1 to 3 levels of 1 <= M_l <= CHAMFER_PYRAMID_MAX_M points, 1 <= N <= CHAMFER_PYRAMID_MAX_N."""
+    return (1 <= len(Ms) <= CHAMFER_PYRAMID_MAX_LEVELS and all(1 <= int(M) <= CHAMFER_PYRAMID_MAX_M for M in Ms)
+            and 1 <= int(N) <= CHAMFER_PYRAMID_MAX_N)
+
+
+class ChamferPyramidTerms:
+    """One ``chamfer_pyramid_terms`` call: ``levels`` a list of ``ChamferTerms`` (level l's ``sums`` is the B x 2 view ``sums[:, l]``),
+    ``sums`` B x L x 2 f64, ``N`` the gt point count."""
+    __slots__ = ("levels", "sums", "N")
+
+
+def _chk_pyramid(preds, gt):
+    """preds: 1 to 3 clouds B x 3 x M_l, gt B x 3 x N, each as ``_chk_clouds`` asks; sizes inside the exported extents."""
+    if not isinstance(preds, (list, tuple)) or not 1 <= len(preds) <= CHAMFER_PYRAMID_MAX_LEVELS:
+        raise SonetHipError("chamfer_pyramid: preds must be a list of 1 to %d predicted clouds" % CHAMFER_PYRAMID_MAX_LEVELS)
+    dev = B = N = None
+    for p in preds:
+        dev, B, _, N = _chk_clouds(p, gt)
+    _same_device(gt, *preds)
+    Ms = [int(p.shape[2]) for p in preds]
+    if not chamfer_pyramid_supported(Ms, N):
+        raise SonetHipError("chamfer_pyramid: need M_l <= %d and N <= %d, got M=%s N=%d" % (CHAMFER_PYRAMID_MAX_M, CHAMFER_PYRAMID_MAX_N, Ms, N))
+    return dev, B, Ms, N
+
+
+def _ptr_array(ts):
+    """The host array of device pointers a pyramid entry reads (None: a NULL entry)."""
+    import ctypes
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _int_array(vs):
+    import ctypes
+    return (ctypes.c_int * len(vs))(*vs)
+
+
+def chamfer_pyramid_terms(preds, gt, want_nn=True, want_elems=True):
+    """preds: 1 to 3 clouds B x 3 x M_l, gt B x 3 x N f32 -> ``ChamferPyramidTerms`` (include/sonet_hip.h: sonet_chamfer_pyramid_loss_f32):
+    what ``chamfer_terms(preds[l], gt)`` gives for every level, bit for bit, from one launch plus a small one for the sums."""
+    dev, B, Ms, N = _chk_pyramid(preds, gt)
+    L = len(Ms)
+    lib = _lib.load()
+    r = ChamferPyramidTerms()
+    r.N, r.levels = N, []
+    tot = B * (sum(Ms) + L * N)
+    nn = torch.empty((tot,), dtype=torch.int32, device=dev) if want_nn else None
+    el = torch.empty((tot,), dtype=torch.float32, device=dev) if want_elems else None
+    f64 = torch.empty((2 * B * L + lib.sonet_chamfer_pyramid_ws_size(B, L, *(Ms + [0, 0])[:3], N) // 8,), dtype=torch.float64, device=dev)
+    r.sums = f64[:2 * B * L].view(B, L, 2)
+    off = 0
+    for l, M in enumerate(Ms):
+        t = ChamferTerms()
+        t.M, t.N, t.sums = M, N, r.sums[:, l]
+        t.nn_pg = t.nn_gp = t.elem_fwd = t.elem_bwd = None
+        if want_nn:
+            t.nn_pg, t.nn_gp = nn[off:off + B * M].view(B, M), nn[off + B * M:off + B * (M + N)].view(B, N)
+        if want_elems:
+            t.elem_fwd, t.elem_bwd = el[off:off + B * M].view(B, M), el[off + B * M:off + B * (M + N)].view(B, N)
+        off += B * (M + N)
+        r.levels.append(t)
+    lv = r.levels
+    _launch(dev, "chamfer_pyramid_loss", lib.sonet_chamfer_pyramid_loss_f32, _ptr_array(preds), ptr(gt), _ptr_array([t.nn_pg for t in lv]),
+            _ptr_array([t.nn_gp for t in lv]), _ptr_array([t.elem_fwd for t in lv]), _ptr_array([t.elem_bwd for t in lv]), ptr(r.sums),
+            ptr(f64[2 * B * L:]), B, L, _int_array(Ms), N)
+    return r
+
+
+def chamfer_pyramid_grad(preds, gt, terms, gscale):
+    """d(sum over l of gf_l * forward_loss_l + gb_l * backward_loss_l) / d preds[l] at the indices and elements of ``terms`` (a
+    ``ChamferPyramidTerms`` or a list of ``ChamferTerms``); gscale: L x 2 f32 (gf_l, gb_l) on the device -> (list of dpred_l B x 3 x M_l
+    f32, bad L i32: per level the index entries outside their range, which contribute nothing).  One launch, no host sync; level l is
+    ``chamfer_grad(preds[l], gt, terms.levels[l], gscale[l])`` bit for bit."""
+    dev, B, Ms, N = _chk_pyramid(preds, gt)
+    L = len(Ms)
+    lv = terms.levels if isinstance(terms, ChamferPyramidTerms) else list(terms)
+    if len(lv) != L:
+        raise SonetHipError("chamfer_pyramid_grad: %d levels of terms for %d predicted clouds" % (len(lv), L))
+    for t, M in zip(lv, Ms):
+        if t.nn_pg is None or t.elem_fwd is None:
+            raise SonetHipError("chamfer_pyramid_grad needs the indices and the elements (chamfer_pyramid_terms(want_nn=True, want_elems=True))")
+        for x, name, dtype, shape in ((t.nn_pg, "nn_pg", torch.int32, (B, M)), (t.nn_gp, "nn_gp", torch.int32, (B, N)),
+                                      (t.elem_fwd, "elem_fwd", torch.float32, (B, M)), (t.elem_bwd, "elem_bwd", torch.float32, (B, N))):
+            _chk(x, name, dtype)
+            if tuple(x.shape) != shape:
+                raise SonetHipError("%s must have shape %s, got %s" % (name, shape, tuple(x.shape)))
+        _same_device(gt, t.nn_pg, t.nn_gp, t.elem_fwd, t.elem_bwd)
+    _chk(gscale, "gscale", torch.float32)
+    if tuple(gscale.shape) != (L, 2):
+        raise SonetHipError("gscale must have shape %s, got %s" % ((L, 2), tuple(gscale.shape)))
+    _same_device(gt, gscale)
+    flat = torch.empty((3 * B * sum(Ms),), dtype=torch.float32, device=dev)
+    dpreds, off = [], 0
+    for M in Ms:
+        dpreds.append(flat[off:off + 3 * B * M].view(B, 3, M))
+        off += 3 * B * M
+    bad = torch.empty((L,), dtype=torch.int32, device=dev)
+    _launch(dev, "chamfer_pyramid_grad", _lib.load().sonet_chamfer_pyramid_grad_f32, _ptr_array(preds), ptr(gt),
+            _ptr_array([t.nn_pg for t in lv]), _ptr_array([t.nn_gp for t in lv]), _ptr_array([t.elem_fwd for t in lv]),
+            _ptr_array([t.elem_bwd for t in lv]), ptr(gscale), _ptr_array(dpreds), ptr(bad), B, L, _int_array(Ms), N)
+    return dpreds, bad
+
+
+_pyramid_denominators = {}
+
+
+def _pyramid_den(dev, Ms, N):
+    """L x 2 f64 on ``dev``: (M_l, N) per level, what a cloud's two sums are divided by (made once per set of sizes: an H2D copy)."""
+    key = (dev, tuple(Ms), N)
+    den = _pyramid_denominators.get(key)
+    if den is None:
+        den = _pyramid_denominators[key] = torch.tensor([[float(M), float(N)] for M in Ms], dtype=torch.float64).to(dev)
+    return den
+
+
+class _ChamferPyramidLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gt, *preds):
+        t = chamfer_pyramid_terms(list(preds), gt)
+        B, L = gt.shape[0], len(preds)
+        den = _pyramid_den(gt.device, [p.shape[2] for p in preds], t.N)
+        arrays = (t.sums / den).float()                                  # B x L x 2: per cloud, the mean of its elements
+        scalars = (t.sums.sum(dim=0) / (den * B)).float()                # L x 2: f64 sums on the device, rounded once
+        saved = [gt]
+        out = []
+        for l in range(L):
+            lv = t.levels[l]
+            saved += [preds[l], lv.nn_pg, lv.nn_gp, lv.elem_fwd, lv.elem_bwd]
+            out += [scalars[l, 0], scalars[l, 1], arrays[:, l, 0], arrays[:, l, 1]]
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(*[o for k, o in enumerate(out) if k % 4 >= 2])
+        ctx.set_materialize_grads(False)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        gt, L = saved[0], (len(saved) - 1) // 5
+        preds, levels = [], []
+        for l in range(L):
+            p, nn_pg, nn_gp, elem_fwd, elem_bwd = saved[1 + 5 * l:6 + 5 * l]
+            t = ChamferTerms()
+            t.nn_pg, t.nn_gp, t.elem_fwd, t.elem_bwd, t.M, t.N = nn_pg, nn_gp, elem_fwd, elem_bwd, p.shape[2], gt.shape[2]
+            preds.append(p)
+            levels.append(t)
+        gs = [grads[4 * l + d] for l in range(L) for d in (0, 1)]
+        if any(g is None for g in gs):
+            zero = torch.zeros((), dtype=torch.float32, device=gt.device)
+            gs = [zero if g is None else g for g in gs]
+        gscale = torch.stack([g.float() for g in gs]).view(L, 2)
+        dpreds, _bad = chamfer_pyramid_grad(preds, gt, levels, gscale)
+        return (None,) + tuple(dpreds)
+
+
+def chamfer_pyramid_loss(preds, gt):
+    """Every Chamfer term of an autoencoder step (models/autoencoder.py:83-98) as one operator: preds a list of 1 to 3 clouds
+    B x 3 x M_l (each may require a gradient), gt B x 3 x N -> a list with, per level, (forward_loss, backward_loss: f32 scalars,
+    differentiable with respect to preds[l]; forward_loss_array, backward_loss_array: B f32, not differentiable).  One
+    ``sonet_chamfer_pyramid_loss_f32`` call forward, one ``sonet_chamfer_pyramid_grad_f32`` call backward, whatever outputs are used."""
+    _chk_pyramid(preds, gt)
+    out = _ChamferPyramidLoss.apply(gt, *preds)
+    return [tuple(out[4 * l:4 * l + 4]) for l in range(len(preds))]
+
+
 # ------------------------------------------------------------------------------------------ upconv3x3
 # Tile extents of csrc/upconv.hip (include/sonet_hip.h SONET_UPCONV_*): a workgroup covers UPCONV_TILE_PIXELS consecutive low-resolution
 # pixels of the flattened (b, i, j) axis and UPCONV_COUT_BLOCK output channels, and stages UPCONV_K_CHUNK input channels at a time.
