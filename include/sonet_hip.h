@@ -712,7 +712,11 @@ int sonet_linear_act_f32(const float *x, const float *W, const float *scale, con
  * g_pooled [B][C][M] at the arg-max positions pos [B][C][M] (i32 in [0, L); out-of-range entries are ignored).
  *   gx1 [B][C1][L], gx2 [B][C2][L]  <-  sum over entries (c, m) with pos == l of g_pooled[b][c][m] * W[c][:]
  * W [C][C1+C2] row-major f32.  Dense outputs (zero where nothing hits), C*M*(C1+C2) MACs per cloud instead of
- * C*L*(C1+C2).  ws: sonet_pooled_dgrad_ws_size bytes.  Deterministic (entries sorted per 64-column tile). */
+ * C*L*(C1+C2).  ws: sonet_pooled_dgrad_ws_size bytes.  Deterministic (entries sorted per 64-column tile).
+ * Alignment (the entries do not check it; sonet_hip/ops.py copies a misaligned W and allocates the rest): when C1 + C2 is a multiple
+ * of 4, W is read with 16-byte loads and must sit on a 16-byte boundary; ws on a 4-byte boundary; the bfloat16 outputs of _obf16 on a
+ * 4-byte boundary when L is even (two columns leave as one dword; _mfma_bf16 refuses others), on a 16-byte boundary for _mfma_bf16's
+ * 128-column workgroups when L is a multiple of 8. */
 size_t sonet_pooled_dgrad_ws_size(int B, int C, int M, int L);
 /* The matching wgrad, with g_pooled and pos TRANSPOSED to [B][M][C] (coalesced entry walks):
  * gw_partial[b][c][ci] = sum_m g_pooled[b][m][c] * x[b][ci][pos[b][m][c]] (x [B][Ci][L]; positions

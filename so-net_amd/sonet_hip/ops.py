@@ -2285,6 +2285,14 @@ def pooled_dgrad(g_pooled, pos_i32, weight2d, C1, C2, L, out_dtype=torch.float32
     _chk(weight2d, "weight", torch.float32, 2)
     dev = _same_device(g_pooled, pos_i32, weight2d)
     B, C, M = g_pooled.shape
+    # (the kernels index pos by g's extents and W by C x (C1 + C2): a short pos or weight would be read past its end)
+    if tuple(pos_i32.shape) != (B, C, M):
+        raise SonetHipError("pooled_dgrad: pos must have g_pooled's shape %s, got %s" % ((B, C, M), tuple(pos_i32.shape)))
+    if int(C1) <= 0 or int(C2) < 0 or int(L) <= 0:
+        raise SonetHipError("pooled_dgrad: C1 > 0, C2 >= 0 and L > 0, got C1=%d C2=%d L=%d" % (C1, C2, L))
+    if tuple(weight2d.shape) != (C, C1 + C2):
+        raise SonetHipError("pooled_dgrad: weight must be C x (C1 + C2) = %s, got %s" % ((C, C1 + C2), tuple(weight2d.shape)))
+    weight2d = _aligned16(weight2d)                               # (16-byte loads of W when (C1 + C2) % 4 == 0)
     lib = _lib.load()
     ws = _ws(lib.sonet_pooled_dgrad_ws_size, dev, B, C, M, int(L))
     gx1 = torch.empty((B, C1, int(L)), dtype=out_dtype, device=dev)
@@ -2341,6 +2349,11 @@ def pooled_wgrad(g_pooled_t, pos_i32_t, x, xaff=None):
     dev = _same_device(g_pooled_t, pos_i32_t, x)
     B, M, C = g_pooled_t.shape
     Ci, L = x.shape[1], x.shape[2]
+    # (the kernel indexes pos by g's extents and x by g's cloud count: a short pos or x would be read past its end)
+    if tuple(pos_i32_t.shape) != (B, M, C):
+        raise SonetHipError("pooled_wgrad: pos_t must have g_pooled_t's shape %s, got %s" % ((B, M, C), tuple(pos_i32_t.shape)))
+    if x.shape[0] != B:
+        raise SonetHipError("pooled_wgrad: x must hold B = %d clouds, got shape %s" % (B, tuple(x.shape)))
     part = torch.empty((B, C, Ci), dtype=torch.float32, device=dev)
     lib = _lib.load()
     if xaff is not None:

@@ -3,7 +3,7 @@ its text, against tests/golden/ops/, without a GPU (tools/op_calls.py: the wrapp
 recording stand-in for the library).  calls.txt.xz is the output of the tool on a checkout of the commit BEFORE the wrappers' building
 blocks were merged, calls.summary.txt its outline per wrapper: they are that commit's behaviour and are never regenerated from the tree
 under test.  tightened.txt holds the cases this tree refuses although that commit launched them (scale / shift / bias of the wrong length
-or dtype, which the kernels would have read past or misread): each replaces the recorded case of the same call and must be a refusal."""
+or dtype, a pos / weight / x of the pooled-layer backward of the wrong shape, which the kernels would have read past or misread): each replaces the recorded case of the same call and must be a refusal."""
 import difflib
 import lzma
 import os

@@ -172,6 +172,34 @@ def test_sparse_input_gradient_kernels_agree(B, C, M, C1, C2, L, monkeypatch):
         assert float((outs[name].cpu().double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max()), name
 
 
+def _balanced_layouts():
+    import pooled_bwd_ref as R
+    return [s[0] for s in R.SHAPES if s[4] % 4 == 0] + [n for n, c in R.LISTS.items() if c[3] % 4 == 0]
+
+
+@pytest.mark.parametrize("name", _balanced_layouts())
+def test_one_channel_and_column_owned_kernels_are_bit_exact_twins(name, monkeypatch):
+    """pooled_bwd.hip calls the column-owned kernel the bit-exact twin of the one-channel kernel: both, forced on the layouts of
+    tests/pooled_bwd_ref.py whose width is a multiple of 4 (the list and tile edges of tests/test_gpu_pooled_bwd.py), equal the numpy
+    restatement of ONE chain per (column, channel) in id order, f32 and bf16 output"""
+    import pooled_bwd_ref as R
+    from sonet_hip import ops
+    g, pos, W, C1, L = R.dgrad_named(name)
+    want = {out: R.dgrad_plain(g, pos, W, C1, L, out) for out in ("f32", "bf16")}
+    for env in ({"SONET_PD_ONE": "1"}, {"SONET_PD_KERNEL": "4"}):
+        for k in ("SONET_PD_ONE", "SONET_PD_KERNEL"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for out, dt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+            got = ops.pooled_dgrad(cu(g), cu(pos), cu(W), C1, W.shape[1] - C1, L, out_dtype=dt)
+            for a, b in zip(got, want[out]):
+                assert (a is None) == (b is None)
+                if a is not None:
+                    a = a.cpu().view(torch.int16).numpy().view(np.uint16) if out == "bf16" else a.cpu().numpy()
+                    assert R.same_bits(a, b), (name, env, out)
+
+
 # ------------------------------------------------------------------------------------------ measured-slower records of round 5
 # (moved here from tests/test_gpu_segpool.py in round 6: the kernels live in the variants build only, as DESIGN section 1 requires)
 from argparse import Namespace  # noqa: E402
