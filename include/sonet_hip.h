@@ -877,6 +877,38 @@ int sonet_seg_metrics_f32(const float *score, const int64_t *seg, const int64_t 
                           int32_t *pred_out /* may be NULL */, int32_t *correct, double *nll_sum, int32_t *inter, int32_t *pred_cnt,
                           int32_t *gt_cnt, double *iou, int32_t *bad, void *ws, int B, int C, int N, sonet_stream_t stream);
 /* ------------------------------------------------------------------------------------------------
+ * ce_loss / ce_grad  -- softmax cross-entropy as one operator with its own gradient (so-net_amd/csrc/ce_loss.hip)
+ *   reference: models/losses.py:30-43 (CrossEntropyLossSeg: log_softmax on a 4-D view + NLLLoss), models/classifier.py:95,105
+ *   (nn.CrossEntropyLoss on the classifier's B x C scores), modelnet/train.py:81-87 (loss, torch.max and the correct mask per test batch)
+ * score [B][C][N] f32 (the layout of score_segmenter; N = 1 is the classifier's [B][C]), target [B][N] i64.
+ * sonet_ce_loss_f32 reads the scores once; everything after the load is float64.  Per point: m the maximum, S = sum exp(x - m) (one pass,
+ * rescaled when the running maximum moves), lse = m + log(S), nll = (m - x[target]) + log(S) -- two non-negative terms.  Outputs:
+ *   lse [B*N] f64 (nullable): kept for sonet_ce_grad_f32;
+ *   nll_sum [B] f64: per cloud the sum of nll in a fixed order -- lanes, waves, workgroup partials in ws added in index order by a
+ *     second launch.  No floating-point atomics: two runs give the same bits;
+ *   pred [B*N] i32 (nullable): arg-max over the C scores as torch.max(dim=1) on CPU tensors -- the first of equal maxima, a NaN beats
+ *     every number, the first NaN wins;
+ *   correct [B] i32: points with pred == target;   bad [B] i32: points whose target is outside [0, C);
+ *   confusion [C][C] i64 (nullable): the entry ADDS 1 to confusion[target][pred] per point with integer atomics (the caller zeroes it).
+ * A point with a bad target adds 0 to nll_sum and to correct, touches no confusion entry and is never used as an index.  Non-finite
+ * scores are not bad inputs: a point whose scores hold a NaN, a +inf, or nothing but -inf has lse = NaN and makes its cloud's nll_sum
+ * NaN (as log_softmax does); a -inf score on the target beside finite ones gives nll = +inf.
+ * ws: sonet_ce_loss_ws_size bytes (0 for non-positive sizes), 8-byte aligned; two launches, one when N == 1.
+ * sonet_ce_grad_f32: grad[b][c][n] = f32((exp(x - lse) - [c == target]) * (double)gout[0] * scale), float64 until the one rounding; gout
+ * is one f32 ON THE DEVICE (the upstream gradient: no host read), scale a host double (1 / (B N) for the mean, 1 for the sum).  A point
+ * with a bad target gets zeros; a point whose lse is NaN gets NaN in every class, and no other point does.  One launch.
+ * 1 <= C <= sonet_ce_max_c(), B N < 2^31, B <= 65535 unless N == 1; lse, nll_sum, confusion and ws 8-byte aligned: otherwise both
+ * entries return an error before any launch.  sonet_ce_block_points(): the points of one forward workgroup.
+ * ---------------------------------------------------------------------------------------------- */
+int sonet_ce_max_c(void);
+int sonet_ce_block_points(void);
+size_t sonet_ce_loss_ws_size(int B, int C, int N);
+int sonet_ce_loss_f32(const float *score, const int64_t *target, double *lse /* may be NULL */, double *nll_sum,
+                      int32_t *pred /* may be NULL */, int32_t *correct, int32_t *bad, int64_t *confusion /* may be NULL */, void *ws,
+                      int B, int C, int N, sonet_stream_t stream);
+int sonet_ce_grad_f32(const float *score, const int64_t *target, const double *lse, const float *gout, double scale, float *grad, int B,
+                      int C, int N, sonet_stream_t stream);
+/* ------------------------------------------------------------------------------------------------
  * retrieval_lists  -- class-restricted ranked neighbour lists: for every query shape the members of its own class, nearest first
  *   reference: shrec16/test.py:68-99 (per test shape: torch.eq + torch.nonzero over the predicted labels, torch.norm of the gathered
  *   K x 55 rows, torch.sort, the first 1000 rows written to a file)
@@ -1021,6 +1053,11 @@ int sonet_pooled_dgrad_tail_f32(const float *g_pooled, const int32_t *pos, const
                                 int L, void *ws, float *gx1, float *gx2, const float *col0, const int32_t *pos0,
                                 const float *sraw, const float *ssc, const float *ssh, int srelu, void *tail_ws, double *sums,
                                 sonet_stream_t stream);
+
+/* sonet_ce_loss_f32 with float32 expf / logf after the load instead of float64: the timing record of what the float64 arithmetic costs
+ * (tools/bench_ce_loss.py); same arguments, same launches. */
+int sonet_ce_loss_f32_sp(const float *score, const int64_t *target, double *lse, double *nll_sum, int32_t *pred, int32_t *correct,
+                         int32_t *bad, int64_t *confusion, void *ws, int B, int C, int N, sonet_stream_t stream);
 #endif /* SONET_VARIANTS */
 
 /* Packs of a matrix given by element strides: element (o, c) = W[o * row_stride + c * col_stride] for o < rows, c < Cin; rows in

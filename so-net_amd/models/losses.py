@@ -36,15 +36,34 @@ def robust_norm(var):
     return ((var ** 2).sum(dim=2) + 1e-8).sqrt()
 
 
-class CrossEntropyLossSeg(nn.Module):
-    """Per-point NLL over B x classes x N scores (models/losses.py:30-43)."""
+def _takes_ce_operator(fused, inputs, targets, weight, dims):
+    """The routing rule of the two cross-entropy classes: the one-operator path (``ops.ce_loss``) when the option is set and the scores
+    are CUDA float32 of ``dims`` dimensions with int64 targets, no class weight and a class count inside the operator's extent."""
+    return (bool(fused) and weight is None and inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == dims
+            and targets.is_cuda and targets.dtype == torch.int64 and targets.dim() == dims - 1
+            and _ops.ce_supported(inputs.shape[1], inputs.shape[0], inputs.shape[2] if dims == 3 else 1))
 
-    def __init__(self, weight=None, size_average=True):
+
+class CrossEntropyLossSeg(nn.Module):
+    """Per-point NLL over B x classes x N scores (models/losses.py:30-43).
+
+    ``fused=True``: CUDA float32 scores without a class weight go through ``ops.ce_loss`` -- one forward call (float64 after the load,
+    deterministic by construction) and one gradient launch; ``last_bad`` then holds the B int32 counts of targets outside [0, C) of the
+    last such call (a device tensor, never read on the host here).  Every other case -- ``fused=False`` included, which launches nothing
+    new -- takes the path below."""
+
+    def __init__(self, weight=None, size_average=True, fused=False):
         super().__init__()
         self.nll_loss = nn.NLLLoss(weight, reduction="mean" if size_average else "sum")
         self.size_average = size_average
+        self.fused = fused
+        self.last_bad = None
 
     def forward(self, inputs, targets):
+        if _takes_ce_operator(self.fused, inputs, targets, self.nll_loss.weight, 3):
+            loss, self.last_bad = _ops.ce_loss(inputs.contiguous(), targets.contiguous(), "mean" if self.size_average else "sum",
+                                               want_bad=True)
+            return loss
         logp = F.log_softmax(inputs.unsqueeze(3), dim=1)
         if logp.is_cuda and self.nll_loss.weight is None:
             # the same sum as a gather + a plain reduction: on the GPU NLLLoss's 4-D forward adds its block partials atomically, so its
@@ -52,6 +71,24 @@ class CrossEntropyLossSeg(nn.Module):
             picked = -torch.gather(logp, 1, targets.unsqueeze(1).unsqueeze(3)).squeeze(1)
             return picked.mean() if self.size_average else picked.sum()
         return self.nll_loss(logp, targets.unsqueeze(2))
+
+
+class CrossEntropyLossCls(nn.Module):
+    """The classifier's criterion (models/classifier.py:95,105: ``torch.nn.CrossEntropyLoss()`` on B x classes scores and B labels).
+    ``fused=True`` routes as ``CrossEntropyLossSeg`` does (``ops.ce_loss`` with N = 1, ``last_bad``); otherwise, and by default, it IS
+    ``nn.CrossEntropyLoss``."""
+
+    def __init__(self, fused=False):
+        super().__init__()
+        self.criterion = nn.CrossEntropyLoss()
+        self.fused = fused
+        self.last_bad = None
+
+    def forward(self, inputs, targets):
+        if _takes_ce_operator(self.fused, inputs, targets, None, 2):
+            loss, self.last_bad = _ops.ce_loss(inputs.contiguous(), targets.contiguous(), "mean", want_bad=True)
+            return loss
+        return self.criterion(inputs, targets)
 
 
 class ChamferLoss(nn.Module):

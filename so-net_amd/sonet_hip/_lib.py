@@ -182,6 +182,11 @@ SIGNATURES = {
     "sonet_upconv3x3_wgrad_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "sonet_seg_metrics_ws_size": [_i, _i, _i],
     "sonet_seg_metrics_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_ce_max_c": [],
+    "sonet_ce_block_points": [],
+    "sonet_ce_loss_ws_size": [_i, _i, _i],
+    "sonet_ce_loss_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "sonet_ce_grad_f32": [_vp, _vp, _vp, _vp, ctypes.c_double, _vp, _i, _i, _i, _vp],
     "sonet_retrieval_chunk_keys": [],
     "sonet_retrieval_ws_size": [_i, _i, _i, _i],
     "sonet_retrieval_lists_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
@@ -219,6 +224,7 @@ _RESTYPES = {
     "sonet_upconv3x3_dgrad_pack_size": ctypes.c_size_t,
     "sonet_upconv3x3_wgrad_ws_size": ctypes.c_size_t,
     "sonet_seg_metrics_ws_size": ctypes.c_size_t,
+    "sonet_ce_loss_ws_size": ctypes.c_size_t,
     "sonet_retrieval_ws_size": ctypes.c_size_t,
 }
 
@@ -229,6 +235,7 @@ VARIANT_SIGNATURES = {
     "sonet_pointmlp_h3_kmax_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp],
     "sonet_pooled_dgrad_tail_ws_size": [_i, _i, _i],
     "sonet_pooled_dgrad_tail_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "sonet_ce_loss_f32_sp": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """Evaluation loops on the device: per-epoch totals with one host transfer at the end (part segmentation: loss, accuracy and IoU;
-autoencoder: the Chamfer test loss -- ``ChamferEvaluator`` / ``evaluate_autoencoder`` at the end of this file).
+autoencoder: the Chamfer test loss -- ``ChamferEvaluator`` / ``evaluate_autoencoder``; classification: loss, accuracy and the confusion
+table -- ``ClsEvaluator`` / ``evaluate_classification`` at the end of this file).
 
 The reference's test loop (part-seg/train.py:75-104) copies every batch's B x 50 x N score tensor to the host and runs
 ``losses.compute_iou``, a Python double loop over clouds and parts.  Here one ``sonet_seg_metrics_f32`` call per batch reads the
@@ -138,4 +139,82 @@ def evaluate_autoencoder(encoder, decoder, assembler, batch_size, evaluator=None
             node, node_knn_I = (batch[4], batch[5]) if shapenet else (batch[3], batch[4])
             predicted_pc = decoder(encoder(pc, sn, node, node_knn_I, False, None))
             ev.update(predicted_pc.float().contiguous(), pc.contiguous())
+    return ev.result()
+
+
+class ClsEvaluator:
+    """Epoch totals of the classification test loop (modelnet/train.py:70-90, which calls ``.cpu()`` on every batch).  ``update`` makes
+    one ``ops.ce_terms`` call -- loss terms, arg-max by ``torch.max``'s rule, correct / bad counts and the confusion table from one read
+    of the B x classes scores -- and a few device adds (no sync, no ``.item()``); ``result`` makes the one device-to-host transfer.
+    ``test_loss`` is the number of train.py:81,89: a batch's mean loss times its batch size is that batch's sum, so the epoch's value
+    is the sum of the per-cloud losses / clouds.  ``test_accuracy``: train.py:84-90."""
+
+    def __init__(self, classes):
+        self.classes = int(classes)
+        if not ops.ce_supported(self.classes):
+            raise SonetHipError("ClsEvaluator: classes must be in [1, %d], got %r" % (ops.CE_MAX_C, classes))
+        self._loss = None              # f64 [1]: sum over clouds of the loss
+        self._ints = None              # i64 [3]: clouds, correct, bad labels
+        self._confusion = None         # i64 [classes][classes]: [label][prediction]
+
+    def reset(self):
+        if self._loss is not None:
+            self._loss.zero_()
+            self._ints.zero_()
+            self._confusion.zero_()
+
+    def update(self, score, label):
+        if isinstance(score, torch.Tensor) and score.dim() == 2 and score.shape[1] != self.classes:
+            raise SonetHipError("ClsEvaluator: scores of %d classes, the evaluator holds %d" % (score.shape[1], self.classes))
+        if not isinstance(score, torch.Tensor) or score.dim() != 2:
+            raise SonetHipError("ClsEvaluator.update: score must be a B x classes torch.Tensor")
+        if self._loss is None or self._loss.device != score.device:
+            ops._chk(score, "score", torch.float32)                   # (before the first allocation: a CPU tensor is refused as CUDA)
+            C = self.classes
+            self._loss = torch.zeros(1, dtype=torch.float64, device=score.device)
+            self._ints = torch.zeros(3, dtype=torch.int64, device=score.device)
+            self._confusion = torch.zeros((C, C), dtype=torch.int64, device=score.device)
+        t = ops.ce_terms(score, label, confusion=self._confusion)
+        self._loss += t.nll_sum.sum()
+        self._ints[0] += score.shape[0]
+        self._ints[1:] += torch.stack([t.correct.sum(), t.bad.sum()])
+        return t
+
+    def result(self):
+        if self._loss is None:
+            raise SonetHipError("ClsEvaluator.result() before any update()")
+        C = self.classes
+        host = torch.cat([self._loss, self._ints.to(torch.float64), self._confusion.view(-1).to(torch.float64)]).cpu()   # the one transfer
+        loss = float(host[0])                                         # (counts < 2^53: exact)
+        count, correct, bad = (int(v) for v in host[1:4].tolist())
+        confusion = host[4:].view(C, C).to(torch.int64).numpy()
+        if bad:
+            raise SonetHipError("classification evaluation: %d label(s) of %d clouds outside [0, %d)" % (bad, count, C))
+        if count == 0:
+            raise SonetHipError("ClsEvaluator.result() without any cloud")
+        if loss != loss:
+            raise SonetHipError("classification evaluation: the loss of %d clouds is NaN (non-finite scores; no bad label)" % count)
+        per_class = confusion.sum(axis=1)
+        seen = per_class > 0
+        class_acc = float((confusion.diagonal()[seen] / per_class[seen]).mean())
+        return {"test_loss": loss / count, "test_accuracy": correct / count, "class_accuracy": class_acc, "confusion": confusion,
+                "count": count}
+
+
+def evaluate_classification(encoder, classifier, assembler, batch_size, evaluator=None):
+    """One pass over the split of a test-mode modelnet or shrec ``BatchAssembler``: encoder, classifier and ``ClsEvaluator.update`` per
+    batch under ``no_grad`` (models/classifier.py:101-107 without the host reads), no host sync inside the loop, the last batch may be
+    short; returns ``ClsEvaluator.result()``."""
+    if assembler.recipe not in ("modelnet", "shrec") or assembler.mode == "train":
+        raise SonetHipError("evaluate_classification needs a test-mode modelnet or shrec BatchAssembler, got recipe %r mode %r"
+                            % (assembler.recipe, assembler.mode))
+    ev = ClsEvaluator(classifier.opt.classes) if evaluator is None else evaluator
+    ev.reset()
+    encoder.eval()
+    classifier.eval()
+    with torch.no_grad():
+        for batch in assembler.epoch(0, batch_size, shuffle=False):
+            pc, sn, label, node, node_knn_I = batch[:5]
+            score = classifier(encoder(pc, sn, node, node_knn_I, False, None))
+            ev.update(score.float().contiguous(), label.contiguous())
     return ev.result()

@@ -2915,6 +2915,127 @@ def seg_metrics(score, seg, label, part_offsets=None, want_pred=False):
     return r
 
 
+# ------------------------------------------------------------------------------------------ cross-entropy
+# Extents of csrc/ce_loss.hip (sonet_ce_max_c / sonet_ce_block_points): the classes a call takes, the points of one forward workgroup.
+CE_MAX_C = 256
+CE_BLOCK_POINTS = 256
+
+
+class CeTerms:
+    """Device tensors of one ``ce_terms`` call: nll_sum B f64, correct B i32, bad B i32, pred B x N i32 and lse B x N f64 (None unless
+    asked for), confusion (the caller's C x C i64 table, added to, or None); N the points per cloud."""
+    __slots__ = ("nll_sum", "correct", "bad", "pred", "lse", "confusion", "N")
+
+
+def ce_supported(C, B=1, N=1):
+    """Sizes the cross-entropy operator takes: 1 <= C <= CE_MAX_C, B N < 2^31, and B <= 65535 unless N == 1."""
+    B, C, N = int(B), int(C), int(N)
+    return 1 <= C <= CE_MAX_C and B >= 1 and N >= 1 and B * N < 1 << 31 and (N == 1 or B <= 65535)
+
+
+def _chk_ce(score, target):
+    """score B x C x N or B x C f32, target B x N or B i64 -> (score as B x C x N, target as B x N, dev, B, C, N).  (A torch tensor's
+    first element sits on a multiple of its element size, so the 8-byte alignment the C entries ask of target and lse always holds.)"""
+    if not isinstance(score, torch.Tensor) or score.dim() not in (2, 3):
+        raise SonetHipError("score must be a B x C x N or B x C torch.Tensor")
+    _chk(score, "score", torch.float32)
+    _chk(target, "target", torch.int64, score.dim() - 1)
+    if score.dim() == 2:
+        score, target = score.unsqueeze(2), target.unsqueeze(1)
+    B, C, N = score.shape
+    if tuple(target.shape) != (B, N):
+        raise SonetHipError("target must be B x N = %s, got %s" % ((B, N), tuple(target.shape)))
+    if not ce_supported(C, B, N):
+        raise SonetHipError("cross-entropy: need 1 <= C <= %d, B, N >= 1, B N < 2^31 (B <= 65535 unless N == 1), got B=%d C=%d N=%d"
+                            % (CE_MAX_C, B, C, N))
+    return score, target, _same_device(score, target), B, C, N
+
+
+def _ce_forward(score, target, dev, B, C, N, want_pred, want_lse, confusion):
+    """The forward launch on operands ``_chk_ce`` has seen: two allocations (float64: sums, lse, workspace; int32: counts, pred)."""
+    lib = _lib.load()
+    r = CeTerms()
+    r.N, r.confusion = N, confusion
+    n_lse = B * N if want_lse else 0
+    f64 = torch.empty((B + n_lse + lib.sonet_ce_loss_ws_size(B, C, N) // 8,), dtype=torch.float64, device=dev)
+    r.nll_sum = f64[:B]
+    r.lse = f64[B:B + n_lse].view(B, N) if want_lse else None
+    ints = torch.empty((2 * B + (B * N if want_pred else 0),), dtype=torch.int32, device=dev)
+    r.correct, r.bad = ints[:B], ints[B:2 * B]
+    r.pred = ints[2 * B:].view(B, N) if want_pred else None
+    _launch(dev, "ce_loss", lib.sonet_ce_loss_f32, ptr(score), ptr(target), ptr(r.lse), ptr(r.nll_sum), ptr(r.pred), ptr(r.correct), ptr(r.bad),
+            ptr(confusion), ptr(f64[B + n_lse:]), B, C, N)
+    return r
+
+
+def ce_terms(score, target, want_pred=False, want_lse=False, confusion=None):
+    """score B x C x N f32 (score_segmenter's layout) or B x C, target B x N or B i64 -> ``CeTerms`` (include/sonet_hip.h:
+    sonet_ce_loss_f32).  confusion: a contiguous C x C i64 device table the call ADDS its counts to.  Nothing is read back."""
+    score, target, dev, B, C, N = _chk_ce(score, target)
+    if confusion is not None:
+        _chk(confusion, "confusion", torch.int64, 2)
+        if tuple(confusion.shape) != (C, C):
+            raise SonetHipError("confusion must be C x C = %s, got %s" % ((C, C), tuple(confusion.shape)))
+        _same_device(score, confusion)
+    return _ce_forward(score, target, dev, B, C, N, want_pred, want_lse, confusion)
+
+
+def _ce_grad_launch(score, target, lse, gout, scale, dev, B, C, N, shape):
+    grad = torch.empty(shape, dtype=torch.float32, device=dev)
+    _launch(dev, "ce_grad", _lib.load().sonet_ce_grad_f32, ptr(score), ptr(target), ptr(lse), ptr(gout), scale, ptr(grad), B, C, N)
+    return grad
+
+
+def ce_grad(score, target, lse, gout, scale):
+    """d(scale * gout * sum of nll) / d score at the ``lse`` of a ``ce_terms(want_lse=True)`` call: gout one f32 on the device, scale a
+    host float -> f32 of score's shape (include/sonet_hip.h: sonet_ce_grad_f32).  One launch, no host sync."""
+    shape = score.shape if isinstance(score, torch.Tensor) else None
+    score, target, dev, B, C, N = _chk_ce(score, target)
+    _chk(lse, "lse", torch.float64)
+    _chk(gout, "gout", torch.float32)
+    if lse.numel() != B * N or gout.numel() != 1:
+        raise SonetHipError("lse must hold B N = %d elements and gout one, got %d and %d" % (B * N, lse.numel(), gout.numel()))
+    _same_device(score, lse, gout)
+    return _ce_grad_launch(score, target, lse, gout, float(scale), dev, B, C, N, shape)
+
+
+class _CeLoss(torch.autograd.Function):
+    """``checked``: what ``_chk_ce`` returned for (score, target) -- the operands are looked at once per call, not once per layer of
+    wrappers, and not again in the backward."""
+
+    @staticmethod
+    def forward(ctx, score, mean, checked):
+        score3, target, dev, B, C, N = checked
+        needs = ctx.needs_input_grad[0]
+        t = _ce_forward(score3, target, dev, B, C, N, False, needs, None)
+        scale = 1.0 / (B * N) if mean else 1.0
+        if needs:
+            ctx.save_for_backward(score, target, t.lse)            # (score3 is score's memory: the same pointer)
+            ctx.ce = (scale, dev, B, C, N, score.shape)
+        ctx.mark_non_differentiable(t.bad)
+        total = t.nll_sum.sum()                                       # f64, on the device
+        return (total / (B * N) if mean else total).float(), t.bad
+
+    @staticmethod
+    def backward(ctx, gout, _gbad):
+        score, target, lse = ctx.saved_tensors
+        if gout.dtype != torch.float32 or not gout.is_contiguous():
+            gout = gout.float().contiguous()
+        return _ce_grad_launch(score, target, lse, gout, *ctx.ce), None, None
+
+
+def ce_loss(score, target, reduction="mean", want_bad=False):
+    """Softmax cross-entropy as one operator: score B x C x N or B x C f32 (may require a gradient), target B x N or B i64 -> the f32
+    scalar mean (or ``reduction="sum"``) over all B N points of lse - score[target], summed in float64 on the device and rounded once;
+    differentiable in ``score``.  A target outside [0, C) adds nothing and gets a zero gradient; the denominator stays B N
+    (``want_bad=True``: also the B i32 counts of such targets, not differentiable).  Forward one ``sonet_ce_loss_f32`` call, which keeps
+    lse only when ``score`` requires a gradient; backward one ``sonet_ce_grad_f32`` call, whatever the upstream gradient."""
+    if reduction not in ("mean", "sum"):
+        raise SonetHipError("ce_loss: reduction must be 'mean' or 'sum', got %r" % (reduction,))
+    loss, bad = _CeLoss.apply(score, reduction == "mean", _chk_ce(score, target))
+    return (loss, bad) if want_bad else loss
+
+
 # ------------------------------------------------------------------------------------------ retrieval lists
 RETRIEVAL_MAX_TOP = 1024
 RETRIEVAL_MAX_D = 1024
